@@ -128,6 +128,8 @@ def parse():
     ap.add_argument("--sv-cpu-full-mb", type=int, default=300, help="up to this genome size the CPU legs of sv_e2e run on the whole file, above it on a bounded sample of contigs")
     ap.add_argument("--full-line", action="store_true", help="print the detailed record (tens of KB) instead of the compact line")
     ap.add_argument("--ingest-mb", type=int, default=8, help="Mb per contig (2 contigs, 30x, 100-bp reads) of the BAM the ingest pass reads")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the float64 coverage bins of the last timed step to "
+                    "DIR/coverage_bins.npy (a seeded sample beyond %d MB, see dump_outputs)" % (DUMP_BUDGET // 10**6))
     return ap.parse_args()
 
 
@@ -256,6 +258,7 @@ def main():
     t_cov = time.perf_counter() - t0
     t_cov = rank_max(t_cov)
     ms_per_step = 1e3 * t_cov / args.steps
+    dumped = out_all.cpu().numpy() if args.dump_outputs else None     # the bins of the last timed step, copied outside the timed region
     kern_all = sorted(a.elapsed_time(b) for a, b in ev_pairs)
     kern_ms = sum(kern_all) / len(kern_all)                                      # avg cov_accumulate launch (whole genome)
     # bytes the launch's OWN input layout holds: 8-byte packed records + 8 B/bin.  (SURVEY §8(d)'s 12 B/read describes the
@@ -494,6 +497,9 @@ def main():
         result["coverage_sv"] = svres
         del out_sv
         hist_sv.close()
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, {"coverage_bins": dumped}, rank, world)
+        del dumped
     del reads, outs, out_all, packed, binned
     hist.close()
     torch.cuda.empty_cache()
@@ -1103,6 +1109,31 @@ def emit(result, args):
         line.pop(k, None)
         text = json.dumps(line)
     print(text, flush=True)
+
+
+# ---- --dump-outputs: what the timed path computed, for comparing two builds output for output
+DUMP_BUDGET = 60_000_000    # bytes of array data over all ranks (under 64 MB with the .npy headers); the default run's 6 M bins fit whole
+
+
+def dump_outputs(d, arrays, rank=0, world=1):
+    """-> DIR/<name>.npy per array (DIR/<name>_rank<r>.npy at N > 1), float64.  An array larger than its share of DUMP_BUDGET is
+    written as a sample: the values at sorted indices drawn with a fixed seed, and those indices (exact in float64) beside
+    them as DIR/<name>[_rank<r>]_index.npy.  A directory created here gets a .gitignore of its own, so a dump inside a checkout leaves `git status` clean."""
+    try:
+        os.makedirs(d)
+        with open(os.path.join(d, ".gitignore"), "w") as f:
+            f.write("*\n")
+    except FileExistsError:
+        pass
+    suffix = "" if world == 1 else "_rank%d" % rank
+    share = DUMP_BUDGET // (len(arrays) * world)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, share // 16, replace=False))    # value + index, 8 bytes each
+            np.save(os.path.join(d, name + suffix + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(d, name + suffix + ".npy"), a)
 
 
 def shared_bucket_sizes(total, seed=99):

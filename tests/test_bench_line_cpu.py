@@ -97,3 +97,26 @@ def test_compact_line_sheds_sections_before_it_breaks_the_budget(bench, capsys, 
     assert len(out) <= bench.LINE_BUDGET
     line = json.loads(out)
     assert "roofline" in line and "sv_e2e" not in line and "sv_e2e" in line["roofline"]["sections"]
+
+
+def test_dump_outputs_whole_below_the_budget_seeded_sample_above(bench, tmp_path):
+    """--dump-outputs: float64 .npy files under the budget; an array too large for it becomes the same seeded sample on every run,
+    with its indices beside it; a directory the dump creates ignores itself in git"""
+    import numpy as np
+    small = np.arange(1000, dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "a"), {"coverage_bins": small})
+    got = np.load(tmp_path / "a" / "coverage_bins.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small)
+    assert (tmp_path / "a" / ".gitignore").read_text() == "*\n"
+    big = np.random.default_rng(0).random(bench.DUMP_BUDGET // 8 + 1)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"coverage_bins": big})
+    total = sum(f.stat().st_size for f in (tmp_path / "b").glob("*.npy"))
+    assert total <= 64 * 10**6
+    idx = np.load(tmp_path / "b" / "coverage_bins_index.npy")
+    val = np.load(tmp_path / "b" / "coverage_bins.npy")
+    assert np.all(np.diff(idx) > 0) and np.array_equal(val, big[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "coverage_bins_index.npy"))
+    bench.dump_outputs(str(tmp_path / "r"), {"coverage_bins": big}, rank=1, world=2)
+    assert sorted(f.name for f in (tmp_path / "r").glob("*.npy")) == ["coverage_bins_rank1.npy", "coverage_bins_rank1_index.npy"]
+    assert sum(f.stat().st_size for f in (tmp_path / "r").glob("*.npy")) <= 32 * 10**6
