@@ -343,6 +343,36 @@ int tdt_region_counts_device(tdt_ctx *ctx, const int32_t *d_start, const int32_t
                              size_t n, int tid, int max_span, int64_t contig_length, const int32_t *d_q_start, const int32_t *d_q_end,
                              const int32_t *d_q_bp, size_t nq, int min_q, int64_t max_ins, int64_t *d_out);
 
+/* ---- the evidence store: the scan's placed records packed for the variant stage ----------------------------------- *
+ * Filled batch by batch during the signal scan (tdt_evstore_append_device: device field arrays of one decoded batch, whose first n
+ * records are placed, tid >= 0; tdt_evstore_append: the same from host arrays, uploaded first).  Records are appended in file
+ * order, so each contig of a coordinate-sorted file is one contiguous, sorted range; the caller keeps the ranges.  One record =
+ * 16 bytes {int32 start, int32 end, int32 mate_pos, uint8 bits, 3 bytes zero}; bits = TDT_EV_* below, LOW_Q / DISCORDANT
+ * evaluated with the store's min_q / max_ins (|tlen| > max_ins or mate_tid != tid).  The buffer grows on the device (a bigger
+ * allocation and a device copy) when a batch does not fit.  tdt_evstore_spans: per contig max(end - start), int32[n_contigs]. */
+#define TDT_EV_UNMAPPED 0x04u
+#define TDT_EV_MATE_UNMAPPED 0x08u
+#define TDT_EV_DUPLICATE 0x01u
+#define TDT_EV_HAS_SA 0x02u
+#define TDT_EV_LOW_Q 0x10u
+#define TDT_EV_DISCORDANT 0x20u
+typedef struct tdt_evstore tdt_evstore;
+int tdt_evstore_create(tdt_ctx *ctx, int n_contigs, int min_q, int64_t max_ins, size_t capacity, tdt_evstore **out);
+int tdt_evstore_destroy(tdt_evstore *s);
+int tdt_evstore_append_device(tdt_evstore *s, const int32_t *d_tid, const int32_t *d_pos, const int32_t *d_end, const uint8_t *d_mapq,
+                              const uint16_t *d_flag, const int32_t *d_mate_tid, const int32_t *d_mate_pos, const int32_t *d_tlen,
+                              const int64_t *d_sa_off, size_t n);
+int tdt_evstore_append(tdt_evstore *s, const int32_t *tid, const int32_t *pos, const int32_t *end, const uint8_t *mapq, const uint16_t *flag,
+                       const int32_t *mate_tid, const int32_t *mate_pos, const int32_t *tlen, const int64_t *sa_off, size_t n);
+int tdt_evstore_info(tdt_evstore *s, size_t *n, size_t *capacity, void **d_records);
+int tdt_evstore_spans(tdt_evstore *s, int32_t *spans);
+/* get_region's seven sums (as tdt_region_counts) for every query of every contig in ONE launch over the store.  contigs =
+ * int64[n_contigs][5] (offset, n, max span, tid, contig length) of the store's ranges; queries = int32[nq][4] (contig row, start,
+ * end, bp); out = int64[nq][7].  Host arrays.  TDT_E_ARG when min_q / max_ins are not the ones the store was packed with,
+ * TDT_E_RANGE when a row lies outside the store or a query names no row. */
+int tdt_region_counts_packed(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *queries, size_t nq,
+                             int min_q, int64_t max_ins, int64_t *out);
+
 /* ---- coverage table text (host, threaded) ----------------------------------------------------------- *
  * The row loop of print_coverage (tiddit_coverage.pyx:30-44) for one contig: kind 0 = bed rows
  * `name \t 1+i*bin \t (i+1)*bin+1 \t value \n` (last row ends at contig_len), kind 1 = wig values, one per line.

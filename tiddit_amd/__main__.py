@@ -4,8 +4,12 @@ Same two modes and the same flags as the reference driver (tiddit/__main__.py:22
 ``--cov`` is complete (byte-identical .bed/.wig for the same alignments).  ``--sv`` runs the stages this
 repository implements — library statistics, signal extraction + coverage (device), GC (device), ploidy,
 clustering (device) — and writes the signal ``.tab`` files, ``{o}.ploidies.tab`` and
-``{o}.candidates.tab``.  Variant typing / filtering / VCF (tiddit_variant.pyx) and local assembly are out
-of scope: the run stops after the candidates table and says so.
+``{o}.candidates.tab``.  By default the run stops after the candidates table and says so.
+
+``TIDDIT_VARIANTS=1`` (one process): the scan also packs every placed record into an evidence store in HBM, and
+the native variant stage (tiddit_amd/tiddit_variant.py: typing, filters, genotypes, QUAL; regional counts in one
+device launch over the store) writes ``{o}.vcf`` with tiddit_amd/tiddit_vcf_header.py's header.  On N ranks the
+switch says so and the run stops at the candidates table.  Local assembly stays out of scope.
 """
 import argparse
 import os
@@ -310,6 +314,11 @@ def run_sv(args, version):
     # one process: the blocks of discordants / splits / clips are placed by a thread while the job goes on (tiddit_cluster takes the tables
     # over, not the files); finish_writes() below waits for it.  TIDDIT_BACKGROUND_WRITES=0: written before tiddit_signal.main returns.
     tiddit_signal.BACKGROUND_WRITES = (not multi) and os.environ.get("TIDDIT_BACKGROUND_WRITES", "1") != "0"
+    # TIDDIT_VARIANTS=1: the scan also packs every placed record into the evidence store the native variant stage reads (one process only)
+    variants_on = os.environ.get("TIDDIT_VARIANTS") == "1"
+    if variants_on and multi and rank == 0:
+        print("the native variant stage (TIDDIT_VARIANTS=1) is one-process only; this run stops at the candidates table")
+    tiddit_signal.KEEP_EVIDENCE = variants_on and not multi
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -319,6 +328,7 @@ def run_sv(args, version):
             if gc_job is not None and gc_mode == "after":
                 tiddit_signal.AFTER_SCAN.remove(start_gc)
             tiddit_signal.BACKGROUND_WRITES = False
+            tiddit_signal.KEEP_EVIDENCE = False
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:
@@ -336,6 +346,11 @@ def run_sv(args, version):
         except BaseException:
             pass
         raise
+    finally:
+        from . import tiddit_variant
+        if tiddit_variant.LIVE_STORE is not None:                        # (a store the variant stage did not take: freed here)
+            tiddit_variant.LIVE_STORE.close()
+            tiddit_variant.LIVE_STORE = None
 
 
 def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, contigs, contig_length, samples, library, coverage_data, bam_header,
@@ -398,10 +413,21 @@ def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, con
     if tiddit_signal.WRITE_SECONDS:
         T["signal files placed (writer thread, beside ploidy and clustering)"] = tiddit_signal.WRITE_SECONDS["writer thread"]
         T["  waited for the writer thread"] = tiddit_signal.WRITE_SECONDS["waited for it"]
-    if rank == 0:
-        # Variant typing / filtering / the VCF (tiddit_variant.pyx, tiddit_vcf_header.py) are outside this build's scope.  When the
-        # reference package itself is importable (it needs pysam) the candidates are handed to it, as the reference's driver does
-        # (__main__.py:193-207), so that a full installation still ends with {prefix}.vcf.
+    if rank == 0 and not multi and os.environ.get("TIDDIT_VARIANTS") == "1":
+        # the native variant stage (tiddit_variant.py over the evidence store the scan filled, tiddit_vcf_header.py): {prefix}.vcf
+        from . import tiddit_variant, tiddit_vcf_header
+        t = time.time()
+        with stage("tiddit: variant typing"):
+            variant_stage(tiddit_variant, tiddit_vcf_header, prefix, contigs, bam_header, library, sample_id, version, args, sv_clusters, min_mapq,
+                          samples, coverage_data, contig_number, max_ins_len, gc_dictionary)
+        T["variant typing (native)"] = time.time() - t
+        T.update({"  " + k: v for k, v in tiddit_variant.STAGE_SECONDS.items()})
+        print("analyzed clusters in")
+        print(T["variant typing (native)"])
+    elif rank == 0:
+        # Without TIDDIT_VARIANTS=1 the run stops at the candidates table.  When the reference package itself is importable (it needs
+        # pysam) the candidates are handed to it, as the reference's driver does (__main__.py:193-207), so that a full installation
+        # still ends with {prefix}.vcf.
         try:
             import tiddit.tiddit_variant as tiddit_variant
             import tiddit.tiddit_vcf_header as tiddit_vcf_header
@@ -412,7 +438,8 @@ def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, con
                          samples, coverage_data, contig_number, max_ins_len, gc_dictionary):
             T["variant typing (reference package)"] = time.time() - t
         else:
-            print("variant typing/filtering (tiddit_variant) is outside this build's scope; candidates written to {}.candidates.tab".format(prefix))
+            print("variant typing/filtering (tiddit_variant) is outside this build's scope; candidates written to {}.candidates.tab "
+                  "(TIDDIT_VARIANTS=1 runs the native variant stage)".format(prefix))
     if multi:
         dist.barrier()                                                   # every output file exists when any rank returns
         if own_group:

@@ -162,3 +162,143 @@ def candidate_means(sv_clusters, coverage_data, gc, library, bin_size=50):
             covM = mean[3 * i + 2] if count[3 * i + 2] > 4 else library["avg_coverage_{}".format(chrA)]
         out[(chrA, chrB, cid)] = {"avg_a": mean[3 * i], "avg_b": mean[3 * i + 1], "covM": covM}
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The evidence store: every placed record of the scan, packed into 16 bytes on the device as the batches go by
+# (csrc/tdt_region.hip, tdt_evstore_*), so that the variant stage answers get_region from HBM without reading the file again.
+EV_RECORD = numpy.dtype([("start", "<i4"), ("end", "<i4"), ("mate_pos", "<i4"), ("bits", "u1"), ("pad", "u1", (3,))])
+EV_UNMAPPED, EV_MATE_UNMAPPED, EV_DUPLICATE, EV_HAS_SA, EV_LOW_Q, EV_DISCORDANT = 0x04, 0x08, 0x01, 0x02, 0x10, 0x20
+_EV_COLUMNS = ("tid", "pos", "end", "mapq", "flag", "mate_tid", "mate_pos", "tlen", "sa_off")
+_EV_TYPES = (numpy.int32, numpy.int32, numpy.int32, numpy.uint8, numpy.uint16, numpy.int32, numpy.int32, numpy.int32, numpy.int64)
+
+
+class EvidenceStore:
+    """Packed records of one coordinate-sorted file in file order: contig t is records [offset[t], offset[t] + count[t]).
+    min_q / max_ins are fixed when the store is made (the scan's own; max_ins truncated to int as get_region's ``int max_ins``)."""
+
+    def __init__(self, path, references, lengths, min_q, max_ins, capacity=0, ctx=None):
+        import ctypes
+        self.ctx = ctx or _native.default_context()
+        self.path = path
+        self.references, self.lengths = list(references), [int(x) for x in lengths]
+        self.tid = {n: i for i, n in enumerate(self.references)}
+        self.min_q, self.max_ins = int(min_q), int(max_ins)
+        self.offset = numpy.zeros(len(self.references), dtype=numpy.int64)
+        self.count = numpy.zeros(len(self.references), dtype=numpy.int64)
+        self.n = 0
+        self._last = -1                    # the contig the store ends with
+        h = ctypes.c_void_p()
+        _native.check(self.ctx.lib.tdt_evstore_create(self.ctx.handle, len(self.references), self.min_q, self.max_ins, int(capacity), ctypes.byref(h)))
+        self.handle = h
+
+    def _placed(self, runs):
+        """the runs [(tid, lo, hi)] of one batch -> n: records [0, n) of the batch are placed and go into the store; the contigs'
+        ranges are booked.  Placed records after unplaced ones, or a contig that comes back, mean an unsorted file: an error."""
+        n, tail = 0, False
+        for t, lo, hi in runs:
+            t, lo, hi = int(t), int(lo), int(hi)
+            if hi <= lo:
+                continue
+            if t < 0:
+                tail = True
+                continue
+            if tail or lo != n or (t != self._last and self.count[t]):
+                raise ValueError("evidence store: %s is not coordinate sorted (%s)" % (self.path, self.references[t]))
+            if t != self._last:
+                self.offset[t] = self.n + lo
+                self._last = t
+            self.count[t] += hi - lo
+            n = hi
+        return n
+
+    def add_device_batch(self, b):
+        """one DeviceBatch: the pack kernel is enqueued on the reader's stream (call before the batch's buffers are handed back)"""
+        n = self._placed(b.runs)
+        if n:
+            d = b.dev
+            _native.check(self.ctx.lib.tdt_evstore_append_device(self.handle, *[d[k] for k in _EV_COLUMNS], n))
+            self.n += n
+
+    def add_host_batch(self, b):
+        """one host-decoded batch: its columns are uploaded, then the same kernel"""
+        tid = b.tid
+        if not len(tid):
+            return
+        edges = numpy.flatnonzero(numpy.diff(tid)) + 1
+        runs = [(int(tid[lo]), lo, hi) for lo, hi in zip(numpy.concatenate([[0], edges]), numpy.concatenate([edges, [len(tid)]]))]
+        n = self._placed(runs)
+        if n:
+            cols = [numpy.ascontiguousarray(getattr(b, k)[:n], dtype=dt) for k, dt in zip(_EV_COLUMNS, _EV_TYPES)]
+            _native.check(self.ctx.lib.tdt_evstore_append(self.handle, *[_native.ptr(c) for c in cols], n))
+            self.n += n
+
+    def spans(self):
+        out = numpy.zeros(len(self.references), dtype=numpy.int32)
+        _native.check(self.ctx.lib.tdt_evstore_spans(self.handle, _native.ptr(out)))
+        return out
+
+    def contig_table(self):
+        """int64[n_contigs, 5]: offset, n, max span, tid, length — the table tdt_region_counts_packed reads"""
+        t = numpy.zeros((len(self.references), 5), dtype=numpy.int64)
+        t[:, 0], t[:, 1], t[:, 2] = self.offset, self.count, self.spans()
+        t[:, 3] = numpy.arange(len(self.references))
+        t[:, 4] = self.lengths
+        return t
+
+    def records(self, t):
+        """contig t's packed records, copied to the host (tests)"""
+        import ctypes
+        out = numpy.zeros(int(self.count[t]), dtype=EV_RECORD)
+        if len(out):
+            base = ctypes.c_void_p()
+            _native.check(self.ctx.lib.tdt_evstore_info(self.handle, None, None, ctypes.byref(base)))
+            self.ctx.sync()
+            _native.check(self.ctx.lib.tdt_copy_to_host(self.ctx.handle, _native.ptr(out), base.value + 16 * int(self.offset[t]), out.nbytes))
+        return out
+
+    def region_counts(self, queries, min_q, max_ins, table=None, ctx=None):
+        """queries: (contig index, start, end, bp) rows -> int64[nq, 7] (bases, n_reads, low_q, n_discs, n_splits, crossing_f,
+        crossing_r) in ONE launch.  min_q / max_ins must be the store's (the library refuses anything else)."""
+        ctx = ctx or self.ctx
+        q = numpy.ascontiguousarray(numpy.asarray(queries, dtype=numpy.int32).reshape(-1, 4))
+        tab = numpy.ascontiguousarray(self.contig_table() if table is None else table, dtype=numpy.int64)
+        out = numpy.zeros((len(q), 7), dtype=numpy.int64)
+        _native.check(ctx.lib.tdt_region_counts_packed(ctx.handle, self.handle, _native.ptr(tab), len(tab), _native.ptr(q), len(q),
+                                                       int(min_q), int(max_ins), _native.ptr(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.tdt_evstore_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def build_store(bam_file_name, min_q, max_ins, ctx=None):
+    """an evidence store from one ingest pass over the file (the device ingest unless TIDDIT_HOST_INGEST=1) — what the variant stage
+    uses when no scan of this process left one"""
+    import os
+    from .bamio import DeviceBatch
+    reader = open_bam(bam_file_name)
+    store = None
+    try:
+        store = EvidenceStore(bam_file_name, reader.references, reader.lengths, min_q, max_ins,
+                              capacity=os.path.getsize(bam_file_name) // 64, ctx=getattr(reader, "ctx", None) or ctx)
+        for b in reader.batches():
+            if isinstance(b, DeviceBatch):
+                store.add_device_batch(b)
+            else:
+                store.add_host_batch(b)
+    except BaseException:
+        if store is not None:
+            store.close()
+        raise
+    finally:
+        reader.close()
+    return store

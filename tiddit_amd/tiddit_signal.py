@@ -326,6 +326,13 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
     T = SCAN_SECONDS
     T.clear()
     T.update({"ingest (inflate + decode, device)": 0.0, "coverage push": 0.0})
+    store = None
+    if KEEP_EVIDENCE:
+        # the variant stage's evidence store (tiddit_region.EvidenceStore): every placed record packed on the device as the batches go by
+        from . import tiddit_region
+        store = tiddit_region.EvidenceStore(bam_file_name, names, lengths, min_q, max_ins, capacity=os.path.getsize(bam_file_name) // 64,
+                                            ctx=getattr(reader, "ctx", None))
+        T["evidence store (pack)"] = 0.0
     tables = data = splits = clips = None
     if isinstance(reader, DeviceBamReader):
         from .sigtab import SignalTables
@@ -368,6 +375,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 hist.push_device_batch(b, min_q, big)           # coverage (filter on the device, :171-182)
                 t3 = time.time()
                 T["coverage push"] += t3 - t1
+                if store is not None:                           # (enqueued before ahead() below hands the batch's buffers on)
+                    store.add_device_batch(b)
+                    t3b = time.time()
+                    T["evidence store (pack)"] += t3b - t3
+                    t3 = t3b
                 # the per-read chain of worker (:171-221) on the device; only the selected reads come back (fields + raw records)
                 # (once the scan's kernels are enqueued nothing will read the batch's raw bytes again: the next span's inflate is started
                 #  behind them — DeviceBamReader.ahead() — and runs while this thread waits for the selected reads and hands them on)
@@ -384,6 +396,10 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 pending = pool.submit(rows_of, sel)
                 t0 = time.time()
                 continue
+            if store is not None:
+                t1b = time.time()
+                store.add_host_batch(b)
+                T["evidence store (pack)"] += time.time() - t1b
             tid = b.tid
             flag = b.flag.astype(numpy.int32)
             placed = tid >= 0
@@ -438,6 +454,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         if tables is not None:
             pool.shutdown(wait=True)
             tables.close()
+        if store is not None:
+            store.close()
         raise
     finally:
         pool.shutdown(wait=True)                              # (also on an error: no row thread outlives the scan)
@@ -451,6 +469,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 READER_SECONDS["push: " + k_[:-3] + " (s)"] = sum(t_[k_] for t_ in reader.timings) * 1e-3
             READER_SECONDS["pushes"] = len(reader.timings)
     reader.close()
+    if store is not None:
+        from . import tiddit_variant
+        if tiddit_variant.LIVE_STORE is not None:
+            tiddit_variant.LIVE_STORE.close()
+        tiddit_variant.LIVE_STORE = store                       # (the variant stage takes it over and frees it)
     chromosomes = [n for n, ok in zip(names, big) if ok]
     if reduce_bins is None and len(chromosomes) <= 64:
         coverage = {n: hist.finish(n) for n in chromosomes}
@@ -484,6 +507,7 @@ _SCAN_CACHE = {}
 STAGE_SECONDS = {}          # wall seconds of the last main(), stage by stage
 SCAN_SECONDS = {}           # ... and of the last scan pass, by what the host waited for
 LAST_SEAM = {}              # seam offsets of the last sharded scan pass (dist.check_seams)
+KEEP_EVIDENCE = False       # the scan packs every placed record into an evidence store for the variant stage (tiddit_variant.LIVE_STORE)
 AFTER_SCAN = []             # callables main() invokes once the file has been scanned, before the tables are written (host-only work from there on)
 READER_SECONDS = {}         # the reader thread of the last scan: seconds reading, scanning BGZF headers, building tables, waiting — and the consumer's waits
 WRITTEN_TABLES = {}         # (discordants path, splits path) -> stamps + the native tables the last main() wrote them from (tiddit_cluster takes them over)
