@@ -372,6 +372,12 @@ int tdt_evstore_spans(tdt_evstore *s, int32_t *spans);
  * TDT_E_RANGE when a row lies outside the store or a query names no row. */
 int tdt_region_counts_packed(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *queries, size_t nq,
                              int min_q, int64_t max_ins, int64_t *out);
+/* The same counts with device queries and a device output (what a broadcast delivers and a reduce sends on): d_queries =
+ * int32[nq][4] in HBM, 16-byte aligned; d_out = int64[nq][7] in HBM; contigs = the host table as above, validated on the host.  The
+ * kernel checks every query's row: a query naming no row gets zeros, and the call returns TDT_E_RANGE naming the first such query.
+ * The library's stream is synchronised before the return.  TDT_E_ARG as above for other min_q / max_ins. */
+int tdt_region_counts_packed_device(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *d_queries,
+                                    size_t nq, int min_q, int64_t max_ins, int64_t *d_out);
 
 /* ---- coverage table text (host, threaded) ----------------------------------------------------------- *
  * The row loop of print_coverage (tiddit_coverage.pyx:30-44) for one contig: kind 0 = bed rows

@@ -6,10 +6,11 @@ repository implements — library statistics, signal extraction + coverage (devi
 clustering (device) — and writes the signal ``.tab`` files, ``{o}.ploidies.tab`` and
 ``{o}.candidates.tab``.  By default the run stops after the candidates table and says so.
 
-``TIDDIT_VARIANTS=1`` (one process): the scan also packs every placed record into an evidence store in HBM, and
-the native variant stage (tiddit_amd/tiddit_variant.py: typing, filters, genotypes, QUAL; regional counts in one
-device launch over the store) writes ``{o}.vcf`` with tiddit_amd/tiddit_vcf_header.py's header.  On N ranks the
-switch says so and the run stops at the candidates table.  Local assembly stays out of scope.
+``TIDDIT_VARIANTS=1``: the scan also packs every placed record into an evidence store in HBM, and the native variant
+stage (tiddit_amd/tiddit_variant.py: typing, filters, genotypes, QUAL; regional counts in one device launch over the
+store) writes ``{o}.vcf`` with tiddit_amd/tiddit_vcf_header.py's header.  On N ranks every rank keeps the store of its
+own shard of the file, answers all of rank 0's queries over it, and the counts are summed on rank 0, which writes the
+same ``{o}.vcf``.  Local assembly stays out of scope.
 """
 import argparse
 import os
@@ -136,13 +137,18 @@ def write_candidates(path, contigs, sv_clusters):
 
 
 def variant_stage(tiddit_variant, tiddit_vcf_header, prefix, contigs, bam_header, library, sample_id, version, args, sv_clusters, min_mapq, samples,
-                  coverage_data, contig_number, max_ins_len, gc_dictionary):
+                  coverage_data, contig_number, max_ins_len, gc_dictionary, entry=None):
     """the tail of the reference's driver (__main__.py:193-207) with the two modules handed in: header, variants per contig sorted by
-    position, {prefix}.vcf.  -> False (nothing written) when the reference package is not there."""
+    position, {prefix}.vcf.  entry: the variant module's function to call (default its ``main``; on N ranks every rank calls
+    ``main_sharded``, and the ranks it returns None on write nothing).  -> False (nothing written) when the reference package is
+    not there, or on a rank that does not write."""
     if tiddit_variant is None or tiddit_vcf_header is None:
         return False
+    variants = (entry or tiddit_variant.main)(args.bam, sv_clusters, args, library, min_mapq, samples, coverage_data, contig_number,
+                                              max_ins_len, gc_dictionary)
+    if variants is None:
+        return False
     vcf_header = tiddit_vcf_header.main(bam_header, library, sample_id, version)
-    variants = tiddit_variant.main(args.bam, sv_clusters, args, library, min_mapq, samples, coverage_data, contig_number, max_ins_len, gc_dictionary)
     with open(prefix + ".vcf", "w") as f:
         f.write(vcf_header + "\n")
         for chrom in contigs:
@@ -314,11 +320,9 @@ def run_sv(args, version):
     # one process: the blocks of discordants / splits / clips are placed by a thread while the job goes on (tiddit_cluster takes the tables
     # over, not the files); finish_writes() below waits for it.  TIDDIT_BACKGROUND_WRITES=0: written before tiddit_signal.main returns.
     tiddit_signal.BACKGROUND_WRITES = (not multi) and os.environ.get("TIDDIT_BACKGROUND_WRITES", "1") != "0"
-    # TIDDIT_VARIANTS=1: the scan also packs every placed record into the evidence store the native variant stage reads (one process only)
-    variants_on = os.environ.get("TIDDIT_VARIANTS") == "1"
-    if variants_on and multi and rank == 0:
-        print("the native variant stage (TIDDIT_VARIANTS=1) is one-process only; this run stops at the candidates table")
-    tiddit_signal.KEEP_EVIDENCE = variants_on and not multi
+    # TIDDIT_VARIANTS=1: the scan also packs every placed record into the evidence store the native variant stage reads (on N ranks:
+    # every rank the records of its own shard)
+    tiddit_signal.KEEP_EVIDENCE = os.environ.get("TIDDIT_VARIANTS") == "1"
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -413,17 +417,20 @@ def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, con
     if tiddit_signal.WRITE_SECONDS:
         T["signal files placed (writer thread, beside ploidy and clustering)"] = tiddit_signal.WRITE_SECONDS["writer thread"]
         T["  waited for the writer thread"] = tiddit_signal.WRITE_SECONDS["waited for it"]
-    if rank == 0 and not multi and os.environ.get("TIDDIT_VARIANTS") == "1":
-        # the native variant stage (tiddit_variant.py over the evidence store the scan filled, tiddit_vcf_header.py): {prefix}.vcf
+    if os.environ.get("TIDDIT_VARIANTS") == "1":
+        # the native variant stage (tiddit_variant.py over the evidence store the scan filled, tiddit_vcf_header.py): {prefix}.vcf.  On N
+        # ranks every rank takes part (the counts over its shard's store); rank 0 types the variants and writes the file.
         from . import tiddit_variant, tiddit_vcf_header
         t = time.time()
         with stage("tiddit: variant typing"):
             variant_stage(tiddit_variant, tiddit_vcf_header, prefix, contigs, bam_header, library, sample_id, version, args, sv_clusters, min_mapq,
-                          samples, coverage_data, contig_number, max_ins_len, gc_dictionary)
+                          samples, coverage_data, contig_number, max_ins_len, gc_dictionary,
+                          entry=tiddit_variant.main_sharded if multi else tiddit_variant.main)
         T["variant typing (native)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_variant.STAGE_SECONDS.items()})
-        print("analyzed clusters in")
-        print(T["variant typing (native)"])
+        if rank == 0:
+            print("analyzed clusters in")
+            print(T["variant typing (native)"])
     elif rank == 0:
         # Without TIDDIT_VARIANTS=1 the run stops at the candidates table.  When the reference package itself is importable (it needs
         # pysam) the candidates are handed to it, as the reference's driver does (__main__.py:193-207), so that a full installation

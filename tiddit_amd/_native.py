@@ -113,6 +113,7 @@ SYMBOLS = {
     "tdt_evstore_info": (_i, [_P, ctypes.POINTER(_sz), ctypes.POINTER(_sz), _PP]),
     "tdt_evstore_spans": (_i, [_P, _P]),
     "tdt_region_counts_packed": (_i, [_P, _P, _P, _i, _P, _sz, _i, _i64, _P]),
+    "tdt_region_counts_packed_device": (_i, [_P, _P, _P, _i, _P, _sz, _i, _i64, _P]),
     "tdt_format_coverage": (_i, [_P, _sz, ctypes.c_char_p, _i64, _i64, _i, _P, _sz, ctypes.POINTER(_sz)]),
     "tdt_fasta_write_fai": (_i, [ctypes.c_char_p, ctypes.c_char_p]),
     "tdt_host_threads": (_i, [_i]),

@@ -371,13 +371,21 @@ extern "C" int tdt_evstore_spans(tdt_evstore *s, int32_t *spans) {
 
 // One wave per query over the store: the query's contig row of the table gives the record range, and everything else is
 // region_counts above with the eight column loads replaced by one 16-byte load and the predicates read from the bits.
+// CHECK (the device-query entry, whose queries the host never sees): a query naming no row of the table writes zeros and leaves
+// the lowest such query index in *bad; the wave's branch is uniform (one query per wave).
+template <bool CHECK>
 __global__ __launch_bounds__(256) void region_counts_packed(const int4 *__restrict__ rec, const long long *__restrict__ ctab,
-                                                            const int32_t *__restrict__ qry, int nq, long long max_ins,
-                                                            long long *__restrict__ out) {
+                                                            int n_contigs, const int32_t *__restrict__ qry, int nq, long long max_ins,
+                                                            long long *__restrict__ out, int *__restrict__ bad) {
     const int lane = threadIdx.x & 63;
     const int q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (q >= nq) return;
     const int4 Q = reinterpret_cast<const int4 *>(qry)[q];                        // (contig index, start, end, bp)
+    if (CHECK && (Q.x < 0 || Q.x >= n_contigs)) {
+        if (lane < 7) out[(size_t)q * 7 + lane] = 0;
+        if (lane == 0) atomicMin(bad, q);
+        return;
+    }
     const long long *C = ctab + 5 * (size_t)Q.x;                                  // (offset, n, max span, tid, length)
     const int4 *__restrict__ R = rec + C[0];
     const int n = (int)C[1];
@@ -427,25 +435,32 @@ __global__ __launch_bounds__(256) void region_counts_packed(const int4 *__restri
     }
 }
 
+// the checks both entries make on the host: the store's parameters, and every contig row inside the store
+static int packed_check(const char *fn, tdt_evstore *s, const int64_t *contigs, int n_contigs, int min_q, int64_t max_ins) {
+    if (min_q != s->min_q || (long long)max_ins != s->max_ins) {
+        tdt_set_error("%s: the store was packed with min_q %d / max_ins %lld, the queries ask for %d / %lld", fn, s->min_q, s->max_ins,
+                      min_q, (long long)max_ins);
+        return TDT_E_ARG;
+    }
+    for (int c = 0; c < n_contigs; c++) {          // every range the kernel may touch lies inside the store
+        const int64_t *C = contigs + 5 * (size_t)c;
+        if (C[0] < 0 || C[1] < 0 || C[1] >= 0x7fffffffll || (size_t)(C[0] + C[1]) > s->n || C[2] < 0 || C[4] < 0) {
+            tdt_set_error("%s: contig row %d (offset %lld, n %lld, span %lld, length %lld) outside the store of %zu", fn, c,
+                          (long long)C[0], (long long)C[1], (long long)C[2], (long long)C[4], s->n);
+            return TDT_E_RANGE;
+        }
+    }
+    return TDT_OK;
+}
+
 extern "C" int tdt_region_counts_packed(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *queries,
                                         size_t nq, int min_q, int64_t max_ins, int64_t *out) {
     if (!ctx || !s || n_contigs < 0 || nq >= 0x7fffffffull || (n_contigs && !contigs) || (nq && (!queries || !out))) {
         tdt_set_error("tdt_region_counts_packed: bad argument");
         return TDT_E_ARG;
     }
-    if (min_q != s->min_q || (long long)max_ins != s->max_ins) {
-        tdt_set_error("tdt_region_counts_packed: the store was packed with min_q %d / max_ins %lld, the queries ask for %d / %lld",
-                      s->min_q, s->max_ins, min_q, (long long)max_ins);
-        return TDT_E_ARG;
-    }
-    for (int c = 0; c < n_contigs; c++) {          // every range the kernel may touch lies inside the store
-        const int64_t *C = contigs + 5 * (size_t)c;
-        if (C[0] < 0 || C[1] < 0 || C[1] >= 0x7fffffffll || (size_t)(C[0] + C[1]) > s->n || C[2] < 0 || C[4] < 0) {
-            tdt_set_error("tdt_region_counts_packed: contig row %d (offset %lld, n %lld, span %lld, length %lld) outside the store of %zu",
-                          c, (long long)C[0], (long long)C[1], (long long)C[2], (long long)C[4], s->n);
-            return TDT_E_RANGE;
-        }
-    }
+    int rc = packed_check("tdt_region_counts_packed", s, contigs, n_contigs, min_q, max_ins);
+    if (rc) return rc;
     for (size_t q = 0; q < nq; q++) {
         if (queries[4 * q] < 0 || queries[4 * q] >= n_contigs) {
             tdt_set_error("tdt_region_counts_packed: query %zu names contig %d of %d", q, queries[4 * q], n_contigs);
@@ -457,7 +472,7 @@ extern "C" int tdt_region_counts_packed(tdt_ctx *ctx, tdt_evstore *s, const int6
     if (ctx != s->ctx) TDT_HIP(hipStreamSynchronize(s->ctx->stream));       // (the packs of another context's stream are complete)
     const size_t ct = ((size_t)n_contigs * 40 + 255) & ~(size_t)255, qb = (nq * 16 + 255) & ~(size_t)255;
     void *d = nullptr;
-    int rc = tdt_scratch(ctx, 26, ct + qb + nq * 56, &d);
+    rc = tdt_scratch(ctx, 26, ct + qb + nq * 56, &d);
     if (rc) return rc;
     long long *dct = (long long *)d;
     int32_t *dq = (int32_t *)((char *)d + ct);
@@ -465,10 +480,49 @@ extern "C" int tdt_region_counts_packed(tdt_ctx *ctx, tdt_evstore *s, const int6
     hipStream_t st = ctx->stream;
     TDT_HIP(hipMemcpyAsync(dct, contigs, (size_t)n_contigs * 40, hipMemcpyHostToDevice, st));
     TDT_HIP(hipMemcpyAsync(dq, queries, nq * 16, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(region_counts_packed, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, s->rec, dct, dq, (int)nq,
-                       (long long)max_ins, dout);
+    hipLaunchKernelGGL(region_counts_packed<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, s->rec, dct, n_contigs, dq, (int)nq,
+                       (long long)max_ins, dout, nullptr);
     TDT_CHECK_LAUNCH();
     TDT_HIP(hipMemcpyAsync(out, dout, nq * 56, hipMemcpyDeviceToHost, st));
     TDT_HIP(hipStreamSynchronize(st));
+    return TDT_OK;
+}
+
+// The same counts with the queries and the output on the device (the N-rank variant stage: the queries arrive by a broadcast into a
+// device tensor, the partial counts leave by a reduce from one).  The contig table is the host's; the kernel checks the queries' rows.
+// The stream is synchronised before the return, so the caller's next collective reads finished counts.
+extern "C" int tdt_region_counts_packed_device(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *d_queries,
+                                               size_t nq, int min_q, int64_t max_ins, int64_t *d_out) {
+    if (!ctx || !s || n_contigs < 0 || nq >= 0x7fffffffull || (n_contigs && !contigs) || (nq && (!d_queries || !d_out)) ||
+        ((uintptr_t)d_queries & 15) || ((uintptr_t)d_out & 7)) {
+        tdt_set_error("tdt_region_counts_packed_device: bad argument");
+        return TDT_E_ARG;
+    }
+    int rc = packed_check("tdt_region_counts_packed_device", s, contigs, n_contigs, min_q, max_ins);
+    if (rc) return rc;
+    if (nq == 0) return TDT_OK;
+    TDT_HIP(hipSetDevice(ctx->device));
+    if (ctx != s->ctx) TDT_HIP(hipStreamSynchronize(s->ctx->stream));
+    const size_t ct = ((size_t)n_contigs * 40 + 255) & ~(size_t)255;
+    void *d = nullptr;
+    rc = tdt_scratch(ctx, 26, ct + 256, &d);
+    if (rc) return rc;
+    long long *dct = (long long *)d;
+    int *dbad = (int *)((char *)d + ct);
+    hipStream_t st = ctx->stream;
+    int bad = 0x7fffffff;                          // (host words: the stream is synchronised before they go out of scope)
+    TDT_HIP(hipMemcpyAsync(dct, contigs, (size_t)n_contigs * 40, hipMemcpyHostToDevice, st));
+    TDT_HIP(hipMemcpyAsync(dbad, &bad, sizeof(int), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(region_counts_packed<true>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, s->rec, dct, n_contigs, d_queries,
+                       (int)nq, (long long)max_ins, (long long *)d_out, dbad);
+    TDT_CHECK_LAUNCH();
+    TDT_HIP(hipMemcpyAsync(&bad, dbad, sizeof(int), hipMemcpyDeviceToHost, st));
+    TDT_HIP(hipStreamSynchronize(st));
+    if (bad != 0x7fffffff) {
+        int row = 0;
+        TDT_HIP(hipMemcpy(&row, d_queries + 4 * (size_t)bad, sizeof(int), hipMemcpyDeviceToHost));
+        tdt_set_error("tdt_region_counts_packed_device: query %d names contig %d of %d", bad, row, n_contigs);
+        return TDT_E_RANGE;
+    }
     return TDT_OK;
 }

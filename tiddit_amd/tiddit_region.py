@@ -268,6 +268,15 @@ class EvidenceStore:
                                                        int(min_q), int(max_ins), _native.ptr(out)))
         return out
 
+    def region_counts_device(self, d_queries, nq, min_q, max_ins, d_out, table=None, ctx=None):
+        """the same counts with the queries and the output in HBM (device pointers: int32[nq][4], 16-byte aligned; int64[nq][7]) —
+        the N-rank stage's broadcast queries and reduced counts.  The kernel checks every query's contig row (TDT_E_RANGE); the
+        library's stream is finished when this returns."""
+        ctx = ctx or self.ctx
+        tab = numpy.ascontiguousarray(self.contig_table() if table is None else table, dtype=numpy.int64)
+        _native.check(ctx.lib.tdt_region_counts_packed_device(ctx.handle, self.handle, _native.ptr(tab), len(tab), d_queries, int(nq),
+                                                              int(min_q), int(max_ins), d_out))
+
     def close(self):
         if getattr(self, "handle", None):
             self.ctx.lib.tdt_evstore_destroy(self.handle)
@@ -280,21 +289,28 @@ class EvidenceStore:
             pass
 
 
-def build_store(bam_file_name, min_q, max_ins, ctx=None):
+def build_store(bam_file_name, min_q, max_ins, ctx=None, shard=None):
     """an evidence store from one ingest pass over the file (the device ingest unless TIDDIT_HOST_INGEST=1) — what the variant stage
-    uses when no scan of this process left one"""
+    uses when no scan of this process left one.  shard = (rank, world): the records that start in this rank's byte range of the file
+    only (bamio.DeviceBamReader); the seam offsets are left in ``store.seam`` = (first_off, next_off, empty) for dist.check_seams."""
     import os
-    from .bamio import DeviceBatch
-    reader = open_bam(bam_file_name)
+    from .bamio import DeviceBamReader, DeviceBatch
+    if shard is None:
+        reader = open_bam(bam_file_name)
+    else:
+        reader = DeviceBamReader(bam_file_name, shard=shard, chunk=int(os.environ.get("TIDDIT_INGEST_CHUNK", str(448 << 20))))
     store = None
     try:
         store = EvidenceStore(bam_file_name, reader.references, reader.lengths, min_q, max_ins,
-                              capacity=os.path.getsize(bam_file_name) // 64, ctx=getattr(reader, "ctx", None) or ctx)
+                              capacity=os.path.getsize(bam_file_name) // 64 // (1 if shard is None else shard[1]),
+                              ctx=getattr(reader, "ctx", None) or ctx)
         for b in reader.batches():
             if isinstance(b, DeviceBatch):
                 store.add_device_batch(b)
             else:
                 store.add_host_batch(b)
+        if shard is not None:
+            store.seam = (reader.first_off, reader.next_off, reader.first_off is None)
     except BaseException:
         if store is not None:
             store.close()

@@ -330,7 +330,9 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
     if KEEP_EVIDENCE:
         # the variant stage's evidence store (tiddit_region.EvidenceStore): every placed record packed on the device as the batches go by
         from . import tiddit_region
-        store = tiddit_region.EvidenceStore(bam_file_name, names, lengths, min_q, max_ins, capacity=os.path.getsize(bam_file_name) // 64,
+        # (sized for this rank's share of the file on N ranks; the store grows 1.5x when a batch does not fit)
+        store = tiddit_region.EvidenceStore(bam_file_name, names, lengths, min_q, max_ins,
+                                            capacity=os.path.getsize(bam_file_name) // 64 // (1 if shard is None else shard[1]),
                                             ctx=getattr(reader, "ctx", None))
         T["evidence store (pack)"] = 0.0
     tables = data = splits = clips = None

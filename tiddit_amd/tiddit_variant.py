@@ -7,7 +7,8 @@ The evidence comes from the device, all candidates at once:
   2. the host pre-filters of define_variant (:251-284) pick the candidates that need regional counts;
   3. ONE tdt_region_counts_packed launch answers every get_region call of those candidates (:290-305) from the evidence store —
      the packed records the signal scan of this process left in HBM, or, when there is none (the module swapped into another
-     driver), a store built by one device-ingest pass over the file.
+     driver), a store built by one device-ingest pass over the file.  On N ranks (:func:`main_sharded`) every rank holds the store
+     of its shard of the file, answers all of rank 0's queries in one launch, and the partial counts are summed on rank 0.
 The typing layer (:define_variant, :finish) takes that evidence as arguments — the get_region results keyed by
 (chrom, start, end, bp) and the means per candidate — and keeps every visible quirk of the reference's output.
 """
@@ -353,10 +354,10 @@ def evidence(store, queries, min_q, max_ins):
     return {k: region_tuple(counts[i], k[1], k[2]) for i, k in enumerate(keys)}
 
 
-def main(bam_file_name, sv_clusters, args, library, min_mapq, samples, coverage_data, contig_number, max_ins_len, gc):
+def _prepare(bam_file_name, sv_clusters, args, library, coverage_data, gc, T):
+    """the host side before the counts: the assembly contigs, the coverage means of every candidate, the get_region calls of the
+    candidates that pass the pre-filters -> (contig_seqs, means, queries)"""
     import time
-    T = STAGE_SECONDS
-    T.clear()
     t = time.time()
     contig_seqs = {}
     if not args.skip_assembly:
@@ -374,6 +375,14 @@ def main(bam_file_name, sv_clusters, args, library, min_mapq, samples, coverage_
         for chrB, cid, c, posA, posB, _, _ in survivors(chrA, sv_clusters, args, library, means):
             queries += region_queries(chrA, chrB, c, posA, posB)
     T["pre-filters (host)"] = time.time() - t
+    return contig_seqs, means, queries
+
+
+def main(bam_file_name, sv_clusters, args, library, min_mapq, samples, coverage_data, contig_number, max_ins_len, gc):
+    import time
+    T = STAGE_SECONDS
+    T.clear()
+    contig_seqs, means, queries = _prepare(bam_file_name, sv_clusters, args, library, coverage_data, gc, T)
     t = time.time()
     store = take_store(bam_file_name, min_mapq, int(max_ins_len))
     if store is None:
@@ -385,6 +394,112 @@ def main(bam_file_name, sv_clusters, args, library, min_mapq, samples, coverage_
     finally:
         store.close()
     T["region counts (device, one launch)"] = time.time() - t
+    t = time.time()
+    out = type_variants(sv_clusters, args, library, samples, max_ins_len, contig_seqs, means, regions)
+    T["typing + scoring (host)"] = time.time() - t
+    return out
+
+
+# ---- N ranks: every rank holds the store of its own shard of the file ---------------------------------------------------------
+# Every record is in exactly one rank's store, and all seven sums of a query are order-independent integer sums over the records
+# its region fetch returns (each shard's range and max span are its own), so the counts of one query over the N stores add up to the
+# counts over the whole file's store: rank 0 broadcasts all the queries, every rank answers them in one launch, one int64 SUM-reduce.
+
+def _broadcast_abort(group=None):
+    """rank 0 failed before it had queries: nq = -1 tells the other ranks (who wait in evidence_sharded's first broadcast)"""
+    import torch
+    import torch.distributed as dist
+    from . import dist as tdist
+    dist.broadcast(torch.tensor([-1], dtype=torch.int64, device=tdist._wire_device(group)), 0, group=group)
+
+
+def evidence_sharded(store, queries, min_q, max_ins, group=None):
+    """:func:`evidence` on N ranks, a collective: every rank calls it with the store of its shard (anything with ``.tid`` on rank 0
+    and ``region_counts`` — or ``region_counts_device`` over nccl); rank 0 passes its (chrom, start, end, bp) list, the other ranks
+    None.  nq, then the int32[nq][4] rows are broadcast (device tensors over nccl, host tensors over gloo); every rank answers all of
+    them over its store; the int64 counts, plus one word counting the ranks whose counts call failed, are SUM-reduced to rank 0.
+    -> the regions dict on rank 0, None elsewhere.  No failure leaves a rank waiting: rank 0 broadcasts nq = -1 when it cannot
+    make the rows, and every rank joins the reduce whether its own call failed or not."""
+    import torch
+    import torch.distributed as dist
+    from . import dist as tdist
+    rank = dist.get_rank(group)
+    dev = tdist._wire_device(group)
+    keys = rows = None
+    if rank == 0:
+        try:
+            keys = list(dict.fromkeys(queries))
+            rows = numpy.array([(store.tid[ch], s, e, bp) for ch, s, e, bp in keys], dtype=numpy.int32).reshape(-1, 4)
+        except BaseException:
+            _broadcast_abort(group)
+            raise
+    n = torch.tensor([len(keys) if rank == 0 else 0], dtype=torch.int64, device=dev)
+    dist.broadcast(n, 0, group=group)
+    nq = int(n.item())
+    if nq < 0:
+        store.close()
+        raise RuntimeError("evidence_sharded: rank 0 failed before it broadcast the queries")
+    if nq == 0:
+        return {} if rank == 0 else None
+    q = torch.from_numpy(rows).to(dev) if rank == 0 else torch.empty((nq, 4), dtype=torch.int32, device=dev)
+    dist.broadcast(q, 0, group=group)
+    out = torch.zeros(nq * 7 + 1, dtype=torch.int64, device=dev)
+    failed = None
+    try:
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)                  # (the broadcast ran on torch's streams, the library runs on its own)
+            store.region_counts_device(q.data_ptr(), nq, min_q, max_ins, out.data_ptr())
+        else:
+            out[:nq * 7] = torch.from_numpy(numpy.ascontiguousarray(store.region_counts(q.numpy(), min_q, max_ins), dtype=numpy.int64).reshape(-1))
+    except Exception as e:
+        failed = e
+        out.zero_()
+        out[-1] = 1
+    dist.reduce(out, 0, op=dist.ReduceOp.SUM, group=group)
+    if failed is not None:
+        raise failed
+    if rank != 0:
+        return None
+    total = out.cpu().numpy()
+    if total[-1]:
+        raise RuntimeError("evidence_sharded: the region counts failed on %d other rank(s)" % int(total[-1]))
+    counts = total[:-1].reshape(nq, 7)
+    return {k: region_tuple(counts[i], k[1], k[2]) for i, k in enumerate(keys)}
+
+
+def main_sharded(bam_file_name, sv_clusters, args, library, min_mapq, samples, coverage_data, contig_number, max_ins_len, gc, group=None):
+    """:func:`main` on N ranks (torch.distributed initialised; nccl = RCCL, or gloo), called by every rank: rank 0 computes the means,
+    the pre-filters and the typing from its arguments (the other ranks' may be anything); every rank answers the queries over the
+    store of its shard — the one its scan left (LIVE_STORE), else one built by a pass over its shard of the file.
+    -> the variants dict on rank 0, None elsewhere."""
+    import time
+    import torch.distributed as dist
+    from . import dist as tdist
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    T = STAGE_SECONDS
+    T.clear()
+    t = time.time()
+    store = take_store(bam_file_name, min_mapq, int(max_ins_len))
+    try:
+        if store is None:
+            store = tiddit_region.build_store(bam_file_name, min_mapq, int(max_ins_len), shard=(rank, world))
+            tdist.check_seams(*store.seam, group=group)
+            T["evidence store (one ingest pass over this rank's shard)"] = time.time() - t
+        contig_seqs = means = queries = None
+        if rank == 0:
+            try:
+                contig_seqs, means, queries = _prepare(bam_file_name, sv_clusters, args, library, coverage_data, gc, T)
+            except BaseException:
+                _broadcast_abort(group)
+                raise
+        t = time.time()
+        regions = evidence_sharded(store, queries, min_mapq, int(max_ins_len), group)
+        T["region counts (N ranks: broadcast, one launch per rank, reduce)"] = time.time() - t
+    finally:
+        if store is not None:
+            store.close()
+    if rank != 0:
+        return None
     t = time.time()
     out = type_variants(sv_clusters, args, library, samples, max_ins_len, contig_seqs, means, regions)
     T["typing + scoring (host)"] = time.time() - t
