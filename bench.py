@@ -14,11 +14,15 @@ With N > 1 ranks the job is ONE shared problem ("scaling": "strong"): the genome
 buckets are split over the ranks, one BAM is read as byte-range shards with one exact all-reduce of the bins
 (tiddit_amd.dist.coverage_sharded); `value` = units of the WHOLE problem / slowest rank's time.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
-Rank 0 prints ONE JSON line: the COMPACT record of the run (<= LINE_BUDGET bytes: the contract's keys, the whole `roofline` object with every
-section's fractions, `cpu_baseline`, the sections' headline figures); the detailed record goes to gpurun_out/bench_detail_n<N>.json
-($TIDDIT_BENCH_DETAIL) and to stdout only with --full-line.
+A plain run measures the headline alone: it makes the coverage input, warms up, times the K steps, writes --dump-outputs if asked,
+and rank 0 prints ONE JSON line (the contract's keys, the workload, the roofline figures of the timed launches themselves).
+--full runs everything else after it, as before: the other layouts of the headline launch, the streaming-read yardstick, profiled
+traffic, the CPU baselines and in-bench parity checks, and the coverage_sv, dbscan, dbscan_shared, gc, ingest, next_rows and sv_e2e
+sections.  Its line is the COMPACT record of the run (<= LINE_BUDGET bytes: the contract's keys, the whole `roofline` object with
+every section's fractions, `cpu_baseline`, the sections' headline figures); the detailed record goes to the file emit() names
+($TIDDIT_BENCH_DETAIL overrides it).  --full-line prints the detailed record instead of the compact one.
 """
 import argparse
 import ctypes
@@ -114,22 +118,24 @@ def parse():
     ap.add_argument("--depth", type=int, default=30)
     ap.add_argument("--bin", type=int, default=500)
     ap.add_argument("--min-q", type=int, default=20)
-    ap.add_argument("--dbscan-n", type=int, default=5_000_000)
-    ap.add_argument("--cpu-contigs", type=int, default=8, help="contigs of the stream the CPU baseline (oracle) is timed on")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cov-sv", action="store_true", help="skip the 50-bp / q>=5 pass over the same stream")
-    ap.add_argument("--no-dbscan", action="store_true")
-    ap.add_argument("--no-gc", action="store_true")
-    ap.add_argument("--gc-len", type=int, default=3_000_000_000, help="reference bases for the GC histogram pass")
-    ap.add_argument("--no-ingest", action="store_true")
-    ap.add_argument("--no-next", action="store_true", help="skip the small next-row kernels (masked medians, regional evidence counts)")
-    ap.add_argument("--no-sv-e2e", action="store_true", help="skip BASELINE configs[3]: tiddit --sv --skip_assembly on a WGS-shaped synthetic BAM")
-    ap.add_argument("--sv-mb", type=int, default=240, help="genome size (Mb, 24 chromosomes with GRCh38's relative lengths, 30x 150-bp pairs) of that BAM")
-    ap.add_argument("--sv-cpu-full-mb", type=int, default=300, help="up to this genome size the CPU legs of sv_e2e run on the whole file, above it on a bounded sample of contigs")
-    ap.add_argument("--full-line", action="store_true", help="print the detailed record (tens of KB) instead of the compact line")
-    ap.add_argument("--ingest-mb", type=int, default=8, help="Mb per contig (2 contigs, 30x, 100-bp reads) of the BAM the ingest pass reads")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other measurement and check (see the options below)")
+    ap.add_argument("--full-line", action="store_true", help="print the detailed record (tens of KB with --full) instead of the compact line")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the float64 coverage bins of the last timed step to "
                     "DIR/coverage_bins.npy (a seeded sample beyond %d MB, see dump_outputs)" % (DUMP_BUDGET // 10**6))
+    fa = ap.add_argument_group("with --full", "these options shape what --full runs after the headline; a plain run ignores them")
+    fa.add_argument("--dbscan-n", type=int, default=5_000_000)
+    fa.add_argument("--cpu-contigs", type=int, default=8, help="contigs of the stream the CPU baseline (oracle) is timed on")
+    fa.add_argument("--no-cpu-baseline", action="store_true")
+    fa.add_argument("--no-cov-sv", action="store_true", help="skip the 50-bp / q>=5 pass over the same stream")
+    fa.add_argument("--no-dbscan", action="store_true")
+    fa.add_argument("--no-gc", action="store_true")
+    fa.add_argument("--gc-len", type=int, default=3_000_000_000, help="reference bases for the GC histogram pass")
+    fa.add_argument("--no-ingest", action="store_true")
+    fa.add_argument("--no-next", action="store_true", help="skip the small next-row kernels (masked medians, regional evidence counts)")
+    fa.add_argument("--no-sv-e2e", action="store_true", help="skip BASELINE configs[3]: tiddit --sv --skip_assembly on a WGS-shaped synthetic BAM")
+    fa.add_argument("--sv-mb", type=int, default=240, help="genome size (Mb, 24 chromosomes with GRCh38's relative lengths, 30x 150-bp pairs) of that BAM")
+    fa.add_argument("--sv-cpu-full-mb", type=int, default=300, help="up to this genome size the CPU legs of sv_e2e run on the whole file, above it on a bounded sample of contigs")
+    fa.add_argument("--ingest-mb", type=int, default=8, help="Mb per contig (2 contigs, 30x, 100-bp reads) of the BAM the ingest pass reads")
     return ap.parse_args()
 
 
@@ -199,26 +205,28 @@ def main():
     items4 = [(c, reads[c][0].data_ptr(), reads[c][1].data_ptr(), reads[c][2].data_ptr(), reads[c][3].data_ptr(), n_reads[c])
               for c in range(C)]
     # the stream as the ingest kernel leaves it for the coverage path: 8-byte packed records (start | span:24 mapq:6 unmapped dup),
-    # packed here once, outside every timed region, by the library's own packing kernel
-    packed = [torch.empty(n_reads[c], dtype=torch.int64, device=dev) for c in range(C)]
+    # packed here once, outside every timed region, by the library's own packing kernel (--full only: the headline reads binned records)
+    packed = None
     pk_a, pk_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for rep in range(2):                                   # (second pass timed: what a caller holding four arrays would pay once)
-        if rep:
-            pk_a.record(stream)
-        for c in range(C):
-            _native.check(ctx.lib.tdt_cov_pack_device(ctx.handle, reads[c][0].data_ptr(), reads[c][1].data_ptr(), reads[c][2].data_ptr(),
-                                                      reads[c][3].data_ptr(), n_reads[c], packed[c].data_ptr()))
-        if rep:
-            pk_b.record(stream)
-        ctx.sync()
-    torch.cuda.synchronize()
-    pack_ms = pk_a.elapsed_time(pk_b)
-    items_packed = [(c, packed[c].data_ptr(), reads[c][1].data_ptr(), n_reads[c]) for c in range(C)]
+    if args.full:
+        packed = [torch.empty(n_reads[c], dtype=torch.int64, device=dev) for c in range(C)]
+        for rep in range(2):                               # (second pass timed: what a caller holding four arrays would pay once)
+            if rep:
+                pk_a.record(stream)
+            for c in range(C):
+                _native.check(ctx.lib.tdt_cov_pack_device(ctx.handle, reads[c][0].data_ptr(), reads[c][1].data_ptr(), reads[c][2].data_ptr(),
+                                                          reads[c][3].data_ptr(), n_reads[c], packed[c].data_ptr()))
+            if rep:
+                pk_b.record(stream)
+            ctx.sync()
+        torch.cuda.synchronize()
+        pack_ms = pk_a.elapsed_time(pk_b)
+        items_packed = [(c, packed[c].data_ptr(), reads[c][1].data_ptr(), n_reads[c]) for c in range(C)]
     # ... and as the ingest kernel leaves it when the reader is bound to THIS histogram (DeviceBamReader.bin_for): 8-byte binned records
     # (first bin << 2 | shape, filter byte, table indices — csrc/tdt_common.h: cov_bin_record), made here by the library's packing kernel
     binned = [torch.empty(n_reads[c], dtype=torch.int64, device=dev) for c in range(C)]
     torch.cuda.synchronize()
-    for rep in range(2):
+    for rep in range(2 if args.full else 1):               # (--full times a second pass; a plain run makes the records once)
         if rep:
             pk_a.record(stream)
         for c in range(C):
@@ -228,7 +236,7 @@ def main():
             pk_b.record(stream)
         ctx.sync()
     torch.cuda.synchronize()
-    bin_pack_ms = pk_a.elapsed_time(pk_b)
+    bin_pack_ms = pk_a.elapsed_time(pk_b) if args.full else None
     items = [(c, binned[c].data_ptr(), reads[c][0].data_ptr(), reads[c][1].data_ptr(), n_reads[c]) for c in range(C)]
 
     ev_pairs = []
@@ -265,9 +273,47 @@ def main():
     # four-array contract — 11 B/read of arrays + 1 pad — and prices only `four_array_layout` below; pricing the packed launch with
     # it would count bytes that are never moved.)
     alg_bytes_launch = 8.0 * total_reads + 8.0 * total_bins
+    achieved = alg_bytes_launch / (kern_ms * 1e-3) / 1e9
+    result = {
+        "metric": "cov bins/sec, 30x WGS synthetic (signals clustered/sec: see 'dbscan')",
+        "value": job_bins / (t_cov / args.steps),
+        "unit": "bins/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "int64",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: coverage histogram, %d contigs x %d bp (%.2f Gb), %dx 150-bp sorted "
+                               "stream, %d-bp bins, q>=%d filter; contigs split over the %d rank(s)" % (C_all, L, C_all * L / 1e9, args.depth, z, args.min_q, world),
+                   "reads": job_reads, "bins": job_bins, "reads_rank0": total_reads, "bins_rank0": total_bins, "launches_per_step": 3,
+                   "layout_short": "8-byte BINNED records in HBM as the ingest kernel writes them (DESIGN 3.1): `value` prices the ACCUMULATE stage of "
+                                   "ingest -> accumulate" + ("; roofline.contract_* is SURVEY 8(d)'s four arrays in one launch" if args.full else ""),
+                   "layout": "8-byte BINNED records in HBM (first_bin << 2 | shape, filter byte, the two table indices of tiddit_coverage.pyx:53-63: "
+                             "csrc/tdt_cov_record.h cov_bin_record) — what the ingest kernel writes when the reader is bound to this histogram "
+                             "(DeviceBamReader.bin_for): the division and the bin split are done once where the record is made.  "
+                             "'packed_layout' times the same launch from the bin-size-agnostic packed records (start | span:24 mapq:6 flags), "
+                             "'four_array_layout' from separate start/end/mapq/flag arrays (11 B/read), 'pack_*_ms' the one-off conversions from "
+                             "four arrays (outside the timed region)",
+                   "arithmetic": "int64 accumulation of the reference's float32 quotients at 2^-S fixed point (exact), float64 bins out"},
+        "reads_per_sec": job_reads / (t_cov / args.steps),
+        # (from the HIP events of the timed steps themselves; what takes runs of its own is added below with --full)
+        "roofline": {"bound": "hbm", "kernel": "cov_accumulate", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "avg_launch_ms": kern_ms,
+                     "median_launch_ms": kern_all[len(kern_all) // 2], "min_launch_ms": kern_all[0],
+                     "algorithmic_bytes_per_launch": alg_bytes_launch,
+                     "bytes_model": "8 B/read (binned record) + 8 B/bin: what this launch's input layout holds"},
+    }
+    if not args.full:                                        # a plain run: the headline is all it measures
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, {"coverage_bins": dumped}, rank, world)
+        if rank == 0:
+            result["run_s"] = {"total": time.perf_counter() - t_run0}
+            emit_plain(result, args)
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
     alg_bytes_4 = 11.0 * total_reads + 8.0 * total_bins
     survey_bytes = 12.0 * total_reads + 8.0 * total_bins
-    achieved = alg_bytes_launch / (kern_ms * 1e-3) / 1e9
     # the same launch fed from the four separate arrays (start, end, mapq, flag: 11 B/read), for the record
     ev4 = []
     for k4 in range(args.warmup + min(args.steps, 10)):
@@ -323,47 +369,22 @@ def main():
     except Exception as e:                                    # (a measurement aid: its absence never fails the bench)
         stream_read = {"error": str(e)}
 
-    result = {
-        "metric": "cov bins/sec, 30x WGS synthetic (signals clustered/sec: see 'dbscan')",
-        "value": job_bins / (t_cov / args.steps),
-        "unit": "bins/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "int64",
-        "data": "synthetic",
-        "config": {"workload": "BASELINE configs[1]: coverage histogram, %d contigs x %d bp (%.2f Gb), %dx 150-bp sorted "
-                               "stream, %d-bp bins, q>=%d filter; contigs split over the %d rank(s)" % (C_all, L, C_all * L / 1e9, args.depth, z, args.min_q, world),
-                   "reads": job_reads, "bins": job_bins, "reads_rank0": total_reads, "bins_rank0": total_bins, "launches_per_step": 3,
-                   "layout_short": "8-byte BINNED records in HBM as the ingest kernel writes them (DESIGN 3.1): `value` prices the ACCUMULATE stage of "
-                                   "ingest -> accumulate; roofline.contract_* is SURVEY 8(d)'s four arrays in one launch",
-                   "layout": "8-byte BINNED records in HBM (first_bin << 2 | shape, filter byte, the two table indices of tiddit_coverage.pyx:53-63: "
-                             "csrc/tdt_cov_record.h cov_bin_record) — what the ingest kernel writes when the reader is bound to this histogram "
-                             "(DeviceBamReader.bin_for): the division and the bin split are done once where the record is made.  "
-                             "'packed_layout' times the same launch from the bin-size-agnostic packed records (start | span:24 mapq:6 flags), "
-                             "'four_array_layout' from separate start/end/mapq/flag arrays (11 B/read), 'pack_*_ms' the one-off conversions from "
-                             "four arrays (outside the timed region)",
-                   "pack_binned_from_four_arrays_ms": bin_pack_ms, "pack_from_four_arrays_ms": pack_ms,
-                   "arithmetic": "int64 accumulation of the reference's float32 quotients at 2^-S fixed point (exact), float64 bins out"},
-        "reads_per_sec": job_reads / (t_cov / args.steps),
-        "roofline": {"bound": "hbm", "kernel": "cov_accumulate", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": TRAFFIC_NOTE,
-                     "frac_traffic": None if traffic is None else traffic / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "avg_launch_ms": kern_ms,
-                     "median_launch_ms": kern_all[len(kern_all) // 2], "min_launch_ms": kern_all[0],
-                     "algorithmic_bytes_per_launch": alg_bytes_launch,
-                     "stream_read": stream_read,
-                     "frac_of_stream_read": (achieved / stream_read["GB_per_s"]) if stream_read and "GB_per_s" in stream_read else None,
-                     "bytes_model": "8 B/read (binned record) + 8 B/bin: what this launch's input layout holds",
-                     "pack_binned_from_four_arrays_ms": bin_pack_ms,
-                     "from_four_arrays_incl_pack": {"ms": bin_pack_ms + kern_ms, "frac": alg_bytes_4 / ((bin_pack_ms + kern_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                                    "note": "a caller holding SURVEY §8(d)'s four arrays pays the one-off packing pass first; the device ingest writes the records itself"}},
-        "packed_layout": {"avg_launch_ms": sum(msp) / len(msp), "median_launch_ms": msp[len(msp) // 2], "min_launch_ms": msp[0],
-                          "algorithmic_bytes_per_launch": alg_bytes_launch, "bytes_model": "8 B/read (packed record) + 8 B/bin",
-                          "frac": alg_bytes_launch / (sum(msp) / len(msp) * 1e-3) / 1e9 / HBM_PEAK_GBS},
-        "four_array_layout": {"avg_launch_ms": sum(ms4) / len(ms4), "median_launch_ms": ms4[len(ms4) // 2], "min_launch_ms": ms4[0],
-                              "algorithmic_bytes_per_launch": alg_bytes_4, "bytes_model": "11 B/read (start i32, end i32, mapq u8, flag u16) + 8 B/bin",
-                              "frac": alg_bytes_4 / (sum(ms4) / len(ms4) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              "frac_survey_8d_12B_per_read": survey_bytes / (sum(ms4) / len(ms4) * 1e-3) / 1e9 / HBM_PEAK_GBS},
-    }
+    result["config"].update({"pack_binned_from_four_arrays_ms": bin_pack_ms, "pack_from_four_arrays_ms": pack_ms})
+    result["roofline"].update({
+        "traffic": traffic, "traffic_source": TRAFFIC_NOTE,
+        "frac_traffic": None if traffic is None else traffic / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+        "stream_read": stream_read,
+        "frac_of_stream_read": (achieved / stream_read["GB_per_s"]) if stream_read and "GB_per_s" in stream_read else None,
+        "pack_binned_from_four_arrays_ms": bin_pack_ms,
+        "from_four_arrays_incl_pack": {"ms": bin_pack_ms + kern_ms, "frac": alg_bytes_4 / ((bin_pack_ms + kern_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                       "note": "a caller holding SURVEY §8(d)'s four arrays pays the one-off packing pass first; the device ingest writes the records itself"}})
+    result["packed_layout"] = {"avg_launch_ms": sum(msp) / len(msp), "median_launch_ms": msp[len(msp) // 2], "min_launch_ms": msp[0],
+                               "algorithmic_bytes_per_launch": alg_bytes_launch, "bytes_model": "8 B/read (packed record) + 8 B/bin",
+                               "frac": alg_bytes_launch / (sum(msp) / len(msp) * 1e-3) / 1e9 / HBM_PEAK_GBS}
+    result["four_array_layout"] = {"avg_launch_ms": sum(ms4) / len(ms4), "median_launch_ms": ms4[len(ms4) // 2], "min_launch_ms": ms4[0],
+                                   "algorithmic_bytes_per_launch": alg_bytes_4, "bytes_model": "11 B/read (start i32, end i32, mapq u8, flag u16) + 8 B/bin",
+                                   "frac": alg_bytes_4 / (sum(ms4) / len(ms4) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                   "frac_survey_8d_12B_per_read": survey_bytes / (sum(ms4) / len(ms4) * 1e-3) / 1e9 / HBM_PEAK_GBS}
 
     # ---------------------------------------------------------------- CPU baseline + in-bench parity (rank 0, N=1)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -1023,7 +1044,8 @@ def compact_line(result):
         r["ingest_records_per_sec"] = secs["ingest"]["records_per_sec"]
     if secs.get("sv_e2e", {}).get("wall_s") is not None:
         r["sv_e2e_wall_s"] = secs["sv_e2e"]["wall_s"]
-    r["sections"] = secs
+    if secs:
+        r["sections"] = secs
     line["roofline"] = r
     cb = result.get("cpu_baseline")
     if cb:
@@ -1084,21 +1106,10 @@ def emit(result, args):
         detail = os.path.relpath(path, os.path.dirname(os.path.abspath(__file__)))
     except OSError as e:
         detail = "not written: %s" % e
+    flush_stdout()
     if getattr(args, "full_line", False):
-        try:
-            sys.stdout.flush()
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
         print(json.dumps(result), flush=True)
         return
-    # whatever native libraries still hold in C stdio buffers (RCCL's start-up banner is written through libc's stdout and would
-    # otherwise be flushed at exit, BEHIND the JSON line) goes out first: the record is the last line of stdout
-    try:
-        sys.stdout.flush()
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
     line = compact_line(result)
     line["detail"] = detail
     text = json.dumps(line)
@@ -1109,6 +1120,23 @@ def emit(result, args):
         line.pop(k, None)
         text = json.dumps(line)
     print(text, flush=True)
+
+
+def emit_plain(result, args):
+    """a plain run's line: the headline record in the compact form (the whole record with --full-line); it is short, and nothing else
+    was measured, so no detailed record is written beside it"""
+    flush_stdout()
+    print(json.dumps(result if getattr(args, "full_line", False) else compact_line(result)), flush=True)
+
+
+def flush_stdout():
+    """whatever native libraries still hold in C stdio buffers (RCCL's start-up banner is written through libc's stdout and would
+    otherwise be flushed at exit, BEHIND the JSON line) goes out first: the record is the last line of stdout"""
+    try:
+        sys.stdout.flush()
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
 
 
 # ---- --dump-outputs: what the timed path computed, for comparing two builds output for output

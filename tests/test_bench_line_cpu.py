@@ -120,3 +120,44 @@ def test_dump_outputs_whole_below_the_budget_seeded_sample_above(bench, tmp_path
     bench.dump_outputs(str(tmp_path / "r"), {"coverage_bins": big}, rank=1, world=2)
     assert sorted(f.name for f in (tmp_path / "r").glob("*.npy")) == ["coverage_bins_rank1.npy", "coverage_bins_rank1_index.npy"]
     assert sum(f.stat().st_size for f in (tmp_path / "r").glob("*.npy")) <= 32 * 10**6
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(bench, monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` measures the headline alone; everything else runs behind --full"""
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-gc"])
+    a = bench.parse()
+    assert a.full and a.no_gc
+
+
+def test_plain_line_is_the_headline_record_and_writes_no_detail(bench, capsys, tmp_path, monkeypatch):
+    """a plain run's record (the contract's keys, the workload, the roofline of the timed launches) printed as ONE line in the
+    compact form; no section, CPU baseline or detail file comes with it"""
+    name, d = _records()[-1]
+    keys = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+            "reads_per_sec", "config")
+    rec = {k: d[k] for k in keys}
+    rec["roofline"] = {k: d["roofline"][k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "avg_launch_ms", "median_launch_ms",
+                                                     "min_launch_ms", "algorithmic_bytes_per_launch", "bytes_model")}
+    rec["run_s"] = {"total": 12.5}
+    monkeypatch.setenv("TIDDIT_BENCH_DETAIL", str(tmp_path / "d.json"))
+
+    class A:
+        full_line = False
+    bench.emit_plain(rec, A)
+    printed = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+    assert len(printed) == 1
+    line = json.loads(printed[0])
+    for k in keys + ("roofline",):
+        assert k in line, k
+    assert line["value"] == pytest.approx(d["value"], rel=1e-5) and line["ms_per_step"] == pytest.approx(d["ms_per_step"], rel=1e-5)
+    assert line["roofline"]["frac"] == pytest.approx(d["roofline"]["frac"], rel=1e-5) and line["roofline"]["traffic"] is None
+    assert "sections" not in line["roofline"] and "cpu_baseline" not in line and "detail" not in line
+    assert line["run_s"]["total"] == 12.5
+    assert not (tmp_path / "d.json").exists()
+    A.full_line = True
+    bench.emit_plain(rec, A)
+    assert json.loads(capsys.readouterr().out.strip()) == rec

@@ -200,7 +200,7 @@ def test_signal_worker_has_the_reference_shape(sv_bam, tmp_path):
 
 
 def test_bench_runs_every_section_on_two_ranks_sharing_the_gpu(tmp_path):
-    """`bench.py --gpus 2` (the driver's multi-GPU invocation, torch.distributed.run, one process per rank) with TIDDIT_BENCH_SHARE_GPU=1:
+    """`bench.py --gpus 2 --full` (the driver's multi-GPU invocation, torch.distributed.run, one process per rank) with TIDDIT_BENCH_SHARE_GPU=1:
     both ranks on the box's one GPU, exchange over gloo — every section takes its N-rank path (contigs / bases split, the shared bucket
     list with its all-gather, ONE BAM as byte-range shards with the exact all-reduce, `tiddit --sv` as one job on two ranks) and rank 0
     prints ONE JSON line with the contract's keys; the N-rank sv_e2e candidates equal the one-rank run's"""
@@ -213,7 +213,7 @@ def test_bench_runs_every_section_on_two_ranks_sharing_the_gpu(tmp_path):
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    small = ["--steps", "2", "--warmup", "1", "--contigs", "4", "--contig-len", "8000000", "--dbscan-n", "300000", "--gc-len", "50000000",
+    small = ["--full", "--steps", "2", "--warmup", "1", "--contigs", "4", "--contig-len", "8000000", "--dbscan-n", "300000", "--gc-len", "50000000",
              "--sv-mb", "3", "--ingest-mb", "1", "--no-next", "--no-cpu-baseline"]
     detail = str(tmp_path / "detail.json")
     env = dict(os.environ, TIDDIT_BENCH_SHARE_GPU="1", TIDDIT_BENCH_TMP=str(tmp_path), TIDDIT_BENCH_DETAIL=detail)
@@ -240,6 +240,38 @@ def test_bench_runs_every_section_on_two_ranks_sharing_the_gpu(tmp_path):
     a = open(os.path.join(str(tmp_path), "tiddit_bench_sv_3", "run1.candidates.tab")).read()
     b = open(os.path.join(str(tmp_path), "tiddit_bench_sv_3", "run2.candidates.tab")).read()
     assert a == b
+
+
+def test_bench_plain_run_is_the_headline_of_the_full_run(tmp_path):
+    """a plain `bench.py` run measures the headline alone (no section, CPU baseline or detailed record) and computes what the
+    headline of a --full run computes: the coverage bins both dump are equal, and --full checks them against the CPU oracle"""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--contigs", "2", "--contig-len", "8000000"]
+    detail = tmp_path / "detail.json"
+    env = dict(os.environ, TIDDIT_BENCH_TMP=str(tmp_path), TIDDIT_BENCH_DETAIL=str(detail))
+
+    def run(*extra):
+        out = subprocess.run([sys.executable, os.path.join(repo, "bench.py")] + small + list(extra), env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    d = run("--dump-outputs", str(tmp_path / "plain"))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert k in d, k
+    assert d["value"] > 0 and d["unit"] == "bins/s" and d["higher_is_better"] is True and d["dtype"] == "int64" and d["ms_per_step"] > 0
+    assert d["config"]["bins"] == 2 * 16000 and d["roofline"]["frac"] > 0
+    for k in ("cpu_baseline", "parity_checked", "coverage_sv", "dbscan", "dbscan_shared", "gc", "ingest", "next_rows", "sv_e2e", "detail"):
+        assert k not in d, k
+    assert not detail.exists()
+    f = run("--full", "--no-cov-sv", "--no-dbscan", "--no-gc", "--no-ingest", "--no-next", "--no-sv-e2e", "--dump-outputs", str(tmp_path / "full"))
+    assert f["metric"] == d["metric"] and f["config"]["workload"] == d["config"]["workload"]
+    assert f["parity_checked"] is True and f["cpu_baseline"]["value"] > 0 and detail.exists()
+    bins = np.load(tmp_path / "plain" / "coverage_bins.npy")
+    assert len(bins) == 2 * 16000 and bins.sum() > 0 and np.array_equal(bins, np.load(tmp_path / "full" / "coverage_bins.npy"))
 
 
 def test_signal_main_on_a_file_that_is_not_in_contig_order(sv_bam, tmp_path):

@@ -2,7 +2,7 @@
 # same-box A/B of ingest builds (variants/lib_<name>.so vs the in-tree library) on bench.py's ingest section: tools/ab_ingest.sh [<variant> ...]
 # prints records/s and the per-stage sums of the one-batch pass (find_records / chain_check / decode are what the segment size and the decode kernel move)
 cd /tmp && export TMPDIR=/tmp
-ARGS="--no-gc --no-next --no-cov-sv --no-dbscan --no-sv-e2e --no-cpu-baseline --contigs 1"
+ARGS="--full --no-gc --no-next --no-cov-sv --no-dbscan --no-sv-e2e --no-cpu-baseline --contigs 1"
 one() {
   local label=$1 lib=$2
   if [ -n "$lib" ]; then export TIDDIT_ALLOW_VARIANT=1 TIDDIT_HIP_LIB=$lib; else unset TIDDIT_HIP_LIB; fi
