@@ -19,36 +19,6 @@
 // ---- measurement builds declare themselves (tdt_build_flags): the macros this file was compiled with, before any default is set
 extern const char *const tdt_variant_coverage;
 const char *const tdt_variant_coverage = ""
-#ifdef COV_EXP_LOADONLY
-    " COV_EXP_LOADONLY"
-#endif
-#ifdef COV_EXP_NOATOMIC
-    " COV_EXP_NOATOMIC"
-#endif
-#ifdef COV_EXP_NOSCAN
-    " COV_EXP_NOSCAN"
-#endif
-#ifdef COV_M1X_NOK
-    " COV_M1X_NOK"
-#endif
-#ifdef COV_M1X_NOLAST
-    " COV_M1X_NOLAST"
-#endif
-#ifdef COV_M1X_NOSPILL
-    " COV_M1X_NOSPILL"
-#endif
-#ifdef COV_M1X_SPILLKIND
-    " COV_M1X_SPILLKIND"
-#endif
-#ifdef COV_M1_SCANK
-    " COV_M1_SCANK"
-#endif
-#ifdef COV_M1_SKIPZERO
-    " COV_M1_SKIPZERO"
-#endif
-#ifdef COV_M1_SPILL_R4
-    " COV_M1_SPILL_R4"
-#endif
 #ifdef COV_MIN_WAVES
     " COV_MIN_WAVES"
 #endif
@@ -60,9 +30,6 @@ const char *const tdt_variant_coverage = ""
 #endif
 #ifdef COV_MIN_WAVES4
     " COV_MIN_WAVES4"
-#endif
-#ifdef COV_PF2
-    " COV_PF2"
 #endif
 #ifdef COV_RPL
     " COV_RPL"
@@ -437,11 +404,6 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
         else return cov_load<RPL>(I, idx, r1);
     };
     auto cur = load_tile(r0 + (unsigned long long)tid * RPL);
-#ifdef COV_PF2           // measurement variant: two tiles in flight per wave instead of one (MODE 1)
-    constexpr bool PF2 = MODE == 1;
-    auto ahead = cur;
-    if (PF2 && r0 + TILE < r1) ahead = load_tile(r0 + TILE + (unsigned long long)tid * RPL);
-#endif
 
     for (int i = tid; i < WIN + 2; i += COV_THREADS) win[i] = 0;
     if (LDS_LUT) {
@@ -494,12 +456,8 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
     // plain (difference-free) contribution, any bin
     auto contribute = [&](int bin, unsigned long long v) {
         const unsigned off = (unsigned)(bin - base);
-#ifdef COV_EXP_NOATOMIC  // measurement variant (tools/build_variant.sh): everything but the LDS atomics — DESIGN.md §3.1 ceilings
-        if (v == 0x1234567ull) win[0] = v;
-#else
         if (off < (unsigned)WIN) atomicAdd(&win[off], v);  // ds_add_u64 (bins past the contig end only ever see +x and -x)
         else if ((unsigned)bin <= (unsigned)last_bin) cov_global_add(I.acc, bin, v);
-#endif
     };
 
     // the literal per-read update (tiddit_coverage.pyx:50-72) for reads the register path cannot hold
@@ -519,9 +477,8 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
     // spill the LDS window to the accumulators (coalesced 64-bit global atomics, zero bins skipped) and clear it
     auto spill = [&]() {
         __syncthreads();
-#if !defined(COV_M1_SPILL_R4)
         if constexpr (MODE == 1) {
-            // ONE pass resolves the difference counts and spills (round 5; COV_M1_SPILL_R4 keeps round 4's two passes for A/B runs).
+            // ONE pass resolves the difference counts and spills (round 5).
             // Thread t owns the words t, t + 256, ... (row k = words [256 k, 256 k + 256)): every LDS access of the pass is a wave's
             // contiguous 512 bytes (round 4 gave a thread eight CONSECUTIVE words — a 64-byte lane stride, four lanes per bank — read them
             // twice and wrote them twice).  The prefix over the window = per row a wave scan (the eight rows' 16-bit difference counts
@@ -561,53 +518,15 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
                 const int i = k * COV_THREADS + tid;
                 if (w[k]) win[i] = 0;
                 if (v) {
-#ifdef COV_M1X_NOSPILL   // measurement variant: what the 60 M global atomics of the 50-bp flavour cost
-                    if (v == 0x1234567ull)
-#endif
-#if defined(COV_M1X_SPILLKIND) && COV_M1X_SPILLKIND == 1      // MEASUREMENT ONLY (races at the borders): plain load / add / store
-                    if (base + i <= last_bin) I.acc[base + i] += v;
-#elif defined(COV_M1X_SPILLKIND) && COV_M1X_SPILLKIND == 2    // MEASUREMENT ONLY: atomics executed in the XCD's own L2 (workgroup scope)
-                    if (base + i <= last_bin) __hip_atomic_fetch_add(&I.acc[base + i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#elif defined(COV_M1X_SPILLKIND) && COV_M1X_SPILLKIND == 3    // MEASUREMENT ONLY: stores
-                    if (base + i <= last_bin) I.acc[base + i] = v;
-#else
                     if (base + i <= last_bin) atomicAdd(&I.acc[base + i], v);
-#endif
                 }
             }
             __syncthreads();                                  // (s_rtot is rewritten by the next spill, the window by the next tile)
             return;
         }
-#endif
-        if (MODE == 1) {
-            // resolve the difference counts: thread t owns window entries [PER*t, PER*t + PER)
-            constexpr int PER = WIN / COV_THREADS;
-            int d = 0;
-#pragma unroll
-            for (int k = 0; k < PER; k++) d += (int)((long long)win[tid * PER + k] >> COV_DBIT);
-            int incl = d;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int up = __shfl_up(incl, o);
-                if (lane >= o) incl += up;
-            }
-            if (lane == 63) s_wsum[tid >> 6] = incl;
-            __syncthreads();
-            int run = incl - d;
-            for (int wv = 0; wv < (tid >> 6); wv++) run += s_wsum[wv];
-#pragma unroll
-            for (int k = 0; k < PER; k++) {
-                const unsigned long long w = win[tid * PER + k];
-                run += (int)((long long)w >> COV_DBIT);
-                win[tid * PER + k] = (w & COV_LOWMASK) + (unsigned long long)(long long)run * P.one;
-            }
-            __syncthreads();
-        }
         for (int i = tid; i < WIN; i += COV_THREADS) {
             const unsigned long long v = win[i];
             if (v) {
-#ifdef COV_M1X_NOSPILL
-                if (MODE != 1 || v == 0x1234567ull)
-#endif
                 if (base + i <= last_bin) atomicAdd(&I.acc[base + i], v);
                 win[i] = 0;
             }
@@ -620,16 +539,8 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
 
     for (unsigned long long t0 = r0; t0 < r1; t0 += TILE) {
         // software prefetch: the next tile's loads are in flight while this one is reduced
-#ifdef COV_PF2
-        auto nxt = cur;
-        if constexpr (PF2) {
-            nxt = ahead;
-            if (t0 + 2 * TILE < r1) ahead = load_tile(t0 + 2 * TILE + (unsigned long long)tid * RPL);
-        } else if (t0 + TILE < r1) nxt = load_tile(t0 + TILE + (unsigned long long)tid * RPL);
-#else
         auto nxt = cur;
         if (t0 + TILE < r1) nxt = load_tile(t0 + TILE + (unsigned long long)tid * RPL);
-#endif
 
         // window re-base (block-uniform): when this tile's last read starts near the window's end the window is spilled
         // and moved to the previous tile's last read, so sparse streams / small bins stay on the LDS path
@@ -659,12 +570,6 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
             const unsigned minq24 = (unsigned)P.min_q << 24, qlim = (64u - (unsigned)P.min_q) << 24;
             unsigned long long slow_any = 0;
             unsigned long long a0 = 0, a1 = 0, a2 = 0;
-#ifdef COV_EXP_LOADONLY  // measurement variant: the loads alone (the ceiling of this access pattern)
-            for (int j = 0; j < RPL; j++) a0 += cur.w[j];
-            if (a0 == 0x1234567ull) contribute(K, a0);
-            cur = nxt;
-            continue;
-#endif
             if constexpr (MODE == 0) {
                 const bool safe = ko < (unsigned)(WIN - 3);
                 const unsigned kw = safe ? ko : 0u;
@@ -707,17 +612,6 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
                 // bin K+2 only ever receives the last-bin part of a two-bin read that starts in bin K+1 — reads behind a bin boundary inside
                 // the lane's eight, a few lanes per wave and hardly two of them on one bin: those go to the window directly, and only
                 // the sums of bins K and K+1 take the wavefront merge (two values instead of three through the scan)
-#ifdef COV_EXP_NOATOMIC
-                if (a0 + a1 + a2 == 0x1234567ull) win[0] = a0;
-                cur = nxt;
-                continue;
-#endif
-#ifdef COV_EXP_NOSCAN
-                if (a0 + a1 + a2 == 0x1234567ull) win[0] = a0;
-                if (a2) atomicAdd(&win[kw + 2], a2);
-                cur = nxt;
-                continue;
-#endif
                 if (a2) atomicAdd(&win[kw + 2], a2);
                 wave_scan2_u64(a0, a1);
                 const int Kprev = (int)__builtin_amdgcn_update_dpp((unsigned)~K, (unsigned)K, DPP_WAVE_SHR1, 0xf, 0xf, false);
@@ -765,42 +659,11 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
                     vL[j] = cov_lds_read64(cov_select(m_multi, (((hi >> 8) & 0xffu) << 3) + tL, tL0));     // the last bin's quotient with the -1 of the pair
                     woff[j] = cov_select(m_multi, (((d >> 2) + ((hi >> 16) & 0xffu)) << 3) + wK, wSpare);
                 }
-#ifndef COV_M1X_NOLAST   // COV_M1X_*: measurement variants (tools/build_variant.sh) — what each group of LDS operations costs
 #pragma unroll
                 for (int j = 0; j < RPL; j++) cov_lds_add64(woff[j], vL[j]);
-#else
-                if (vL[0] + vL[1] + vL[2] + vL[3] + woff[0] + woff[1] + woff[2] + woff[3] == 0x1234567ull) win[0] = 1;
-#endif
-#ifdef COV_M1X_NOK
-                if (a0 + a1 + d12 + d2 == 0x1234567ull) win[0] = a0;
-#elif defined(COV_M1_SCANK)
-                // equal-K neighbours (2-3 lanes share a 50-bp first bin) merged before they reach the window: inclusive wave scan of the
-                // two sums, the run's tail adds P[tail], its head takes P[head - 1] back (exact in modular arithmetic, like MODE 0)
-                {
-                    unsigned long long s0 = a0, s1 = a1 + ((unsigned long long)(d12 - d2) << COV_DBIT);
-                    if (d2) atomicAdd(&win[kw + 2], (unsigned long long)d2 << COV_DBIT);
-                    wave_scan2_u64(s0, s1);
-                    const int Kprev = (int)__builtin_amdgcn_update_dpp((unsigned)~K, (unsigned)K, DPP_WAVE_SHR1, 0xf, 0xf, false);
-                    const int Knext = (int)__builtin_amdgcn_update_dpp((unsigned)~K, (unsigned)K, DPP_WAVE_SHL1, 0xf, 0xf, false);
-                    const unsigned long long q0 = dpp_u64<DPP_WAVE_SHR1>(s0), q1 = dpp_u64<DPP_WAVE_SHR1>(s1);
-                    if (safe && Knext != K) {
-                        atomicAdd(&win[kw], s0);
-                        atomicAdd(&win[kw + 1], s1);
-                    }
-                    if (safe && Kprev != K && lane != 0) {
-                        atomicAdd(&win[kw], 0ull - q0);
-                        atomicAdd(&win[kw + 1], 0ull - q1);
-                    }
-                }
-#else
                 atomicAdd(&win[kw], a0);
                 atomicAdd(&win[kw + 1], a1 + ((unsigned long long)(d12 - d2) << COV_DBIT));
-#ifdef COV_M1_SKIPZERO
-                if (d2) atomicAdd(&win[kw + 2], (unsigned long long)d2 << COV_DBIT);
-#else
                 atomicAdd(&win[kw + 2], (unsigned long long)d2 << COV_DBIT);
-#endif
-#endif
                 if (slow_any) {
                     const unsigned long long idx = t0 + (unsigned long long)tid * RPL;
 #pragma unroll
@@ -865,12 +728,6 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
         const int K = div(sv[0] < 0 ? 0 : sv[0]);
         const unsigned Kz = (unsigned)K * z;
         unsigned long long a0 = 0, a1 = 0, a2 = 0;
-#ifdef COV_EXP_LOADONLY  // measurement variant: the loads alone (the 0.79 "load-only" ceiling quoted in DESIGN.md §3.1)
-        for (int j = 0; j < RPL; j++) a0 += (unsigned)(sv[j] + ev[j]) + mq[j] + fl[j];
-        if (a0 == 0x1234567ull) contribute(K, a0);
-        cur = nxt;
-        continue;
-#endif
         unsigned slowmask = 0;
         constexpr bool TABLED = MODE == 0 && LDS_LUT && !Z1;      // MODE 0 with the pair tables in LDS (2 <= bin_size < 1024)
         if (TABLED) {
@@ -930,7 +787,6 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
             const int Kprev = (int)__builtin_amdgcn_update_dpp((unsigned)~K, (unsigned)K, DPP_WAVE_SHR1, 0xf, 0xf, false);
             const int Knext = (int)__builtin_amdgcn_update_dpp((unsigned)~K, (unsigned)K, DPP_WAVE_SHL1, 0xf, 0xf, false);
             const unsigned long long q0 = dpp_u64<DPP_WAVE_SHR1>(a0), q1 = dpp_u64<DPP_WAVE_SHR1>(a1), q2 = dpp_u64<DPP_WAVE_SHR1>(a2);
-#ifndef COV_EXP_NOATOMIC
             if (safe && Knext != K) {  // run tail (lane 63 always: it reads ~K)
                 if (a0) atomicAdd(&win[kw], a0);
                 if (a1) atomicAdd(&win[kw + 1], a1);
@@ -941,7 +797,6 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
                 if (q1) atomicAdd(&win[kw + 1], 0ull - q1);
                 if (q2) atomicAdd(&win[kw + 2], 0ull - q2);
             }
-#endif
         } else if (MODE == 0) {
             // (bin_size 1, or >= 1024 with the tables in global memory) compare-and-select form of the same folding:
             // A read whose first bin is K or K+1 and whose last bin is at most one further is folded into the three
@@ -1039,14 +894,12 @@ __global__ __launch_bounds__(COV_THREADS, MODE == 1 ? (REC ? COV_MIN_WAVES1 : CO
                 vL[j] = tabL[multi ? bl1 - 1u : z + 1u];
                 woff[j] = multi ? kw + dq : (unsigned)WIN;
             }
-#ifndef COV_EXP_NOATOMIC
             // phase 2: the atomics
 #pragma unroll
             for (int j = 0; j < RPL; j++) atomicAdd(&win[woff[j]], vL[j]);
             atomicAdd(&win[kw], a0);
             atomicAdd(&win[kw + 1], a1 + ((unsigned long long)d1 << COV_DBIT));
             atomicAdd(&win[kw + 2], (unsigned long long)d2 << COV_DBIT);
-#endif
             if (slowmask) {
 #pragma unroll
                 for (int j = 0; j < RPL; j++)

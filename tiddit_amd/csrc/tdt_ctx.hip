@@ -17,15 +17,14 @@ void tdt_set_error(const char *fmt, ...) {
 extern "C" const char *tdt_last_error(void) { return g_err; }
 extern "C" int tdt_version(void) { return 100; }
 
-// The measurement macros (ablations: COV_M1X_*, B2_EXP_*, DT_PERSIST ...; tunables given on the command line: COV_WIN, B2_OCC, RS_ROUNDS ...)
-// the library's translation units were compiled with — "" for the product build.  Two of the ablations produce wrong results by design;
-// the Python binding refuses a library that reports any unless TIDDIT_ALLOW_VARIANT=1 (tools/ab_*.sh set it).
-extern const char *const tdt_variant_coverage, *const tdt_variant_dbscan, *const tdt_variant_inflate, *const tdt_variant_inflate2,
-    *const tdt_variant_ingest, *const tdt_variant_sort;
+// The tunables given on the command line (COV_WIN, B2_OCC, RS_ROUNDS ...) the library's translation units were compiled with — "" for
+// the product build.  The Python binding refuses a library that reports any unless TIDDIT_ALLOW_VARIANT=1 (tools/ab_*.sh set it).
+extern const char *const tdt_variant_coverage, *const tdt_variant_dbscan, *const tdt_variant_inflate2, *const tdt_variant_ingest,
+    *const tdt_variant_sort;
 extern "C" const char *tdt_build_flags(void) {
     static const std::string all = [] {
         std::string s;
-        for (const char *p : {tdt_variant_coverage, tdt_variant_dbscan, tdt_variant_inflate, tdt_variant_inflate2, tdt_variant_ingest, tdt_variant_sort}) s += p;
+        for (const char *p : {tdt_variant_coverage, tdt_variant_dbscan, tdt_variant_inflate2, tdt_variant_ingest, tdt_variant_sort}) s += p;
         return s.empty() ? s : s.substr(1);
     }();
     return all.c_str();

@@ -14,15 +14,6 @@
 // ---- measurement builds declare themselves (tdt_build_flags): the macros this file was compiled with, before any default is set
 extern const char *const tdt_variant_dbscan;
 const char *const tdt_variant_dbscan = ""
-#ifdef DB_BUCKET_PERLANE
-    " DB_BUCKET_PERLANE"
-#endif
-#ifdef DT_PERSIST
-    " DT_PERSIST"
-#endif
-#ifdef DT_PROF
-    " DT_PROF"
-#endif
 #ifdef DT_FTPB
     " DT_FTPB"
 #endif
@@ -54,8 +45,6 @@ const char *const tdt_variant_dbscan = ""
 int tdt_radix_sort_pairs(tdt_ctx *ctx, unsigned long long *keys, unsigned *vals, unsigned long long *keys_tmp, unsigned *vals_tmp,
                          size_t n, unsigned long long bitmask, unsigned long long **out_keys, unsigned **out_vals);   // tdt_sort.hip
 
-// largest b in [0, nb) with boff[b] <= i
-__device__ __forceinline__ int db_bucket(const int *__restrict__ boff, int nb, int i);
 // The bucket of position i when the wave's lanes hold positions inside [first, last] (first / last the same in every lane): the search
 // is done ONCE, on the scalar unit, for `first`; a wave of 64-128 consecutive positions almost never contains a bucket boundary (300
 // buckets in 10 M signals), and then one more scalar load settles it.  Lanes of a wave that does contain boundaries step forward from
@@ -63,9 +52,6 @@ __device__ __forceinline__ int db_bucket(const int *__restrict__ boff, int nb, i
 // where the one-bucket dbt_finish1 takes 14.)
 __device__ __forceinline__ int db_bucket_wave(const int *__restrict__ boff, int nb, int first, int last, int i) {
     if (nb == 1) return 0;
-#ifdef DB_BUCKET_PERLANE   // measurement variant: every lane searches for itself, as before round 5
-    return db_bucket(boff, nb, i);
-#endif
     const int f = __builtin_amdgcn_readfirstlane(first), l = __builtin_amdgcn_readfirstlane(last);
     int lo = 0, hi = nb;
     while (hi - lo > 1) {
@@ -78,6 +64,7 @@ __device__ __forceinline__ int db_bucket_wave(const int *__restrict__ boff, int 
         while (b + 1 < nb && boff[b + 1] <= i) b++;
     return b;
 }
+// largest b in [0, nb) with boff[b] <= i
 __device__ __forceinline__ int db_bucket(const int *__restrict__ boff, int nb, int i) {
     if (nb == 1) return 0;
     int lo = 0, hi = nb;
@@ -93,17 +80,6 @@ __device__ __forceinline__ unsigned db_absdiff(unsigned a, unsigned b) { return 
 
 #include "tdt_dbscan_fused.h"
 #include "tdt_dbscan_tile.h"
-
-// workgroups of a dbt_tile launch: what the chip holds at once (eight 256-thread workgroups per CU), or one per tile if that is fewer
-static inline int dbt_grid(const tdt_ctx *ctx, int ntiles) {
-#ifndef DT_PERSIST
-    (void)ctx;
-    return ntiles;
-#else
-    const int resident = ctx->num_cu * 8;
-    return ntiles < resident ? ntiles : resident;
-#endif
-}
 
 // ---------------------------------------------------------------------------------------- scan
 // In-place inclusive scan of a u32 array: reduce tiles -> scan the tile sums (one block) -> apply.
@@ -529,8 +505,7 @@ extern "C" int tdt_dbscan_device(tdt_ctx *ctx, const uint32_t *d_x, const uint32
         return TDT_OK;
     }
     const bool fused = m <= DBF_M_MAX;
-    static const bool no_tile = getenv("TIDDIT_DBSCAN_LAUNCHES") != nullptr;     // measurement switch: the multi-launch path only
-    if (fused && !no_tile && n < 0x7fff0000) {
+    if (fused && n < 0x7fff0000) {
         // tile-resident pass (tdt_dbscan_tile.h): three launches; falls through to the multi-launch path below when an
         // x-cluster is too large for it
         const int ntt = (n + DT_T - 1) / DT_T;
@@ -589,11 +564,10 @@ extern "C" int tdt_dbscan_device(tdt_ctx *ctx, const uint32_t *d_x, const uint32
         unsigned seq = ++tile_seq;
         if (seq == 0) seq = ++tile_seq;                                    // never 0
         hw[1] = 0;
-        const int tgrid = dbt_grid(ctx, ntt);
-        if (nb == 1 && mode == 0) hipLaunchKernelGGL((dbt_tile<true, false>), dim3(tgrid), dim3(DT_THREADS), 0, st, TP);
-        else if (nb == 1) hipLaunchKernelGGL((dbt_tile<true, true>), dim3(tgrid), dim3(DT_THREADS), 0, st, TP);
-        else if (mode == 0) hipLaunchKernelGGL((dbt_tile<false, false>), dim3(tgrid), dim3(DT_THREADS), 0, st, TP);
-        else hipLaunchKernelGGL((dbt_tile<false, true>), dim3(tgrid), dim3(DT_THREADS), 0, st, TP);
+        if (nb == 1 && mode == 0) hipLaunchKernelGGL((dbt_tile<true, false>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
+        else if (nb == 1) hipLaunchKernelGGL((dbt_tile<true, true>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
+        else if (mode == 0) hipLaunchKernelGGL((dbt_tile<false, false>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
+        else hipLaunchKernelGGL((dbt_tile<false, true>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
         TDT_CHECK_LAUNCH();
         if (nb == 1) {
             ctx->tile_groups_max = std::max(ctx->tile_groups_max, (ntt + DT_GRP - 1) / DT_GRP);
@@ -878,7 +852,7 @@ extern "C" int tdt_dbscan_y_device(tdt_ctx *ctx, const int32_t *d_xlab, const ui
     static std::atomic<unsigned> y_seq{0x40000000u};
     const unsigned seq = ++y_seq | 0x40000000u;
     hw[1] = 0;
-    hipLaunchKernelGGL((dbt_tile<true, false, true>), dim3(dbt_grid(ctx, ntt)), dim3(DT_THREADS), 0, st, TP);
+    hipLaunchKernelGGL((dbt_tile<true, false, true>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
     ctx->tile_groups_max = std::max(ctx->tile_groups_max, (ntt + DT_GRP - 1) / DT_GRP);
     hipLaunchKernelGGL(dbt_finish1, dim3((ntt + DT_FTPB - 1) / DT_FTPB), dim3(256), 0, st, (const unsigned short *)t_code, d_labels, n, (const int *)d_xlab,
                        (const unsigned *)t_aggR, (const unsigned *)t_aggE, ntt, (const unsigned *)TP.grp, odd ? t_grp0 : t_grp1, ctx->tile_groups_max,
@@ -1333,15 +1307,3 @@ extern "C" int tdt_host_free(void *p) {
     if (p) (void)hipHostFree(p);
     return TDT_OK;
 }
-
-#ifdef DT_PROF
-// variant builds only: per-phase cycles of dbt_tile summed over the workgroups of the last launch
-extern "C" int tdt_debug_dt_prof(unsigned long long *out16) {
-    static unsigned h[DT_PROF_TILES * 16];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(dt_prof), sizeof(h)) != hipSuccess) return -1;
-    for (int k = 0; k < 16; k++) out16[k] = 0;
-    for (int t = 0; t < DT_PROF_TILES; t++)
-        for (int k = 0; k < 16; k++) out16[k] += h[t * 16 + k];
-    return 0;
-}
-#endif

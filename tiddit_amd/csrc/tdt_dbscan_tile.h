@@ -45,15 +45,6 @@
 #define DT_GRP 64                           // tiles per group of the two-level count sums (one-bucket path)
 #define DT_GRPMAX (0x7fffffff / (DT_GRP * DT_T) + 2)   // groups of tiles a call can have (n < 2^31)
 
-#ifdef DT_PROF
-// variant builds only (tools/dt_prof.sh): shader-clock cycles per phase of dbt_tile as seen by thread 0, per workgroup
-#define DT_PROF_TILES 8192
-__device__ unsigned dt_prof[DT_PROF_TILES * 16];
-#define DT_MARK(k) do { if (ONE_BUCKET && !LABELS && tid == 0 && tile < DT_PROF_TILES) { const unsigned long long t_ = clock64(); dt_prof[tile * 16 + k] = (unsigned)(t_ - t_last); t_last = t_; } } while (0)
-#else
-#define DT_MARK(k) do { } while (0)
-#endif
-
 struct DtParams {
     const unsigned *x, *y;
     int n;
@@ -74,7 +65,7 @@ __device__ __forceinline__ void dt_signal_host(unsigned *flags, volatile unsigne
     if (blockIdx.x == 0 && threadIdx.x == 0 && host) {
         host[0] = flags[0];
         flags[0] = 0;                      // ready for the next call (nothing else touches it before the next tile kernel)
-        flags[1] = 0;                      // ... and so is the tile counter of the persistent grid
+        flags[1] = 0;                      // (word 1, once the tile counter of a persistent grid, is not read)
         __threadfence_system();
         host[1] = seq;
     }
@@ -121,20 +112,11 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
     ull *SY = BM;                        // the bucket-boundary stream is read by the x pass only
     __shared__ unsigned runBase[DT_NW + 1], extBase[DT_NW + 1];
     __shared__ unsigned s_owned, s_b0, s_b1;
-    int tid_ = threadIdx.x;
-#ifdef DT_PERSIST
-    // (inlined into the tile loop: without this opaque copy the compiler hoists everything derived from the thread index out of the
-    // loop and keeps it live across tiles — 64 VGPRs + 22 spilled to scratch against 42)
-    asm volatile("" : "+v"(tid_));
-#endif
-    const int tid = tid_, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = P.n, m = P.m;
     const int t0 = tile * DT_T;          // the host takes this path only for n < 2^31 - 2^16: int arithmetic cannot overflow
     const int sh0 = t0 - 64;
     unsigned *ysrt = xs;
-#ifdef DT_PROF
-    unsigned long long t_last = clock64();
-#endif
 
     // ---- stage x [t0-64, ...) and y [t0, t0+S) with 16-byte loads, zero outside the array
     {
@@ -211,7 +193,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
         }
     }
     __syncthreads();
-    DT_MARK(0);
 
     // ---- x pass: p words -1 .. NW-1   (PM[1 + W]; PM[0] = the word before the tile)
     auto p_word = [&](int W, auto m3) -> ull {                // m3: m == 3, the caller's usual l (tiddit_cluster.pyx: min_pts = 3)
@@ -283,7 +264,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
         else x_pass(std::false_type{});
     }
     __syncthreads();
-    DT_MARK(1);
 
     // ---- lane = word: run starts, labelled mask, cluster tails; counts of starts before every word
     if (wave == 0) {
@@ -319,7 +299,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
         }
     }
     __syncthreads();
-    DT_MARK(2);
     const unsigned n_owned = s_owned;
 
     // ---- lane = point: cluster ids and extents.  cid = index (1-based) of the point's cluster among the runs started in the
@@ -360,7 +339,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
         return;
     }
     __syncthreads();
-    DT_MARK(3);
 
     // ---- stable y order inside every owned cluster (:76-81): rank = members sorting before the point
     unsigned ext[DT_WPW];      // a | e << 16 of the point's cluster (0: not a member of an owned small cluster)
@@ -376,7 +354,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
         }
     }
     __syncthreads();           // every x read is done: xs becomes ysrt
-    DT_MARK(4);
 #pragma unroll
     for (int s = 0; s < DT_WPW; s++) {
         const int W = wave * DT_WPW + s;
@@ -406,7 +383,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
     }
     if (large) atomicOr(P.flags, 1u);
     __syncthreads();
-    DT_MARK(5);
 
     // ---- y pass on the sorted values: window test with m-1 following members (:90-99)
 #pragma unroll
@@ -423,7 +399,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
     }
     if (tid == 0) PY[0] = 0;
     __syncthreads();
-    DT_MARK(6);
     if (wave == 0) {   // lane = word: sub-run starts (a cluster head always starts one), labelled mask, starts before every word
         const int W = lane;
         ull sy = 0;
@@ -442,7 +417,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
         if (W < DT_NW) extBase[W] = incl - c;      // (the array holds the extra-start counts later)
     }
     __syncthreads();
-    DT_MARK(7);
     // sub-run number of a member = sub-run starts in [a, q] = starts up to q minus starts before the cluster's head, which the
     // head publishes; a start that is not the first of its cluster is an EXTRA (:112-122)
     unsigned short *cHead = segA;                  // the cluster extents live in registers by now
@@ -456,7 +430,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
         if (ext[s] && (int)(ext[s] & 0xffff) == q) cHead[(info[s] >> 1) - 1] = (unsigned short)(sub[s] - (unsigned)((sy >> lane) & 1ull));
     }
     __syncthreads();
-    DT_MARK(8);
 #pragma unroll
     for (int s = 0; s < DT_WPW; s++) {
         const int W = wave * DT_WPW + s;
@@ -469,7 +442,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
         if (lane == 0) EB[W] = w;
     }
     __syncthreads();
-    DT_MARK(9);
     if (wave == 0) {
         const unsigned c = lane < DT_NW ? (unsigned)dbf_popc(EB[lane]) : 0u;
         unsigned incl = c;
@@ -484,7 +456,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
         }
     }
     __syncthreads();
-    DT_MARK(10);
 
     // ---- results: -1.0 or a code, written at the member's ORIGINAL position (labels come back in input order)
 #pragma unroll
@@ -505,7 +476,6 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
             P.code[t0 + q] = (unsigned short)DT_C_MINUS1;       // not in any x-cluster
         }
     }
-    DT_MARK(11);
     if (!ONE_BUCKET) {
         for (unsigned b = s_b0 + tid; b < s_b1; b += DT_THREADS) {
             const int off = P.boff[b] - t0;
@@ -519,25 +489,12 @@ __device__ __forceinline__ void dbt_tile_body(const DtParams &P, const int tile)
 }
 
 // The launch: one workgroup per tile.  5 M points are 3552 tiles on 2048 resident slots — 1.73 "rounds", the second one 27 % empty — so a
-// PERSISTENT grid (as many workgroups as the chip holds, each taking tiles off one counter, P.flags[1]) was measured in round 4
-// (-DDT_PERSIST, tools/ab_db.sh): 93-100 us between events against 65-67 us, with or without the register spills the tile loop first
-// caused (64 VGPRs + 22 spilled; 57 and none with the opaque thread index below).  The tail round is cheaper than the loop: kept off.
+// PERSISTENT grid (as many workgroups as the chip holds, each taking tiles off one counter, P.flags[1]) was measured in round 4:
+// 93-100 us between events against 65-67 us, with or without the register spills the tile loop first caused (64 VGPRs + 22 spilled;
+// 57 and none with an opaque copy of the thread index).  The tail round is cheaper than the loop.
 template <bool ONE_BUCKET, bool XONLY, bool LABELS = false>
 __global__ __launch_bounds__(DT_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void dbt_tile(DtParams P) {
-#ifndef DT_PERSIST
     dbt_tile_body<ONE_BUCKET, XONLY, LABELS>(P, (int)blockIdx.x);
-#else
-    __shared__ int s_tile;
-    const int ntiles = (P.n + DT_T - 1) / DT_T;
-    for (;;) {
-        __syncthreads();                     // the previous tile's last LDS reads are done
-        if (threadIdx.x == 0) s_tile = (int)atomicAdd(P.flags + 1, 1u);
-        __syncthreads();
-        const int tile = s_tile;
-        if (tile >= ntiles) return;
-        dbt_tile_body<ONE_BUCKET, XONLY, LABELS>(P, tile);
-    }
-#endif
 }
 
 // exclusive scans of the per-tile counts; bases of every bucket; last_id; the host's status word

@@ -15,13 +15,6 @@
 //     reads what earlier stores of the same wave wrote;
 //   * every loop is bounded by ISIZE / the compressed length, a malformed stream sets the block's status and stops.
 // A second kernel checks each block's CRC32 (lane-parallel table CRC + GF(2) combine).
-// ---- measurement builds declare themselves (tdt_build_flags): the macros this file was compiled with, before any default is set
-extern const char *const tdt_variant_inflate;
-const char *const tdt_variant_inflate = ""
-#ifdef BZ_STATS
-    " BZ_STATS"
-#endif
-    ;
 
 #include "tdt_common.h"
 
@@ -43,18 +36,6 @@ enum { BZ_OK = 0, BZ_E_BTYPE = 1, BZ_E_STORED = 2, BZ_E_TABLE = 3, BZ_E_SYMBOL =
 typedef unsigned long long u64;
 
 __device__ __forceinline__ unsigned bz_rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-
-#ifdef BZ_STATS
-__device__ unsigned long long bz_stats[64];   // [0] literals [1] matches [2] match bytes [3] deflate blocks, [8+k] matches with dist < 2^k, [32+k] len < 2^k
-// BZ_STATS measurement builds only (tools/inflate_stats.py); not part of the shipped ABI
-extern "C" int tdt_debug_bz_stats(unsigned long long *out, int reset) {
-    if (reset) {
-        unsigned long long z[64] = {0};
-        return hipMemcpyToSymbol(HIP_SYMBOL(bz_stats), z, sizeof z) == hipSuccess ? 0 : -2;
-    }
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(bz_stats), 64 * 8) == hipSuccess ? 0 : -2;
-}
-#endif
 
 __constant__ unsigned char bz_clorder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
@@ -364,9 +345,6 @@ __global__ __launch_bounds__(64 * BZ_WAVES) void bgzf_inflate(const unsigned cha
             BZ_TAKE(e & 15);
             const unsigned sym = e >> 4;
             if (sym < 256) {
-#ifdef BZ_STATS
-                if (lane == 0) atomicAdd(&bz_stats[0], 1ull);
-#endif
                 litv = (unsigned)lane == nlit ? sym : litv;
                 nlit++;
                 if (nlit == 64) {
@@ -416,14 +394,6 @@ __global__ __launch_bounds__(64 * BZ_WAVES) void bgzf_inflate(const unsigned cha
                 dist = 1 + ((2 + (dc & 1)) << eb) + ((unsigned)bb & ((1u << eb) - 1));
                 BZ_TAKE(eb);
             }
-#ifdef BZ_STATS
-            if (lane == 0) {
-                atomicAdd(&bz_stats[1], 1ull);
-                atomicAdd(&bz_stats[2], (unsigned long long)len);
-                atomicAdd(&bz_stats[8 + (32 - __clz(dist))], 1ull);
-                atomicAdd(&bz_stats[32 + (32 - __clz(len))], 1ull);
-            }
-#endif
             BZ_FLUSH_LITS();
             if (dist > op) {
                 err = BZ_E_DIST;

@@ -17,38 +17,8 @@
 // ---- measurement builds declare themselves (tdt_build_flags): the macros this file was compiled with, before any default is set
 extern const char *const tdt_variant_inflate2;
 const char *const tdt_variant_inflate2 = ""
-#ifdef B2_EARLYM
-    " B2_EARLYM"
-#endif
-#ifdef B2_EXP_NOLIT
-    " B2_EXP_NOLIT"
-#endif
-#ifdef B2_EXP_NOOWN
-    " B2_EXP_NOOWN"
-#endif
-#ifdef B2_EXP_NOREPLAY
-    " B2_EXP_NOREPLAY"
-#endif
-#ifdef B2_HOP2
-    " B2_HOP2"
-#endif
-#ifdef B2_NOPERSIST
-    " B2_NOPERSIST"
-#endif
 #ifdef B2_OCC
     " B2_OCC"
-#endif
-#ifdef B2_PHASED
-    " B2_PHASED"
-#endif
-#ifdef B2_PIPE
-    " B2_PIPE"
-#endif
-#ifdef B2_PROF
-    " B2_PROF"
-#endif
-#ifdef B2_STATS
-    " B2_STATS"
 #endif
 #ifdef B2_TB_D
     " B2_TB_D"
@@ -58,15 +28,6 @@ const char *const tdt_variant_inflate2 = ""
 #endif
 #ifdef B2_WAVES
     " B2_WAVES"
-#endif
-#ifdef B2_WBITS
-    " B2_WBITS"
-#endif
-#ifdef B2_W2
-    " B2_W2"
-#endif
-#ifdef B2_W2_EARLY
-    " B2_W2_EARLY"
 #endif
     ;
 
@@ -89,29 +50,6 @@ const char *const tdt_variant_inflate2 = ""
 #define B2_WAVES 4
 #endif
 #define B2_PARMAX 16                       // longest match a lane copies by itself (bytes); 32 with two loads was measured: slower
-#ifndef B2_HOP2
-#define B2_HOP2 1
-#endif
-#ifndef B2_W2
-#define B2_W2 0                            // 1: TWO windows (128 bit offsets) per trip of the symbol loop — see the B2_W2 loop below
-#endif
-#ifndef B2_W2_EARLY
-#define B2_W2_EARLY 0                      // B2_W2: 1 = each set's first long match that reads only earlier trips' output is copied by all lanes in the own-lane
-                                           // phases (measured: +4.5 % / +7 % SLOWER than B2_W2 without it — the instructions it adds to every trip cost more
-                                           // than the replay round trips it saves, as B2_EARLYM in the one-window loop)
-#endif
-#ifndef B2_WBITS
-#define B2_WBITS 64                        // bit offsets a window's chain walk accepts (measurement builds: 32 / 16 — what a window costs apart from its symbols)
-#endif
-#ifndef B2_PHASED
-#define B2_PHASED 0                        // 1: all loads of the window's independent copies first, one wait, then all their stores (measured in round 4:
-#endif                                     // 15.0 ms against 14.75 at level 6, 16.9 against 17.4 at level 1 — kept as a variant; B2_EARLYM adds the window's
-#ifndef B2_EARLYM                          // first long independent match to the phase: 15.05 / 17.25)
-#define B2_EARLYM 0
-#endif
-#ifndef B2_PIPE
-#define B2_PIPE 0                          // 1: the copies pipelined over two windows (measured in round 4: 18.3 ms against 17.9, 22.4 against 21.7 —
-#endif                                     // the wait it moves is not what a window waits for; ten more live registers spill).  Kept as a variant.
 // LDS bytes per wave: lens 320 | lut_ll 4 << TB_LL | lut_d 4 << TB_D | sorted_ll 576 | sorted_d 64 | meta_ll 96 | meta_d 96 | ring 512 + 16
 // (the ring's first two dwords are mirrored behind it: a lane's three consecutive dwords never wrap, one address serves all three reads)
 #define B2_OFF_LUTLL 320
@@ -148,39 +86,6 @@ struct __attribute__((packed, aligned(1))) B2U128 {
 
 __device__ __forceinline__ unsigned b2_rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ unsigned b2_rl(unsigned v, unsigned lane) { return (unsigned)__builtin_amdgcn_readlane((int)v, (int)lane); }
-
-#ifdef B2_STATS   // measurement builds only (tools/inflate_stats2.py): what the windows of the lanes kernel are made of
-__device__ unsigned long long b2_stats[16];   // 0 windows, 1 symbols, 2 literals, 3 matches copied by their own lane, 4 replayed: longer than 16, 5 replayed: source
-                                              // inside the window's own output, 6 stops at a long code, 7 match bytes, 8 replayed match bytes
-extern "C" int tdt_debug_b2_stats(unsigned long long *out, int reset) {
-    if (reset) {
-        unsigned long long z[16] = {0};
-        return hipMemcpyToSymbol(HIP_SYMBOL(b2_stats), z, sizeof z) == hipSuccess ? 0 : -2;
-    }
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(b2_stats), 16 * 8) == hipSuccess ? 0 : -2;
-}
-#endif
-
-#ifdef B2_PROF   // measurement builds only (tools/inflate_prof.py): shader-clock cycles per phase of the window loop, summed over all waves
-__device__ unsigned long long b2_prof[16];    // 0 gather + LUT lookups, 1 per-lane lengths / distances, 2 chain walk (+ long codes), 3 prefix sum + checks,
-                                              // 4 literal store + own-lane copies (load, wait, stores), 5 replayed matches, 6 cursor + ring refill, 7 tables / headers, 8 windows,
-                                              // 9 the hops of the chain walk alone (2 then holds the long-code path), 10 long codes resolved, 11 DEFLATE block header + tables (7 then: between windows)
-extern "C" int tdt_debug_b2_prof(unsigned long long *out, int reset) {
-    if (reset) {
-        unsigned long long z[16] = {0};
-        return hipMemcpyToSymbol(HIP_SYMBOL(b2_prof), z, sizeof z) == hipSuccess ? 0 : -2;
-    }
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(b2_prof), 16 * 8) == hipSuccess ? 0 : -2;
-}
-#define B2_MARK(k_)                                               \
-    do {                                                          \
-        const unsigned long long t_ = __builtin_readcyclecounter(); \
-        pf[k_] += (unsigned)(t_ - pf_last);                       \
-        pf_last = t_;                                             \
-    } while (0)
-#else
-#define B2_MARK(k_) do { } while (0)
-#endif
 
 // lane's bit of a 64-bit scalar mask selects between two values: ONE v_cndmask with the mask as its SGPR-pair operand
 __device__ __forceinline__ unsigned b2_sel(u64 m, unsigned if_set, unsigned if_clear) {
@@ -317,105 +222,6 @@ __device__ __forceinline__ unsigned b2_scan(unsigned v) {
     return v;
 }
 
-// two independent inclusive prefix sums over the 64 lanes, their DPP steps interleaved: a step's result is read two instructions
-// later (the other value's step + one wait state), so the pair costs little more than one scan
-__device__ __forceinline__ void b2_scan2(unsigned &a, unsigned &b) {
-#define B2_S2(CTRL) "v_add_u32_dpp %0, %0, %0 " CTRL "\n\tv_add_u32_dpp %1, %1, %1 " CTRL "\n\ts_nop 0\n\t"
-    asm volatile("s_nop 1\n\t"
-                 B2_S2("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0")
-                 B2_S2("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0")
-                 B2_S2("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0")
-                 B2_S2("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0")
-                 B2_S2("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 B2_S2("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 "s_nop 0"
-                 : "+v"(a), "+v"(b));
-#undef B2_S2
-}
-
-// B2_W2: what the symbol starting `q` bits into the stream would be, for the lane's own q.  -> pk = the chain walk's packed word (bits 7:0 the
-// lane one symbol ahead, 64 when that hop leaves the window; from bit 8 where the walk stands after two symbols), sy = what the symbol
-// writes in ONE word: bits 8:0 the number of output bytes (0 end of block, 1 literal, 3..258 match), from bit 9 the literal byte or the
-// match's distance - 1
-__device__ __forceinline__ void b2_spec(const unsigned *win, const unsigned *lut_ll, const unsigned *lut_d, unsigned q, int lane, unsigned &pk, unsigned &sy) {
-    const unsigned qd = (q >> 5) & 127, qs = q & 31;
-    const unsigned wa = win[qd], wb = win[qd + 1], wc = win[qd + 2];
-    const unsigned lo = __builtin_amdgcn_alignbit(wb, wa, qs), hi = __builtin_amdgcn_alignbit(wc, wb, qs);
-    const unsigned e1 = lut_ll[lo & ((1u << B2_TB_LL) - 1)];
-    const unsigned step1 = B2_STEP(e1);
-    const unsigned e2 = lut_d[__builtin_amdgcn_ubfe(lo, step1, B2_TB_D)];
-    const bool is_len = e1 & B2_F_LEN;
-    const unsigned nxt = (unsigned)lane + step1 + (is_len ? B2_STEP(e2) : 0u);
-    const unsigned m1 = nxt < 64u ? nxt : 64u;
-    const unsigned n2r = (unsigned)__builtin_amdgcn_ds_bpermute((int)(m1 << 2), (int)nxt);
-    pk = m1 | ((nxt < 64u ? n2r : nxt) << 8);
-    const unsigned l1 = e1 & 15, eb1 = (e1 >> 4) & 15, litv = (e1 >> 8) & 0x1ff;
-    const unsigned mlen = litv + __builtin_amdgcn_ubfe(lo >> l1, 0u, eb1);
-    const unsigned l2 = e2 & 15, eb2 = (e2 >> 4) & 15, base2 = (e2 >> 8) & 0x7fff;
-    const unsigned dist = base2 + __builtin_amdgcn_ubfe(__builtin_amdgcn_alignbit(hi, lo, (step1 + l2) & 31), 0u, eb2);
-    sy = is_len ? (mlen | ((dist - 1u) << 9)) : ((e1 & B2_F_EOB) ? 0u : (1u | (litv << 9)));
-}
-
-// B2_W2: the chain of true symbol starts through one set of 64 bit offsets, from lane `cur` (scalar; two symbols per hop).  Codes longer
-// than the LUTs are resolved on the way and their lane's `sy` patched (as in the one-window loop).  -> chain = the lanes on it, cur = where
-// the walk left the set (64 .. 111: that many bits behind the set's first; the bits past an end of block when stop == 2)
-__device__ __forceinline__ void b2_walk(const unsigned *win, const unsigned *lut_ll, const unsigned *lut_d, const unsigned short *sorted_ll,
-                                        const unsigned short *meta_ll, const unsigned short *sorted_d, const unsigned short *meta_d, unsigned qbase,
-                                        int lane, unsigned pk, unsigned &sy, u64 &chain, unsigned &cur, unsigned &stop, unsigned &err) {
-    const unsigned start = cur;
-    for (;;) {
-        while (cur < 64u) {
-            const unsigned p2 = b2_rl(pk, cur);
-            asm("s_bitset1_b64 %0, %1" : "+s"(chain) : "s"(cur));
-            asm("s_bitset1_b64 %0, %1" : "+s"(chain) : "s"(p2));       // (bits 5:0 = the next symbol's lane, or lane 0 when that hop leaves the set: undone below)
-            cur = p2 >> 8;
-        }
-        if (__builtin_expect(cur < 128u, 1)) break;                      // (the common exit first, as in the one-window loop)
-        if (cur >= 256u) {
-            stop = 2;
-            cur -= 256u;
-            break;
-        }
-        const unsigned at = 63u - (unsigned)__builtin_clzll(chain);      // the chain's last member is the symbol the LUTs did not resolve
-        const unsigned qq = qbase + at, d = (qq >> 5) & 127, sh = qq & 31;
-        const unsigned w0 = b2_rfl(win[d]), w1 = b2_rfl(win[d + 1]), w2 = b2_rfl(win[d + 2]);
-        u64 v = ((u64)__builtin_amdgcn_alignbit(w2, w1, sh) << 32) | __builtin_amdgcn_alignbit(w1, w0, sh);
-        unsigned e = b2_rfl(lut_ll[(unsigned)v & ((1u << B2_TB_LL) - 1)]);
-        if (e == B2_ESC) e = b2_long_code((unsigned)v, B2_TB_LL, B2_MODE_LL, sorted_ll, meta_ll, lane);
-        if (e == B2_ESC) {
-            err = B2_E_SYMBOL;
-            break;
-        }
-        unsigned used = e & 15;
-        v >>= used;
-        unsigned s_sy = 1u | (((e >> 8) & 0xff) << 9);
-        if (e & B2_F_EOB) {
-            s_sy = 0;
-            stop = 2;
-        } else if (e & B2_F_LEN) {
-            unsigned eb = (e >> 4) & 15;
-            const unsigned s_len = ((e >> 8) & 0x1ff) + ((unsigned)v & ((1u << eb) - 1));
-            v >>= eb;
-            used += eb;
-            unsigned ed = b2_rfl(lut_d[(unsigned)v & ((1u << B2_TB_D) - 1)]);
-            if (ed == B2_ESC) ed = b2_long_code((unsigned)v, B2_TB_D, B2_MODE_DIST, sorted_d, meta_d, lane);
-            if (ed == B2_ESC) {
-                err = B2_E_DIST;
-                break;
-            }
-            v >>= ed & 15;
-            eb = (ed >> 4) & 15;
-            const unsigned s_dist = ((ed >> 8) & 0x7fff) + ((unsigned)v & ((1u << eb) - 1));
-            used += (ed & 15) + eb;
-            s_sy = s_len | ((s_dist - 1u) << 9);
-        }
-        b2_wl(sy, s_sy, at);
-        cur = at + used;
-        if (stop == 2) break;
-    }
-    if (start != 0) chain &= ~1ull;                                 // (a walk that starts behind lane 0 never has lane 0 on its chain)
-}
-
 // 64 stream bits starting `q` bits into the stream, gathered from the LDS ring (any lane, any q inside the staged windows)
 __device__ __forceinline__ u64 b2_bits_at(const unsigned *win, unsigned q) {
     const unsigned d = (q >> 5) & 127, s = q & 31;
@@ -433,17 +239,11 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
     // Persistent waves: the grid is what the chip holds at once (8 waves per SIMD) and every wave takes BGZF blocks off one counter
     // until none is left.  With one launch slot per block, a span of 20 k blocks ran as 2.5 "rounds" of 8192 resident waves, the last
     // one 60 % empty, and a workgroup's four slots stayed taken until its slowest block was done.
-#ifdef B2_NOPERSIST   // measurement variant: one launch slot per block, as before round 4
-    for (int once = 0; once < 1; once++) {
-    const int b = blockIdx.x * B2_WAVES + wv;
-    if (b >= nblocks) return;
-#else
     for (;;) {
     unsigned b_ = 0;
     if (lane == 0) b_ = atomicAdd(next_block, 1u);
     const int b = (int)b2_rfl(b_);
     if (b >= nblocks) return;
-#endif
     unsigned char *lds = lds_all[wv];
     unsigned char *lens = lds;
     unsigned *lut_ll = (unsigned *)(lds + B2_OFF_LUTLL), *lut_d = (unsigned *)(lds + B2_OFF_LUTD);
@@ -461,10 +261,6 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
     unsigned cw = 0;                                            // windows cw and cw+1 are staged (window w in ring half w & 1)
     unsigned err = B2_OK;
     unsigned op = 0;
-#ifdef B2_PROF
-    unsigned pf[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long pf_last = __builtin_readcyclecounter();
-#endif
 
 // ring half h (0 / 1) <- the 64 dwords of window w_; the ring's first two dwords are mirrored behind its end
 #define B2_STAGE(h_, w_)                                                                   \
@@ -495,38 +291,6 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
         }                                                                                 \
     } while (0)
 
-#if B2_PIPE
-    // copies of the previous window that are still to be stored: per lane its kind (1 = own-lane copy with the source bytes loaded,
-    // 2 = own-lane byte copy, 3 = replayed in stream order by all lanes), where, how long, how far back, and the loaded bytes
-    unsigned pd_kind = 0, pd_pos = 0, pd_mlen = 0, pd_dist = 0, pd_tail = 0;
-    B2U128 pd_v = {{0, 0, 0, 0}};
-#define B2_FLUSH()                                                                                               \
-    do {                                                                                                         \
-        if (pd_kind == 2u)                      /* a 3-byte match, or a source in the block's last bytes */      \
-            for (unsigned k_ = 0; k_ < pd_mlen; k_++) dst[pd_pos + k_] = dst[pd_pos - pd_dist + k_];             \
-        if (pd_kind == 1u) {                    /* whole dwords, the last one overlapping its predecessor */     \
-            unsigned char *const p_ = dst + pd_pos;                                                              \
-            reinterpret_cast<B2U32 *>(p_)->v = pd_v.w[0];                                                        \
-            if (pd_mlen >= 8) reinterpret_cast<B2U32 *>(p_ + 4)->v = pd_v.w[1];                                  \
-            if (pd_mlen >= 12) reinterpret_cast<B2U32 *>(p_ + 8)->v = pd_v.w[2];                                 \
-            if (pd_mlen >= 16) reinterpret_cast<B2U32 *>(p_ + 12)->v = pd_v.w[3];                                \
-            if (pd_mlen & 3) reinterpret_cast<B2U32 *>(p_ + pd_mlen - 4)->v = pd_tail;                           \
-        }                                                                                                        \
-        u64 mm_ = __ballot(pd_kind == 3u);      /* the others in stream order (they may read each other's output) */ \
-        while (mm_) {                                                                                            \
-            const unsigned l_ = (unsigned)__builtin_ctzll(mm_);                                                  \
-            mm_ &= ~(1ull << l_);                                                                                \
-            const unsigned len_ = b2_rl(pd_mlen, l_), dd_ = b2_rl(pd_dist, l_), q_ = b2_rl(pd_pos, l_), so_ = q_ - dd_; \
-            unsigned i_ = (unsigned)lane;                                                                        \
-            do {                                                                                                 \
-                const unsigned j_ = dd_ >= len_ ? i_ : i_ % dd_;   /* a distance shorter than the match repeats its source */ \
-                if (i_ < len_) dst[q_ + i_] = dst[so_ + j_];                                                     \
-                i_ += 64;                                                                                        \
-            } while (i_ - (unsigned)lane < len_);                                                                \
-        }                                                                                                        \
-        pd_kind = 0;                                                                                             \
-    } while (0)
-#endif
     bool last = false;
     while (!last && err == B2_OK) {
         u64 hb;
@@ -671,153 +435,10 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
             break;
         }
         // ---- the symbols of this block, a window of 64 bit offsets at a time
-        B2_MARK(11);                                                  // (block header + code lengths + the two table builds)
-#if B2_W2
-        // ---- TWO windows per trip: the lanes decode the symbols that would start at bp + lane AND at bp + 64 + lane, the chain is walked
-        // through the first set and on through the second, and what a trip pays once whatever it decodes — the ring gather and the LUT round
-        // trips, the prefix sum, the memory round trip of the own-lane copies, the cursor and the ring refill — is paid once per ~11 symbols
-        // instead of once per 5.4 (a -DB2_WBITS=32 / 16 build prices that part at half of a 64-bit window's time: profiles/r06_ab_inflate_w2.txt).
-        // A symbol's output size, literal byte and distance travel in one register (b2_spec), so the second set costs two live registers
-        // across the first one's walk.
-        for (;;) {
-            unsigned pk0, sy0, pk1, sy1;
-            b2_spec(win, lut_ll, lut_d, bp + (unsigned)lane, lane, pk0, sy0);
-            b2_spec(win, lut_ll, lut_d, bp + 64u + (unsigned)lane, lane, pk1, sy1);
-            u64 chain0 = 0, chain1 = 0;
-            unsigned stop = 0, cur = 0, adv = 0;
-            b2_walk(win, lut_ll, lut_d, sorted_ll, meta_ll, sorted_d, meta_d, bp, lane, pk0, sy0, chain0, cur, stop, err);
-            if (err != B2_OK) break;
-            if (stop != 2) {
-                cur -= 64u;                                             // (64 .. 111 behind the first set's first bit)
-                adv = 64u;
-                b2_walk(win, lut_ll, lut_d, sorted_ll, meta_ll, sorted_d, meta_d, bp + 64u, lane, pk1, sy1, chain1, cur, stop, err);
-                if (err != B2_OK) break;
-            }
-            adv += cur;
-            unsigned ol0 = b2_sel(chain0, sy0 & 0x1ffu, 0u), ol1 = b2_sel(chain1, sy1 & 0x1ffu, 0u);
-            unsigned incl0 = ol0, incl1 = ol1;
-            b2_scan2(incl0, incl1);
-            const unsigned tot0 = b2_rl(incl0, 63), tot = tot0 + b2_rl(incl1, 63);
-            const unsigned pos0 = op + incl0 - ol0, pos1 = op + tot0 + incl1 - ol1;
-            const bool copy0 = ol0 >= 3, copy1 = ol1 >= 3;
-            const unsigned x0 = sy0 >> 9, x1 = sy1 >> 9;                // literal byte / distance - 1
-            if (op + tot > isize || __ballot((copy0 && x0 >= pos0) || (copy1 && x1 >= pos1))) {
-                err = op + tot > isize ? B2_E_OVERRUN : B2_E_DIST;
-                break;
-            }
-            if (ol0 == 1) dst[pos0] = (unsigned char)x0;
-            if (ol1 == 1) dst[pos1] = (unsigned char)x1;
-            const unsigned srco0 = pos0 - x0 - 1u, srco1 = pos1 - x1 - 1u;
-            // own-lane copies of BOTH sets: sources wholly before this trip's output (op) and at most B2_PARMAX bytes.  ALL their loads, ONE
-            // wait, all their stores: a trip pays one memory round trip for them.  (The loaded words are deliberately not initialised and the
-            // wait is unconditional: a zeroed register that a masked load may still be writing, or a wait the compiler can only see on one side
-            // of an exec branch, makes its wait-count pass drain the queue — the previous trip's stores included — BEFORE the loads go out.)
-            const bool wide0 = copy0 && srco0 + ol0 <= op && ol0 <= B2_PARMAX && ol0 >= 4 && srco0 + 16 <= isize;
-            const bool wide1 = copy1 && srco1 + ol1 <= op && ol1 <= B2_PARMAX && ol1 >= 4 && srco1 + 16 <= isize;
-            const bool tri0 = copy0 && ol0 == 3 && srco0 + 3 <= op, tri1 = copy1 && ol1 == 3 && srco1 + 3 <= op;   // (the dword read ends at srco + 4 <= pos + 1 <= isize)
-            // The lanes on a chain are few (5.4 of a set's 64), so the two sets' own-lane copies share ONE set of copy instructions: a lane
-            // copies the first set's match if it has one, else the second set's; a lane with one in both (one trip in eight) leaves its
-            // second to the replay loop.
-            const bool par0 = wide0 || tri0, par1 = (wide1 || tri1) && !par0;
-            const bool wide = par0 ? wide0 : (wide1 && par1), tri = par0 ? tri0 : (tri1 && par1);
-            const unsigned olm = par0 ? ol0 : ol1, posm = par0 ? pos0 : pos1, srcom = par0 ? srco0 : srco1;
-            unsigned w3, tw;
-            B2U128 vv;
-            asm volatile("" : "=v"(w3), "=v"(tw), "=v"(vv.w[0]), "=v"(vv.w[1]), "=v"(vv.w[2]), "=v"(vv.w[3]));
-#if B2_W2_EARLY
-            // Each set's FIRST match that its lane cannot copy (longer than B2_PARMAX, or the lane's second) but that reads only what earlier
-            // trips wrote is independent of everything this trip writes: ALL lanes copy it — lane k the k-th dword, the lane behind them the
-            // last four bytes — with one load in the load phase and one store in the store phase, instead of a round trip of its own in
-            // the replay loop (three replayed matches in four are of this kind: profiles/r04_inflate_windows.txt).
-            const u64 ml0 = __ballot(copy0 && !par0 && srco0 + ol0 <= op && ol0 - 4u <= 252u);
-            const u64 ml1 = __ballot(copy1 && !par1 && srco1 + ol1 <= op && ol1 - 4u <= 252u);
-            unsigned e_len0 = 0, e_p0 = 0, e_so0 = 0, e_len1 = 0, e_p1 = 0, e_so1 = 0;
-            u64 e_bit0 = 0, e_bit1 = 0;
-            if (ml0) {
-                const unsigned l = (unsigned)__builtin_ctzll(ml0);
-                e_bit0 = 1ull << l;
-                e_len0 = b2_rl(ol0, l), e_p0 = b2_rl(pos0, l), e_so0 = b2_rl(srco0, l);
-            }
-            if (ml1) {
-                const unsigned l = (unsigned)__builtin_ctzll(ml1);
-                e_bit1 = 1ull << l;
-                e_len1 = b2_rl(ol1, l), e_p1 = b2_rl(pos1, l), e_so1 = b2_rl(srco1, l);
-            }
-            const unsigned nd0 = e_len0 >> 2, nd1 = e_len1 >> 2;
-            const bool ea0 = (unsigned)lane < nd0 || ((unsigned)lane == nd0 && (e_len0 & 3u));
-            const bool ea1 = (unsigned)lane < nd1 || ((unsigned)lane == nd1 && (e_len1 & 3u));
-            const unsigned eo0 = (unsigned)lane < nd0 ? 4u * (unsigned)lane : e_len0 - 4u, eo1 = (unsigned)lane < nd1 ? 4u * (unsigned)lane : e_len1 - 4u;
-            unsigned ev0, ev1;
-            asm volatile("" : "=v"(ev0), "=v"(ev1));
-            if (ea0) ev0 = reinterpret_cast<const B2U32 *>(dst + (e_so0 + eo0))->v;
-            if (ea1) ev1 = reinterpret_cast<const B2U32 *>(dst + (e_so1 + eo1))->v;
-#endif
-            if (tri) w3 = reinterpret_cast<const B2U32 *>(dst + srcom)->v;
-            if (wide) {
-                vv = *reinterpret_cast<const B2U128 *>(dst + srcom);
-                tw = reinterpret_cast<const B2U32 *>(dst + (srcom + olm - 4u))->v;
-            }
-            __builtin_amdgcn_s_waitcnt(0x0f70);                     // vmcnt(0), nothing else
-#if B2_W2_EARLY
-            if (ea0) reinterpret_cast<B2U32 *>(dst + (e_p0 + eo0))->v = ev0;
-            if (ea1) reinterpret_cast<B2U32 *>(dst + (e_p1 + eo1))->v = ev1;
-#endif
-            if (tri) {
-                reinterpret_cast<B2U16 *>(dst + posm)->v = (unsigned short)w3;
-                dst[posm + 2] = (unsigned char)(w3 >> 16);
-            }
-            if (wide) {
-                const bool g8 = olm >= 8, g12 = olm >= 12, g16 = olm >= 16;
-                reinterpret_cast<B2U32 *>(dst + posm)->v = vv.w[0];
-                reinterpret_cast<B2U32 *>(dst + (posm + (g8 ? 4u : 0u)))->v = g8 ? vv.w[1] : vv.w[0];
-                reinterpret_cast<B2U32 *>(dst + (posm + (g12 ? 8u : 0u)))->v = g12 ? vv.w[2] : vv.w[0];
-                reinterpret_cast<B2U32 *>(dst + (posm + (g16 ? 12u : 0u)))->v = g16 ? vv.w[3] : vv.w[0];
-                reinterpret_cast<B2U32 *>(dst + (posm + olm - 4u))->v = tw;
-            }
-            // the others in stream order (they may read each other's output, and the second set's may read the first set's)
-#define B2_REPLAY(copy_, par_, ol_, x_, pos_, srco_, done_)                                                            \
-            do {                                                                                                       \
-                u64 mm = __ballot(copy_ && !par_) & ~(done_);                                                          \
-                while (mm) {                                                                                           \
-                    const unsigned l = (unsigned)__builtin_ctzll(mm);                                                  \
-                    mm &= ~(1ull << l);                                                                                \
-                    const unsigned len = b2_rl(ol_, l), dd = b2_rl(x_, l) + 1u, p = b2_rl(pos_, l), so = b2_rl(srco_, l); \
-                    if (dd >= len) {                                                                                   \
-                        for (unsigned i = (unsigned)lane; i < len; i += 64) dst[p + i] = dst[so + i];                  \
-                    } else {                                                                                           \
-                        unsigned j = (unsigned)lane % dd;                                                              \
-                        const unsigned step = 64u % dd;                                                                \
-                        for (unsigned i = (unsigned)lane; i < len; i += 64) {                                          \
-                            dst[p + i] = dst[so + j];                                                                  \
-                            j += step;                                                                                 \
-                            j -= j >= dd ? dd : 0u;                                                                    \
-                        }                                                                                              \
-                    }                                                                                                  \
-                }                                                                                                      \
-            } while (0)
-#if B2_W2_EARLY
-            B2_REPLAY(copy0, par0, ol0, x0, pos0, srco0, e_bit0);
-            B2_REPLAY(copy1, par1, ol1, x1, pos1, srco1, e_bit1);
-#else
-            B2_REPLAY(copy0, par0, ol0, x0, pos0, srco0, 0ull);
-            B2_REPLAY(copy1, par1, ol1, x1, pos1, srco1, 0ull);
-#endif
-#undef B2_REPLAY
-            op += tot;
-            bp += adv;
-            if (bp > end_bit) {                                     // a valid block ends (EOB included) inside the payload
-                err = B2_E_INPUT;
-                break;
-            }
-            B2_ENSURE();
-            if (err != B2_OK || stop == 2) break;
-        }
-#else
         for (;;) {
             // every lane: the symbol that would start at bit bp + lane
             // (three dwords from the ring; every field but the distance's extra bits lies in the first 32 stream bits:
             //  9-bit code + 5 extra + 8-bit code = 22, so 64-bit shifts are not needed)
-            B2_MARK(7);                                               // (whatever came before this window: tables, headers, the previous window's tail)
             const unsigned q = bp + (unsigned)lane, qd = (q >> 5) & 127, qs = q & 31;
             const unsigned wa = win[qd], wb = win[qd + 1], wc = win[qd + 2];      // one address, three reads (the ring's mirror: no wrap)
             const unsigned lo = __builtin_amdgcn_alignbit(wb, wa, qs), hi = __builtin_amdgcn_alignbit(wc, wb, qs);
@@ -828,19 +449,13 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
             // next[i] = i + bits consumed; a chain ends at a value >= 64: [128, 256) = a code the tables do not resolve (the literal /
             // length code itself or the distance code behind it), >= 256 = end of block (256 + the bit after it)
             const unsigned nxt = (unsigned)lane + step1 + (is_len ? B2_STEP(e2) : 0u);
-#if B2_HOP2
             // TWO symbols per hop of the chain walk: every lane also learns where the symbol BEHIND its own would end (one LDS permute:
             // lane i reads next[next[i]]), and the walk reads both with one v_readlane — the scalar / vector hand-over, half of a hop's
             // ≈ 185 cycles, is paid once per two symbols.  m1 = the lane one symbol ahead, 64 when that hop leaves the window;
             // n2 = where the walk stands after two symbols (the exit value of whichever hop leaves the window first).
-            const unsigned m1 = nxt < (unsigned)B2_WBITS ? nxt : 64u;
+            const unsigned m1 = nxt < 64u ? nxt : 64u;
             const unsigned n2r = (unsigned)__builtin_amdgcn_ds_bpermute((int)(m1 << 2), (int)nxt);   // (m1 = 64 reads lane 0: not used)
-            const unsigned pack2 = m1 | ((nxt < (unsigned)B2_WBITS ? n2r : nxt) << 8);
-#endif
-#ifdef B2_PROF
-            asm volatile("" :: "v"(nxt));
-            B2_MARK(0);
-#endif
+            const unsigned pack2 = m1 | ((nxt < 64u ? n2r : nxt) << 8);
             // what a symbol starting at this lane's bit would write — 1 byte (literal), its length (match), nothing (end of block) — and,
             // for a match, from how far back
             const unsigned l1 = e1 & 15, eb1 = (e1 >> 4) & 15;
@@ -849,10 +464,6 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
             unsigned olraw = is_len ? mlen : ((e1 & B2_F_EOB) ? 0u : 1u);
             const unsigned l2 = e2 & 15, eb2 = (e2 >> 4) & 15, base2 = (e2 >> 8) & 0x7fff;
             unsigned dist = base2 + __builtin_amdgcn_ubfe(__builtin_amdgcn_alignbit(hi, lo, (step1 + l2) & 31), 0u, eb2);
-#ifdef B2_PROF
-            asm volatile("" :: "v"(dist), "v"(olraw));
-            B2_MARK(1);
-#endif
             // The true chain of symbol starts (scalar: one readlane per symbol).  A code longer than the LUTs (one symbol in ten on
             // BAM-shaped data) does not end the window: it is resolved right here by the scalar canonical walk, its lane is patched with
             // what the symbol writes, and the chain goes on behind it — the symbol's bytes leave with the window's other output instead of
@@ -861,21 +472,12 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
             u64 chain = 0;
             unsigned stop = 0;                                      // 2 = end of block
             for (;;) {
-                while (cur < (unsigned)B2_WBITS) {
-#if B2_HOP2
+                while (cur < 64u) {
                     const unsigned p2 = b2_rl(pack2, cur);
                     asm("s_bitset1_b64 %0, %1" : "+s"(chain) : "s"(cur));
                     asm("s_bitset1_b64 %0, %1" : "+s"(chain) : "s"(p2));       // bits 5:0 = m1 & 63: the next symbol's lane, or lane 0 — always on the
                     cur = p2 >> 8;                                             // chain — when that hop leaves the window
-#else
-                    asm("s_bitset1_b64 %0, %1" : "+s"(chain) : "s"(cur));      // chain |= 1 << cur in ONE scalar instruction (the scalar unit is shared by the CU's 32 waves)
-                    cur = b2_rl(nxt, cur);
-#endif
                 }
-#ifdef B2_PROF
-                B2_MARK(9);                                         // (the hops alone; what is left under mark 2 is the long-code path)
-                if (cur >= 128 && cur < 256) pf[10]++;
-#endif
                 // (the common exit first — the walk left the window, 64 <= cur < 128: one compare and one branch on the path every window takes;
                 //  tested behind the end-of-block case it cost 1.5 % of the launch, profiles/r06_ab_inflate_w2.txt (10))
                 if (__builtin_expect(cur < 128, 1)) break;
@@ -925,7 +527,6 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
                 if (stop == 2) break;
             }
             if (err != B2_OK) break;
-            B2_MARK(2);
             const unsigned ol = b2_sel(chain, olraw, 0u);           // off the chain: nothing
             const unsigned incl = b2_scan(ol);
             const unsigned tot = b2_rl(incl, 63);
@@ -935,89 +536,12 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
                 err = op + tot > isize ? B2_E_OVERRUN : B2_E_DIST;
                 break;
             }
-            B2_MARK(3);
-#if !defined(B2_EXP_NOLIT) && !(B2_PHASED && !B2_PIPE)   // B2_EXP_*: ablation switches (tools/build_variant.sh) behind the stage costs quoted in DESIGN.md 3.6
             if (ol == 1) dst[pos] = (unsigned char)litv;
-#endif
             const unsigned srco = pos - dist;                       // first source byte of this lane's match
             // Matches whose source lies wholly before this window's output cannot depend on anything decoded in it: each of
             // those is copied by its own lane, all at once (3 bytes unconditionally — the minimum match — then the rest).
-#ifdef B2_EXP_NOOWN    // ablation (output wrong): what the own-lane copies cost
-            const bool par = false;
-#else
             const bool par = copy && srco + mlen <= op && mlen <= B2_PARMAX;
-#endif
             const bool wide = par && mlen >= 4 && srco + 16 <= isize;   // the 16-byte read stays inside this block's output
-#if B2_PIPE
-            // (measurement variant) The copies are PIPELINED over two windows: this window was decoded while the previous window's loads
-            // were in flight; now the previous window's bytes are stored (B2_FLUSH waits for them here, one decode later than it used to), and
-            // only then are this window's loads issued — a source may lie in what the flush has just written, and the memory operations
-            // of one wave stay in order.
-            B2_FLUSH();
-            pd_kind = wide ? 1u : par ? 2u : copy ? 3u : 0u;
-            pd_pos = pos;
-            pd_mlen = mlen;
-            pd_dist = dist;
-            if (wide) {
-                const unsigned char *const s_ = dst + srco;
-                pd_v = *reinterpret_cast<const B2U128 *>(s_);
-                pd_tail = reinterpret_cast<const B2U32 *>(s_ + mlen - 4)->v;
-            }
-#else
-#if B2_PHASED
-            // Every copy whose source lies before this window's output is independent of the window's other copies, so ALL their loads are
-            // issued first and all their stores afterwards: the byte path (3-byte matches, block ends), the wide path, and the window's
-            // first match that is too long for its own lane but reads only earlier windows' output (three replayed matches in four) — ONE
-            // memory round trip where the three paths took one each, one after the other.  (The order matters for a second reason: a
-            // wave's memory operations return in order, so a wait for a load that has younger STORES behind it in the queue — the
-            // compiler cannot count them across exec regions and waits for everything — waits for their acknowledgements too, which is
-            // what made "loads early, stores late" for one path alone slower, twice.)
-            const bool bytep = par && !wide;
-            unsigned char by0 = 0, by1 = 0, by2 = 0;
-            B2U128 v = {{0, 0, 0, 0}};
-            unsigned tailw = 0;
-            unsigned e_len = 0, e_p = 0, e_lane = 0;
-            unsigned char e_v = 0;
-            if (bytep) {
-                by0 = dst[srco];
-                by1 = dst[srco + 1];
-                by2 = dst[srco + 2];
-            }
-            if (wide) {
-                v = *reinterpret_cast<const B2U128 *>(dst + srco);
-                tailw = reinterpret_cast<const B2U32 *>(dst + (srco + mlen - 4u))->v;
-            }
-            {
-                const u64 mi = B2_EARLYM ? __ballot(copy && !par && srco + mlen <= op && mlen <= 64u) : 0ull;
-                if (mi) {
-                    e_lane = (unsigned)__builtin_ctzll(mi);
-                    e_len = b2_rl(mlen, e_lane);
-                    e_p = b2_rl(pos, e_lane);
-                    const unsigned so = b2_rl(srco, e_lane);
-                    if ((unsigned)lane < e_len) e_v = dst[so + (unsigned)lane];
-                }
-            }
-            // every load of the phase is back before the first store goes out (the builtin, not inline asm: the compiler's own wait-count
-            // pass sees it and places no further waits between the stores — placed by itself, each path's wait for ITS loads counts the
-            // stores of the path in front of it as well)
-            __builtin_amdgcn_s_waitcnt(0x0f70);                     // vmcnt(0), nothing else; unconditional, or the pass cannot rely on it
-            if (ol == 1) dst[pos] = (unsigned char)litv;            // (the literals too go out behind the wait, not in front of the loads)
-            if (e_len && (unsigned)lane < e_len) dst[e_p + (unsigned)lane] = e_v;
-            if (bytep) {
-                dst[pos] = by0;
-                dst[pos + 1] = by1;
-                dst[pos + 2] = by2;
-                for (unsigned k = 3; k < mlen; k++) dst[pos + k] = dst[srco + k];
-            }
-            if (wide) {
-                const bool g8 = mlen >= 8, g12 = mlen >= 12, g16 = mlen >= 16;
-                reinterpret_cast<B2U32 *>(dst + pos)->v = v.w[0];
-                reinterpret_cast<B2U32 *>(dst + (pos + (g8 ? 4u : 0u)))->v = g8 ? v.w[1] : v.w[0];
-                reinterpret_cast<B2U32 *>(dst + (pos + (g12 ? 8u : 0u)))->v = g12 ? v.w[2] : v.w[0];
-                reinterpret_cast<B2U32 *>(dst + (pos + (g16 ? 12u : 0u)))->v = g16 ? v.w[3] : v.w[0];
-                reinterpret_cast<B2U32 *>(dst + (pos + mlen - 4u))->v = tailw;
-            }
-#else
             // (a 3-byte match, or a source in the block's last bytes.  Its source lies before this window's output, so the three bytes every
             //  match has are LOADED FIRST and stored together: one memory round trip; written as a plain byte loop the compiler, which
             //  cannot see that, waited for every byte before storing it — three round trips for the commonest match of zlib level 1)
@@ -1044,41 +568,7 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
                 reinterpret_cast<B2U32 *>(dst + (pos + (g16 ? 12u : 0u)))->v = g16 ? v.w[3] : v.w[0];
                 reinterpret_cast<B2U32 *>(dst + (pos + mlen - 4u))->v = tailw;
             }
-#endif
-#endif
-#ifdef B2_STATS
-            {
-                const u64 m_lit = __ballot(ol == 1), m_par = __ballot(par), m_long = __ballot(copy && !par && srco + mlen <= op), m_dep = __ballot(copy && !par && srco + mlen > op);
-                unsigned mb = copy ? mlen : 0u, rb = (copy && !par) ? mlen : 0u;
-                for (int d_ = 32; d_ > 0; d_ >>= 1) {
-                    mb += __shfl_xor(mb, d_);
-                    rb += __shfl_xor(rb, d_);
-                }
-                if (lane == 0) {
-                    atomicAdd(&b2_stats[0], 1ull);
-                    atomicAdd(&b2_stats[1], (unsigned long long)__popcll(chain));
-                    atomicAdd(&b2_stats[2], (unsigned long long)__popcll(m_lit));
-                    atomicAdd(&b2_stats[3], (unsigned long long)__popcll(m_par));
-                    atomicAdd(&b2_stats[4], (unsigned long long)__popcll(m_long));
-                    atomicAdd(&b2_stats[5], (unsigned long long)__popcll(m_dep));
-                    atomicAdd(&b2_stats[6], 0ull);
-                    atomicAdd(&b2_stats[7], (unsigned long long)mb);
-                    atomicAdd(&b2_stats[8], (unsigned long long)rb);
-                }
-            }
-#endif
-#ifdef B2_PROF
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (the copies' stores are issued: charge their completion to the copies)
-            B2_MARK(4);
-#endif
-#if !B2_PIPE
             u64 mm = __ballot(copy && !par);
-#ifdef B2_EXP_NOREPLAY  // ablation (output wrong): what the replayed matches cost
-            mm = 0;
-#endif
-#if B2_PHASED
-            if (e_len) mm &= ~(1ull << e_lane);
-#endif
             while (mm) {                                            // the others in stream order (they may read each other's output)
                 const unsigned l = (unsigned)__builtin_ctzll(mm);
                 mm &= ~(1ull << l);
@@ -1095,13 +585,7 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
                     }
                 }
             }
-#endif
             if (err != B2_OK) break;
-#ifdef B2_PROF
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            B2_MARK(5);
-            pf[8]++;
-#endif
             op += tot;
             bp += cur;
             if (bp > end_bit) {                                     // a valid block ends (EOB included) inside the payload
@@ -1109,39 +593,22 @@ __global__ __launch_bounds__(64 * B2_WAVES) __attribute__((amdgpu_waves_per_eu(B
                 break;
             }
             B2_ENSURE();
-            B2_MARK(6);
             if (err != B2_OK || stop == 2) break;
         }
-#endif
-#if B2_PIPE
-        if (err == B2_OK) B2_FLUSH();                              // the last window's copies, before the next DEFLATE block writes behind them
-#endif
     }
     if (err == B2_OK && op != isize) err = B2_E_SIZE;
     if (err == B2_OK && bp > end_bit + 7) err = B2_E_INPUT;
     if (lane == 0) status[b] = err;
-#ifdef B2_PROF
-    B2_MARK(7);
-    if (lane == 0)
-        for (int k_ = 0; k_ < 12; k_++) atomicAdd(&b2_prof[k_], (unsigned long long)pf[k_]);
-#endif
     __builtin_amdgcn_wave_barrier();                          // (the next block's staging writes the ring this one may still be reading)
     }
 #undef B2_ENSURE
 #undef B2_STAGE
-#if B2_PIPE
-#undef B2_FLUSH
-#endif
 }
 
 void tdt_bz_launch_lanes(hipStream_t st, int num_cu, int reserve, const unsigned char *d_comp, const BzDesc *d_blocks, size_t nblocks,
                          unsigned char *d_out, unsigned *d_status, unsigned *d_next_block) {
-#ifdef B2_NOPERSIST
-    const size_t resident = ~(size_t)0;
-#else
     const int per_cu = 4 * B2_OCC / B2_WAVES;                                          // workgroups a CU holds at 8 waves per SIMD
     const size_t resident = (size_t)num_cu * (size_t)(reserve > 0 && reserve < per_cu ? per_cu - reserve : per_cu);
-#endif
     const unsigned grid = (unsigned)std::min(resident, (nblocks + B2_WAVES - 1) / B2_WAVES);
     hipLaunchKernelGGL(bgzf_inflate_lanes, dim3(grid), dim3(64 * B2_WAVES), 0, st, d_comp, d_blocks, (int)nblocks, d_out, d_status, d_next_block);
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Ceilings of the binned 500-bp coverage launch: the in-tree library and measurement variants (variants/lib_<name>.so built by
-tools/build_variant.sh with -DCOV_EXP_*), each in its own process, same box.  usage: python tools/ab_cov_variants.py name ..."""
+"""The binned 500-bp coverage launch: the in-tree library and variant builds (variants/lib_<name>.so built by tools/build_variant.sh
+with tunables such as -DCOV_RPL=4), each in its own process, same box.  usage: python tools/ab_cov_variants.py name ..."""
 import os, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 code = r'''
