@@ -452,6 +452,14 @@ int tdt_ingest_packed(tdt_ingest *g, const uint64_t **d_packed);
 /* From the next push on the reader writes BINNED records for `cov` (NULL: the generic packed records again) into the column
  * tdt_ingest_packed returns; *binned = 1 when it does (0: that histogram's bin size has no binned form, the column stays generic). */
 int tdt_ingest_bin_for(tdt_ingest *g, tdt_cov *cov, int *binned);
+/* A SECOND histogram for the same pass (`tiddit --sv` writing the --cov track from its scan): from the next push on the field-decode
+ * kernel writes one more 8-byte coverage record per read, for `cov`, from the fields it already holds — BINNED records when `cov`'s bin
+ * size has a binned form (*binned = 1), the generic packed records otherwise (*binned = 0).  The column is independent of
+ * tdt_ingest_bin_for's.  cov == NULL detaches: the reader then launches the kernels it launched before and allocates nothing for the
+ * column.  tdt_ingest_packed_second: the column's device pointer (NULL: the batch was decoded with nothing attached); it lives and
+ * dies with the batch's other arrays (next push / tdt_ingest_retain + tdt_ingest_release). */
+int tdt_ingest_second_for(tdt_ingest *g, tdt_cov *cov, int *binned);
+int tdt_ingest_packed_second(tdt_ingest *g, const uint64_t **d_packed);
 /* Enqueue the FIRST HALF of a coming span's push — its copy (or the prefetched one), its block table, the inflate + CRC kernels and the
  * copy of their status word — on the reader's own (low-priority) inflate streams, without waiting for anything.  A span inflates into an
  * output buffer of its own, a fixed gap into it (1 MB; TIDDIT_INGEST_GAP), and the partial record the batch before it ends with is copied

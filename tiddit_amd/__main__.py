@@ -11,6 +11,10 @@ stage (tiddit_amd/tiddit_variant.py: typing, filters, genotypes, QUAL; regional 
 store) writes ``{o}.vcf`` with tiddit_amd/tiddit_vcf_header.py's header.  On N ranks every rank keeps the store of its
 own shard of the file, answers all of rank 0's queries over it, and the counts are summed on rank 0, which writes the
 same ``{o}.vcf``.  Local assembly stays out of scope.
+
+``TIDDIT_COV_TRACK=Z[:Q[:bed|wig]]``: ``--sv`` also writes ``{o}.bed`` (or ``{o}.wig``), byte for byte the file ``--cov -z Z -q Q [-w]``
+writes for the same BAM — from the scan's own pass over the file: the ingest kernel writes a second coverage record per read, a second
+histogram is filled beside the 50-bp one, and no second job reads and inflates the file again.  On N ranks rank 0 writes it.
 """
 import argparse
 import os
@@ -105,19 +109,34 @@ def run_cov(args):
                 if tid[lo] >= 0:
                     hist.push(int(tid[lo]), b.pos[lo:hi], b.end[lo:hi], b.mapq[lo:hi], b.flag[lo:hi], args.q)
         reader.close()
-        if len(coverage_data) > 64:          # a header of thousands of contigs: every contig's bins in one launch + copy (tdt_cov_finish_all)
-            allbins = hist.finish_all()
-            for i, contig in enumerate(coverage_data):
-                o = hist.offset(i)
-                coverage_data[contig] = allbins[o:o + hist.nbins(i)[0]].copy()
-        else:
-            for contig in coverage_data:
-                coverage_data[contig] = hist.finish(contig)
+        # (a header of thousands of contigs: every contig's bins in one launch + copy, tdt_cov_finish_all; contigs are found by name)
+        coverage_data.update(tiddit_coverage.bins_by_contig(hist, coverage_data))
         hist.close()
     if args.w:
         tiddit_coverage.print_coverage(coverage_data, bam_header, args.z, "wig", args.o + ".wig")
     else:
         tiddit_coverage.print_coverage(coverage_data, bam_header, args.z, "bed", args.o + ".bed")
+
+
+def parse_cov_track(value):
+    """``TIDDIT_COV_TRACK``: ``Z[:Q[:bed|wig]]`` -> (bin size, minimum mapping quality, file type), with the defaults of ``--cov``
+    (-q 20, bed); None when the switch is unset or empty.  Raises ValueError (its text is the error line) for anything else."""
+    if value is None or value == "":
+        return None
+    fields = value.split(":")
+    if len(fields) > 3:
+        raise ValueError("at most three fields, Z[:Q[:bed|wig]]")
+    import re
+    if not re.fullmatch(r"[0-9]+", fields[0]) or (len(fields) > 1 and not re.fullmatch(r"-?[0-9]+", fields[1])):
+        raise ValueError("the bin size and the mapping quality are integers")
+    z = int(fields[0])
+    q = int(fields[1]) if len(fields) > 1 else 20
+    if z < 1:
+        raise ValueError("the bin size must be at least 1")
+    fmt = fields[2] if len(fields) > 2 else "bed"
+    if fmt not in ("bed", "wig"):
+        raise ValueError("the file type is bed or wig")
+    return z, q, fmt
 
 
 STAGE_SECONDS = {}          # wall seconds of the last run_sv, stage by stage (bench.py reads it)
@@ -165,6 +184,11 @@ def run_sv(args, version):
     from .fasta import FastaFile
     if args.l < 2:
         print("error, too low --l value!")
+        quit()
+    try:
+        track = parse_cov_track(os.environ.get("TIDDIT_COV_TRACK"))
+    except ValueError as e:
+        print("error, TIDDIT_COV_TRACK={}: {}".format(os.environ.get("TIDDIT_COV_TRACK"), e))
         quit()
     if not args.skip_assembly:
         print("error, local assembly is outside this build's scope; rerun with --skip_assembly")
@@ -273,7 +297,8 @@ def run_sv(args, version):
     with stage("tiddit: library statistics"):
         if not multi:
             try:
-                library = tiddit_stats.statistics(args.bam, args.ref, min_mapq, max_ins_len, args.s, carry=True)
+                library = tiddit_stats.statistics(args.bam, args.ref, min_mapq, max_ins_len, args.s, carry=True,
+                                                     **({} if track is None else {"track_bin_size": track[0]}))
             except BaseException:
                 if gc_job is not None and "thread" in gc_job:
                     gc_job["thread"].join()                  # (no helper thread outlives the error)
@@ -289,7 +314,8 @@ def run_sv(args, version):
             wire = torch.zeros(8192, dtype=torch.uint8, device=tdist._wire_device())
             overlap = os.environ.get("TIDDIT_DIST_PREINGEST", "1") != "0" and os.environ.get("TIDDIT_HOST_INGEST") != "1"
             if rank == 0:
-                library = tiddit_stats.statistics(args.bam, args.ref, min_mapq, max_ins_len, args.s, carry=overlap, shard=(0, world) if overlap else None)
+                library = tiddit_stats.statistics(args.bam, args.ref, min_mapq, max_ins_len, args.s, carry=overlap, shard=(0, world) if overlap else None,
+                                                     **({} if track is None else {"track_bin_size": track[0]}))
                 blob = pickle.dumps(library, protocol=4)
                 host = numpy.zeros(8192, dtype=numpy.uint8)
                 big = len(blob) > host.size - 4               # (never seen: a dozen numbers) -> marker here, the object by itself below
@@ -305,7 +331,8 @@ def run_sv(args, version):
                 held = 0
                 if overlap:
                     held = bamio.preingest(args.bam, (rank, world), 50, stop=work.is_completed,
-                                           chunk=int(os.environ.get("TIDDIT_INGEST_CHUNK", str(448 << 20))))
+                                           chunk=int(os.environ.get("TIDDIT_INGEST_CHUNK", str(448 << 20))),
+                                           **({} if track is None else {"track_bin_size": track[0]}))
                 work.wait()
                 host = wire.cpu().numpy()
                 size = int(host[:4].view("<u4")[0])
@@ -323,6 +350,9 @@ def run_sv(args, version):
     # TIDDIT_VARIANTS=1: the scan also packs every placed record into the evidence store the native variant stage reads (on N ranks:
     # every rank the records of its own shard)
     tiddit_signal.KEEP_EVIDENCE = os.environ.get("TIDDIT_VARIANTS") == "1"
+    if track is not None:
+        # TIDDIT_COV_TRACK: the scan fills a second histogram — every contig, the track's bin size and mapq cut — from the same batches
+        tiddit_signal.COV_TRACK = (track[0], track[1])
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -333,6 +363,8 @@ def run_sv(args, version):
                 tiddit_signal.AFTER_SCAN.remove(start_gc)
             tiddit_signal.BACKGROUND_WRITES = False
             tiddit_signal.KEEP_EVIDENCE = False
+            if track is not None:
+                tiddit_signal.COV_TRACK = None
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:
@@ -340,6 +372,15 @@ def run_sv(args, version):
         print(t - time.time())
     T["signal extraction + coverage"] = time.time() - t
     T.update({"  " + k: v for k, v in tiddit_signal.STAGE_SECONDS.items()})
+    if track is not None:
+        bins, tiddit_signal.COV_TRACK_BINS = tiddit_signal.COV_TRACK_BINS, None
+        if rank == 0:
+            # what run_cov writes for `--cov -z Z -q Q [-w] -o {o}`, through the same function
+            from . import tiddit_coverage
+            t = time.time()
+            tiddit_coverage.print_coverage(bins, bam_header, track[0], track[2], "{}.{}".format(prefix, track[2]))
+            T["coverage track ({o}.bed / {o}.wig, from the scan's second histogram)"] = time.time() - t
+        del bins
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False)

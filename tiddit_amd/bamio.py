@@ -370,6 +370,9 @@ class DeviceBatch:
     def __init__(self, reader, n, ptrs, raw_len, runs):
         self._reader, self._n, self._raw_len, self.runs = reader, n, raw_len, runs
         self.binned_for = None          # the CoverageHistogram whose bin size the "packed" column was written for (None: generic packed records)
+        # the SECOND coverage-record column (dev["packed2"], DeviceBamReader.second_for): the histogram it was written for, and whether its
+        # records are binned records for that histogram's bin size or the generic packed ones (which serve any histogram)
+        self.second_for, self.second_binned = None, False
         self.dev = {k: int(ptrs[i] or 0) for i, (k, _) in enumerate(_FIELDS)}
         self.dev["raw"] = int(ptrs[13] or 0)
         self._host = {}
@@ -386,7 +389,7 @@ class DeviceBatch:
                 raise RuntimeError("DeviceBatch used after the reader moved on to the next batch")
             if name == "raw":
                 a = np.empty(self._raw_len, dtype=np.uint8)
-            elif name == "packed":
+            elif name in ("packed", "packed2"):
                 a = np.empty(self._n, dtype=np.uint64)
             else:
                 a = np.empty(self._n, dtype=dict(_FIELDS)[name])
@@ -409,12 +412,14 @@ class DeviceBatch:
 
 class ScanCarry:
     """What `tiddit --sv`'s library-statistics pass hands to the signal pass of the same file: the reader (positioned behind the
-    sampled batches), its batch iterator, the retained batches and the 50-bp histogram their coverage records were written for."""
+    sampled batches), its batch iterator, the retained batches and the 50-bp histogram their coverage records were written for.
+    hist2: the second histogram (the coverage track, ``tiddit_signal.COV_TRACK``) whose records the batches carry in their second
+    column, or None."""
 
-    def __init__(self, path, reader, iterator, batches, hist):
+    def __init__(self, path, reader, iterator, batches, hist, hist2=None):
         import os
         self.path, self.stamp = os.path.abspath(path), os.stat(path).st_mtime_ns
-        self.reader, self.iterator, self.batches, self.hist = reader, iterator, batches, hist
+        self.reader, self.iterator, self.batches, self.hist, self.hist2 = reader, iterator, batches, hist, hist2
         self.shard = getattr(reader, "shard", None)          # (rank, world) when the reader covers one rank's byte range of the file
 
     def drop(self):
@@ -428,6 +433,8 @@ class ScanCarry:
         self.reader.close()
         if self.hist is not None:
             self.hist.close()
+        if self.hist2 is not None:
+            self.hist2.close()
 
 
 _CARRY = None
@@ -458,16 +465,21 @@ def take_carry(path, bin_size, shard=None):
     return c
 
 
-def preingest(path, shard, bin_size, stop, max_batches=12, chunk=448 << 20, ctx=None):
+def preingest(path, shard, bin_size, stop, max_batches=12, chunk=448 << 20, ctx=None, track_bin_size=None):
     """Start on this rank's share of the file before the scan's parameters are known: the N-rank `tiddit --sv` needs the library
     statistics (rank 0 samples them from the head of the file) before any signal predicate can run, but inflate, record decode and the
     coverage records depend on nothing — so the other ranks ingest their first batches meanwhile and keep them in HBM (retained, like
     the statistics pass's own).  Reads batches until ``stop()`` is true, the share is exhausted or `max_batches` are held (a batch
-    holds ~1.8 GB of device memory at the default span); leaves a :class:`ScanCarry` for :func:`take_carry`.  -> batches held."""
+    holds ~1.8 GB of device memory at the default span); leaves a :class:`ScanCarry` for :func:`take_carry`.  track_bin_size: the batches
+    also carry the second coverage-record column, written for a histogram of that bin size (the coverage track).  -> batches held."""
     from . import tiddit_coverage
     reader = DeviceBamReader(path, ctx=ctx, chunk=chunk, shard=shard)
     hist = tiddit_coverage.CoverageHistogram([(n, l) for n, l in zip(reader.references, reader.lengths)], bin_size, ctx=reader.ctx)
     reader.bin_for(hist)
+    hist2 = None
+    if track_bin_size is not None:
+        hist2 = tiddit_coverage.CoverageHistogram([(n, l) for n, l in zip(reader.references, reader.lengths)], track_bin_size, ctx=reader.ctx)
+        reader.second_for(hist2)
     reader.retain = True
     it = reader.batches()
     kept = []
@@ -483,9 +495,11 @@ def preingest(path, shard, bin_size, stop, max_batches=12, chunk=448 << 20, ctx=
         it.close()
         reader.close()
         hist.close()
+        if hist2 is not None:
+            hist2.close()
         raise
     reader.retain = False
-    set_carry(ScanCarry(path, reader, it, kept, hist))
+    set_carry(ScanCarry(path, reader, it, kept, hist, hist2))
     return len(kept)
 
 
@@ -550,6 +564,16 @@ class DeviceBamReader:
         on = ctypes.c_int(0)
         _native.check(self.ctx.lib.tdt_ingest_bin_for(self._h, hist.handle if hist is not None else None, ctypes.byref(on)))
         self._binned_for = hist if on.value else None
+        return bool(on.value)
+
+    def second_for(self, hist):
+        """From the next batch on, the ingest kernel writes a SECOND 8-byte coverage record per read, for `hist` (``dev["packed2"]`` of
+        every batch; CoverageHistogram.push_device_batch(..., column="packed2") reads it): binned records when `hist`'s bin size has a
+        binned form, the generic packed records otherwise.  None detaches: no column, no allocation, the kernels of a plain reader.
+        -> whether the column holds binned records."""
+        on = ctypes.c_int(0)
+        _native.check(self.ctx.lib.tdt_ingest_second_for(self._h, hist.handle if hist is not None else None, ctypes.byref(on)))
+        self._second_for, self._second_binned = hist, bool(on.value)
         return bool(on.value)
 
     def _spans(self):
@@ -882,6 +906,11 @@ class DeviceBamReader:
             _native.check(lib.tdt_ingest_packed(self._h, ctypes.byref(pk)))
             b.dev["packed"] = int(pk.value or 0)         # 8-byte coverage records (csrc/tdt_common.h: cov_pack_record / cov_bin_record)
             b.binned_for = getattr(self, "_binned_for", None)
+            if getattr(self, "_second_for", None) is not None:
+                pk2 = ctypes.c_void_p()
+                _native.check(lib.tdt_ingest_packed_second(self._h, ctypes.byref(pk2)))
+                b.dev["packed2"] = int(pk2.value or 0)
+                b.second_for, b.second_binned = self._second_for, self._second_binned
             if ne.value == ctypes.c_size_t(-1).value:                   # not coordinate sorted: runs from the tid column
                 tid = b.tid
                 lo = np.concatenate([[0], np.flatnonzero(np.diff(tid)) + 1])

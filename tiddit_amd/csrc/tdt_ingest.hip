@@ -197,6 +197,13 @@ struct IngestOut {
                                      // (tdt_ingest_bin_for), cov_bin_record for its bin size: what the coverage kernels read
     CovBinSpec bin;                  // bin.z != 0: binned records
 };
+// A SECOND coverage-record column for a second histogram (tdt_ingest_second_for): `tiddit --sv` writes the --cov track from the scan's own
+// pass.  It travels as a kernel argument of its own, and only to the kernel flavours that write it: the flavours of a reader
+// without a second histogram take the arguments — and compile to the code — they had before the column existed.
+struct IngestSecond {
+    unsigned long long *packed = nullptr;   // cov_bin_record for bin (bin.z != 0), else cov_pack_record
+    CovBinSpec bin;
+};
 
 __device__ __forceinline__ long long aux_value_size(unsigned char t, const unsigned char *p, const unsigned char *end) {
     switch (t) {
@@ -220,7 +227,10 @@ __device__ __forceinline__ long long aux_value_size(unsigned char t, const unsig
 }
 
 // one record at byte p of the batch -> element i of the field arrays; returns its block_size
-__device__ __forceinline__ unsigned bam_decode_one(const unsigned char *__restrict__ buf, long long p, size_t i, const IngestOut &O) {
+// SECOND: the record's second coverage record goes to S2.packed[i], from the same registers (the inflated bytes are read once)
+template <bool SECOND>
+__device__ __forceinline__ unsigned bam_decode_one(const unsigned char *__restrict__ buf, long long p, size_t i, const IngestOut &O,
+                                                   const IngestSecond &S2) {
     const unsigned bs = ld_u32(buf + p);
     const unsigned char *r = buf + p + 4;
     const int pos = (int)ld_u32(r + 4), lseq = (int)ld_u32(r + 16);
@@ -243,6 +253,14 @@ __device__ __forceinline__ unsigned bam_decode_one(const unsigned char *__restri
         O.packed[i] = cov_bin_record(pos, (int)(pos + rlen), r[9], fl, nb_, O.bin.z, O.bin.magic, O.bin.shift, O.bin.mode1 != 0);
     } else {
         O.packed[i] = cov_pack_record(pos, (int)(pos + rlen), r[9], fl);
+    }
+    if (SECOND) {                                                                   // (one more coalesced 8-byte store per lane)
+        if (S2.bin.z) {
+            const int nb2 = (tid_ >= 0 && tid_ < S2.bin.n_contigs) ? S2.bin.d_nbins[tid_] : 0;
+            S2.packed[i] = cov_bin_record(pos, (int)(pos + rlen), r[9], fl, nb2, S2.bin.z, S2.bin.magic, S2.bin.shift, S2.bin.mode1 != 0);
+        } else {
+            S2.packed[i] = cov_pack_record(pos, (int)(pos + rlen), r[9], fl);
+        }
     }
     O.mate_tid[i] = (int)ld_u32(r + 20);
     O.mate_pos[i] = (int)ld_u32(r + 24);
@@ -271,29 +289,52 @@ __device__ __forceinline__ unsigned bam_decode_one(const unsigned char *__restri
 // records of a segment are decoded side by side and their fields leave in coalesced stores.  (One lane per segment walking its ~55
 // records — rounds 2-4 — was 1 250 waves of 64 dependent chains for a 1.3-GB batch: a sixth of the chip's wave slots, every load a
 // round trip nobody hid.)
-__global__ __launch_bounds__(256) void bam_decode_fields(const unsigned char *__restrict__ buf, long long T, int nseg,
-                                                         const unsigned *__restrict__ base, const unsigned *__restrict__ count,
-                                                         const unsigned short *__restrict__ rel, IngestOut O) {
+template <bool SECOND>
+__device__ __forceinline__ void decode_fields_wave(const unsigned char *__restrict__ buf, int nseg, const unsigned *__restrict__ base,
+                                                   const unsigned *__restrict__ count, const unsigned short *__restrict__ rel, const IngestOut &O,
+                                                   const IngestSecond &S2) {
     const int g = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
     if (g >= nseg) return;
     const unsigned n = count[g], b = base[g];
     if (b == ING_NONE || n == 0) return;
     const long long lo = (long long)g * ING_SEG;
     const unsigned short *const row = rel + (size_t)g * ING_MAXREC;
-    for (unsigned k = (unsigned)lane; k < n; k += 64) (void)bam_decode_one(buf, lo + row[k], (size_t)b + k, O);
+    for (unsigned k = (unsigned)lane; k < n; k += 64) (void)bam_decode_one<SECOND>(buf, lo + row[k], (size_t)b + k, O, S2);
+}
+__global__ __launch_bounds__(256) void bam_decode_fields(const unsigned char *__restrict__ buf, long long T, int nseg,
+                                                         const unsigned *__restrict__ base, const unsigned *__restrict__ count,
+                                                         const unsigned short *__restrict__ rel, IngestOut O) {
+    decode_fields_wave<false>(buf, nseg, base, count, rel, O, IngestSecond());
+}
+// ... and the flavour of a reader with a second histogram attached: chosen at the launch, not by a branch per read
+__global__ __launch_bounds__(256) void bam_decode_fields_second(const unsigned char *__restrict__ buf, long long T, int nseg,
+                                                                const unsigned *__restrict__ base, const unsigned *__restrict__ count,
+                                                                const unsigned short *__restrict__ rel, IngestOut O, IngestSecond S2) {
+    decode_fields_wave<true>(buf, nseg, base, count, rel, O, S2);
 }
 
 // The same with a lane per segment walking its records: after a host chase (the segment table rebuilt on the host, no `rel` rows)
-__global__ __launch_bounds__(64) void bam_decode_fields_serial(const unsigned char *__restrict__ buf, long long T, int nseg,
-                                                               const unsigned *__restrict__ first, const unsigned *__restrict__ base,
-                                                               const unsigned *__restrict__ count, IngestOut O) {
+template <bool SECOND>
+__device__ __forceinline__ void decode_fields_lane(const unsigned char *__restrict__ buf, int nseg, const unsigned *__restrict__ first,
+                                                   const unsigned *__restrict__ base, const unsigned *__restrict__ count, const IngestOut &O,
+                                                   const IngestSecond &S2) {
     const int g = blockIdx.x * 64 + threadIdx.x;
     if (g >= nseg) return;
     const unsigned n = count[g];
     if (base[g] == ING_NONE || n == 0) return;
     long long p = first[g];
     size_t i = base[g];
-    for (unsigned k = 0; k < n; k++, i++) p += 4 + (long long)bam_decode_one(buf, p, i, O);
+    for (unsigned k = 0; k < n; k++, i++) p += 4 + (long long)bam_decode_one<SECOND>(buf, p, i, O, S2);
+}
+__global__ __launch_bounds__(64) void bam_decode_fields_serial(const unsigned char *__restrict__ buf, long long T, int nseg,
+                                                               const unsigned *__restrict__ first, const unsigned *__restrict__ base,
+                                                               const unsigned *__restrict__ count, IngestOut O) {
+    decode_fields_lane<false>(buf, nseg, first, base, count, O, IngestSecond());
+}
+__global__ __launch_bounds__(64) void bam_decode_fields_serial_second(const unsigned char *__restrict__ buf, long long T, int nseg,
+                                                                      const unsigned *__restrict__ first, const unsigned *__restrict__ base,
+                                                                      const unsigned *__restrict__ count, IngestOut O, IngestSecond S2) {
+    decode_fields_lane<true>(buf, nseg, first, base, count, O, S2);
 }
 
 // positions where tid changes (i = 0 included): the per-contig runs of a coordinate-sorted batch
@@ -367,6 +408,8 @@ struct tdt_ingest {
     size_t out_len = 0;                            // carry + inflated bytes of the current batch
     size_t n_records = 0, rec_cap = 0;
     IngestOut O{};
+    bool second = false;                           // a second histogram is attached (tdt_ingest_second_for): S2.packed is written beside O.packed
+    IngestSecond S2{};
     std::vector<unsigned> edges;
     std::vector<int32_t> edge_tids;              // the contig id of the run that starts at edges[k]
     bool edges_overflow = false;
@@ -1067,13 +1110,17 @@ static int ing_push(tdt_ingest *g, const uint8_t *comp, size_t len, size_t skip,
     if (n) {
         const size_t N = n;
         const size_t a4 = (N * 4 + 255) & ~(size_t)255, a2 = (N * 2 + 255) & ~(size_t)255, a1 = (N + 255) & ~(size_t)255, a8 = (N * 8 + 255) & ~(size_t)255;
-        rc = ing_grow(g, g->soa, 9 * a4 + a2 + a1 + 3 * a8 + 8 * (ING_EDGES + 1) + 256);
+        rc = ing_grow(g, g->soa, 9 * a4 + a2 + a1 + (g->second ? 4 : 3) * a8 + 8 * (ING_EDGES + 1) + 256);
         if (rc) return rc;
         char *p = (char *)g->soa.p;
         IngestOut &O = g->O;
         O.rec_off = (uint64_t *)p; p += a8;
         O.sa_off = (int64_t *)p; p += a8;
         O.packed = (unsigned long long *)p; p += a8;
+        g->S2.packed = nullptr;
+        if (g->second) {
+            g->S2.packed = (unsigned long long *)p; p += a8;
+        }
         O.tid = (int32_t *)p; p += a4;
         O.pos = (int32_t *)p; p += a4;
         O.end = (int32_t *)p; p += a4;
@@ -1093,8 +1140,13 @@ static int ing_push(tdt_ingest *g, const uint8_t *comp, size_t len, size_t skip,
         }
         g->t_chain_ms = ing_now_ms() - t_chain0;
         if (g->tev[2]) (void)hipEventRecord(g->tev[2], st);
-        if (table_dirty)
+        if (table_dirty && g->second)
+            hipLaunchKernelGGL(bam_decode_fields_serial_second, dim3((nseg + 63) / 64), dim3(64), 0, st, d_out, (long long)T, nseg, d_first, d_base, d_count,
+                               O, g->S2);
+        else if (table_dirty)
             hipLaunchKernelGGL(bam_decode_fields_serial, dim3((nseg + 63) / 64), dim3(64), 0, st, d_out, (long long)T, nseg, d_first, d_base, d_count, O);
+        else if (g->second)
+            hipLaunchKernelGGL(bam_decode_fields_second, dim3((nseg + 3) / 4), dim3(256), 0, st, d_out, (long long)T, nseg, d_base, d_count, d_rel, O, g->S2);
         else
             hipLaunchKernelGGL(bam_decode_fields, dim3((nseg + 3) / 4), dim3(256), 0, st, d_out, (long long)T, nseg, d_base, d_count, d_rel, O);
         TDT_CHECK_LAUNCH();
@@ -1173,6 +1225,26 @@ extern "C" int tdt_ingest_bin_for(tdt_ingest *g, tdt_cov *cov, int *binned) {
     return TDT_OK;
 }
 
+// From the next push on, the reader writes a SECOND 8-byte coverage record per read, for `cov`, beside the column of tdt_ingest_bin_for:
+// cov_bin_record records when `cov`'s bin size has a binned form (*binned = 1), the generic cov_pack_record otherwise (*binned = 0).
+// cov == NULL detaches: the reader launches the kernel flavours without the column again and allocates nothing for it.
+extern "C" int tdt_ingest_second_for(tdt_ingest *g, tdt_cov *cov, int *binned) {
+    if (!g) {
+        tdt_set_error("tdt_ingest_second_for: bad argument");
+        return TDT_E_ARG;
+    }
+    g->second = false;
+    g->S2.bin = CovBinSpec();
+    if (cov) {
+        int rc = tdt_cov_bin_spec(cov, &g->S2.bin);
+        if (rc) return rc;
+        if (g->S2.bin.n_contigs != g->n_ref) g->S2.bin = CovBinSpec();    // not this file's contig table
+        g->second = true;
+    }
+    if (binned) *binned = g->S2.bin.z != 0;
+    return TDT_OK;
+}
+
 // Keep the current batch: its inflated records and field arrays move into a handle and stay valid until tdt_ingest_release, while the
 // reader goes on with fresh buffers (the partial record behind the batch is carried over).  `tiddit --sv` samples its library statistics
 // from the first reads of the file and then scans the whole file for signals: the sampled batches are retained and scanned where they
@@ -1203,6 +1275,7 @@ extern "C" int tdt_ingest_retain(tdt_ingest *g, tdt_retained **handle) {
         IngestOut fresh_o{};
         fresh_o.bin = g->O.bin;
         g->O = fresh_o;
+        g->S2.packed = nullptr;                      // (the column lies in the array block that went with the batch)
     }
     g->n_records = 0;
     *handle = r;
@@ -1262,6 +1335,16 @@ extern "C" int tdt_ingest_packed(tdt_ingest *g, const uint64_t **d_packed) {
         return TDT_E_ARG;
     }
     *d_packed = g->n_records ? (const uint64_t *)g->O.packed : nullptr;
+    return TDT_OK;
+}
+
+// the second coverage-record column of the current batch (tdt_ingest_second_for); NULL when the batch was decoded without one
+extern "C" int tdt_ingest_packed_second(tdt_ingest *g, const uint64_t **d_packed) {
+    if (!g || !d_packed) {
+        tdt_set_error("tdt_ingest_packed_second: bad argument");
+        return TDT_E_ARG;
+    }
+    *d_packed = g->n_records ? (const uint64_t *)g->S2.packed : nullptr;
     return TDT_OK;
 }
 

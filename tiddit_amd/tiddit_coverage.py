@@ -157,14 +157,26 @@ class CoverageHistogram:
         _native.check(self.lib.tdt_cov_push_binned_device_multi(self.handle, k, _native.ptr(tids), _native.ptr(pk), _native.ptr(st), _native.ptr(en),
                                                                 _native.ptr(ns), int(min_q)))
 
-    def push_device_batch(self, batch, min_q, want=None):
+    def push_device_batch(self, batch, min_q, want=None, column="packed"):
         """every per-contig run of a DeviceBatch (bamio.DeviceBamReader) in ONE launch, through the 8-byte packed records the
-        ingest kernel wrote when min_q fits their 6-bit mapq field; want[tid] false skips a contig"""
+        ingest kernel wrote when min_q fits their 6-bit mapq field; want[tid] false skips a contig.  column="packed2": through the
+        batch's SECOND record column (DeviceBamReader.second_for) — its binned records when they were written for THIS histogram, its
+        generic packed records for any histogram; a batch without a usable second column goes through its four field arrays."""
         d = batch.dev
         runs = [(t, lo, hi) for t, lo, hi in batch.runs if t >= 0 and (want is None or want[t])]
         if not runs:
             return
-        if d.get("packed") and int(min_q) <= 63 and getattr(batch, "binned_for", None) is self:
+        if column == "packed2":
+            pk = d.get("packed2") if int(min_q) <= 63 and getattr(batch, "second_for", None) is not None else 0
+            if pk and batch.second_binned and batch.second_for is self:
+                self.push_binned_device_multi([(t, pk + 8 * lo, d["pos"] + 4 * lo, d["end"] + 4 * lo, hi - lo) for t, lo, hi in runs], min_q)
+            elif pk and not batch.second_binned:
+                self.push_packed_device_multi([(t, pk + 8 * lo, d["end"] + 4 * lo, hi - lo) for t, lo, hi in runs], min_q)
+            else:
+                self.push_device_multi([(t, d["pos"] + 4 * lo, d["end"] + 4 * lo, d["mapq"] + lo, d["flag"] + 2 * lo, hi - lo) for t, lo, hi in runs], min_q)
+        elif column != "packed":
+            raise ValueError("column must be 'packed' or 'packed2'")
+        elif d.get("packed") and int(min_q) <= 63 and getattr(batch, "binned_for", None) is self:
             self.push_binned_device_multi([(t, d["packed"] + 8 * lo, d["pos"] + 4 * lo, d["end"] + 4 * lo, hi - lo) for t, lo, hi in runs], min_q)
         elif d.get("packed") and int(min_q) <= 63 and getattr(batch, "binned_for", None) is None:
             self.push_packed_device_multi([(t, d["packed"] + 8 * lo, d["end"] + 4 * lo, hi - lo) for t, lo, hi in runs], min_q)
@@ -218,6 +230,26 @@ class CoverageHistogram:
             self.close()
         except Exception:
             pass
+
+
+def bins_by_contig(hist, contigs, allbins=None):
+    """{contig name: float64 bins} of a :class:`CoverageHistogram` for the names in `contigs`, in their order: what ``tiddit --cov``
+    and the coverage track of ``tiddit --sv`` hand to :func:`print_coverage`.  A few contigs are finished one by one; a header of many
+    (GRCh38's alt contigs), or `allbins` given (every bin of the histogram in one piece: ``finish_all`` / the N-rank job's reduced
+    bins), is cut out of the one array.  Either way a contig is found by its NAME — never by its position in a dictionary, which
+    equals its contig id only while no two ``@SQ`` lines share a name."""
+    contigs = list(contigs)
+    if allbins is None and len(contigs) <= 64:
+        return {n: hist.finish(n) for n in contigs}
+    if allbins is None:
+        allbins = hist.finish_all()
+    if len(allbins) != hist.total_bins():
+        raise ValueError("bins_by_contig: %d bins for a histogram of %d" % (len(allbins), hist.total_bins()))
+    out = {}
+    for n in contigs:
+        o = hist.offset(n)
+        out[n] = allbins[o:o + hist.nbins(n)[0]].copy()
+    return out
 
 
 def _contig_length(coverage_data, bin_size, end_bin_size):

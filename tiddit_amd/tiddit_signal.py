@@ -297,7 +297,13 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
 
     shard = (rank, world): only the records that start in this rank's byte range of the file (bamio.DeviceBamReader); the
     seam offsets are left in ``LAST_SEAM`` for dist.check_seams.  reduce_bins(hist) -> float64 array of ALL the histogram's
-    bins (the sharded caller all-reduces them there); default: this process's own bins."""
+    bins (the sharded caller all-reduces them there); default: this process's own bins.
+
+    ``COV_TRACK = (bin_size, min_q)``: a second histogram over EVERY contig of the header is filled from the same batches (their second
+    coverage-record column, written by the ingest kernel in the pass that decodes them) and its bins are left in ``COV_TRACK_BINS``."""
+    global COV_TRACK_BINS
+    COV_TRACK_BINS = None
+    track = COV_TRACK
     max_ins = int(max_ins)         # the reference's `int max_ins` argument truncates a float percentile (:147,:230; probed with Cython 3.2)
     from . import bamio
     carry = None
@@ -323,9 +329,25 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         hist = tiddit_coverage.CoverageHistogram([(n, l) for n, l in zip(names, lengths)], bin_size)
         if hasattr(reader, "bin_for"):
             reader.bin_for(hist)                 # the ingest kernel writes the coverage records for this bin size
+    hist2 = None
+    if carry is not None and carry.hist2 is not None:
+        # (the carried batches' second column was written for it; one made for another bin size is of no use: those batches then go
+        # through their field arrays, CoverageHistogram.push_device_batch)
+        hist2, carry.hist2 = carry.hist2, None
+        if track is None or hist2.bin_size != track[0]:
+            hist2.close()
+            hist2 = None
+        else:
+            hist2.reset()
+    if track is not None and hist2 is None:
+        hist2 = tiddit_coverage.CoverageHistogram([(n, l) for n, l in zip(names, lengths)], track[0], ctx=getattr(reader, "ctx", None))
+    if hasattr(reader, "second_for") and (hist2 is not None or getattr(reader, "_second_for", None) is not None):
+        reader.second_for(hist2)                 # the ingest kernel writes a second record per read, for this histogram
     T = SCAN_SECONDS
     T.clear()
     T.update({"ingest (inflate + decode, device)": 0.0, "coverage push": 0.0})
+    if hist2 is not None:
+        T["coverage track push (second histogram)"] = 0.0
     store = None
     if KEEP_EVIDENCE:
         # the variant stage's evidence store (tiddit_region.EvidenceStore): every placed record packed on the device as the batches go by
@@ -377,6 +399,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 hist.push_device_batch(b, min_q, big)           # coverage (filter on the device, :171-182)
                 t3 = time.time()
                 T["coverage push"] += t3 - t1
+                if hist2 is not None:                           # the track: every contig, its own mapq cut; one more launch, nothing waited for
+                    hist2.push_device_batch(b, track[1], None, column="packed2")
+                    t3b = time.time()
+                    T["coverage track push (second histogram)"] += t3b - t3
+                    t3 = t3b
                 if store is not None:                           # (enqueued before ahead() below hands the batch's buffers on)
                     store.add_device_batch(b)
                     t3b = time.time()
@@ -414,6 +441,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 t = int(tid[lo])
                 if t >= 0 and big[t]:
                     hist.push(t, b.pos[lo:hi], b.end[lo:hi], b.mapq[lo:hi], b.flag[lo:hi], min_q)
+                if t >= 0 and hist2 is not None:
+                    hist2.push(t, b.pos[lo:hi], b.end[lo:hi], b.mapq[lo:hi], b.flag[lo:hi], track[1])
             t3 = time.time()
             T["coverage push"] += t3 - t2
             primary = ok_contig & ((flag & 0x404) == 0) & ((flag & 0x900) == 0) & (b.mapq >= min_q)   # :171,:184,:188
@@ -458,6 +487,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             tables.close()
         if store is not None:
             store.close()
+        if hist2 is not None:
+            hist2.close()
         raise
     finally:
         pool.shutdown(wait=True)                              # (also on an error: no row thread outlives the scan)
@@ -488,6 +519,12 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 o = hist.offset(i)
                 coverage[n] = allbins[o:o + hist.nbins(i)[0]].copy()
     hist.close()
+    if hist2 is not None:
+        # the track's bins, every contig of the header (on N ranks: through the same exact all-reduce as the 50-bp bins)
+        try:
+            COV_TRACK_BINS = tiddit_coverage.bins_by_contig(hist2, names, reduce_bins(hist2) if reduce_bins is not None else None)
+        finally:
+            hist2.close()
     return header, chromosomes, coverage, data, splits, clips, tables
 
 
@@ -509,6 +546,9 @@ _SCAN_CACHE = {}
 STAGE_SECONDS = {}          # wall seconds of the last main(), stage by stage
 SCAN_SECONDS = {}           # ... and of the last scan pass, by what the host waited for
 LAST_SEAM = {}              # seam offsets of the last sharded scan pass (dist.check_seams)
+COV_TRACK = None            # (bin_size, min_q): the scan also fills a second histogram over every contig — the coverage `tiddit --cov -z -q` computes —
+                            # from the same batches; None (the default): the scan does what it does without it
+COV_TRACK_BINS = None       # {contig: float64 bins} of that histogram after the last scan that had COV_TRACK set (on N ranks: the reduced bins), else None
 KEEP_EVIDENCE = False       # the scan packs every placed record into an evidence store for the variant stage (tiddit_variant.LIVE_STORE)
 AFTER_SCAN = []             # callables main() invokes once the file has been scanned, before the tables are written (host-only work from there on)
 READER_SECONDS = {}         # the reader thread of the last scan: seconds reading, scanning BGZF headers, building tables, waiting — and the consumer's waits
@@ -792,6 +832,8 @@ def _main_sharded(bam_file_name, ref, prefix, min_q, max_ins, sample_id, threads
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     t = time.time()
 
+    seams = []
+
     def reduce_bins(hist):
         ctx = hist.ctx
         dev = torch.device("cuda", ctx.device)
@@ -799,7 +841,9 @@ def _main_sharded(bam_file_name, ref, prefix, min_q, max_ins, sample_id, threads
         torch.cuda.synchronize(dev)          # torch's allocator work runs on torch's stream, the library on its own: order them
         hist.finish_all_device(bins.data_ptr())
         ctx.sync()
-        tdist.check_seams(LAST_SEAM["first_off"], LAST_SEAM["next_off"], LAST_SEAM["empty"], group)
+        if not seams:                        # (once per scan: the coverage track's histogram comes through here a second time)
+            tdist.check_seams(LAST_SEAM["first_off"], LAST_SEAM["next_off"], LAST_SEAM["empty"], group)
+            seams.append(True)
         if dist.get_backend(group) != "nccl":
             bins = tdist.allreduce_bins(bins.cpu(), group)
         else:

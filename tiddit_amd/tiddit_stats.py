@@ -39,7 +39,7 @@ def _device_figures(lib, h, state):
 STAGE_SECONDS = {}          # wall seconds inside the last statistics() call, by what it waited for
 
 
-def _statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=False, shard=None):
+def _statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=False, shard=None, track_bin_size=None):
     import os
     from . import bamio
     library = {}
@@ -57,11 +57,15 @@ def _statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=False,
     STAGE_SECONDS["open the reader"] = time.time() - t
     on_device = isinstance(reader, bamio.DeviceBamReader)
     carry = carry and on_device and os.environ.get("TIDDIT_NO_CARRY") != "1"
-    kept, hist = [], None
+    kept, hist, hist2 = [], None, None
     if carry:
         from . import tiddit_coverage
         hist = tiddit_coverage.CoverageHistogram([(n, l) for n, l in zip(reader.references, reader.lengths)], 50, ctx=reader.ctx)
         reader.bin_for(hist)
+        if track_bin_size is not None:
+            # (the scan also fills the coverage track's histogram: the carried batches bring its records along in their second column)
+            hist2 = tiddit_coverage.CoverageHistogram([(n, l) for n, l in zip(reader.references, reader.lengths)], track_bin_size, ctx=reader.ctx)
+            reader.second_for(hist2)
         reader.retain = True
     STAGE_SECONDS["50-bp histogram for the carried batches"] = time.time() - t - STAGE_SECONDS["open the reader"]
     lib = _native.load()
@@ -98,6 +102,8 @@ def _statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=False,
                 reader.close()
                 if hist is not None:
                     hist.close()
+                if hist2 is not None:
+                    hist2.close()
                 return _statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=False, shard=None)
             STAGE_SECONDS["the other batches + sampling kernels"] = time.time() - (t_first or t_loop)
             t_f = time.time()
@@ -136,7 +142,7 @@ def _statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=False,
             figures = (numpy.average(insert_size), numpy.std(insert_size), numpy.percentile(insert_size, 99.9))
     if carry:
         reader.retain = False
-        bamio.set_carry(bamio.ScanCarry(bam_file_name, reader, batches, kept, hist))
+        bamio.set_carry(bamio.ScanCarry(bam_file_name, reader, batches, kept, hist, hist2))
     else:
         batches.close()                          # (the generator's finally stops the span thread and hands its pinned buffers back)
         reader.close()
@@ -166,11 +172,13 @@ def _statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=False,
     return library
 
 
-def statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=False, shard=None):
+def statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=False, shard=None, track_bin_size=None):
     """``tiddit_stats.statistics`` (tiddit_stats.py:5-78); the collector is off meanwhile (hostutil.quiet_gc).
     carry=True (the one-process `tiddit --sv` sets it: the signal scan of the same file follows at once and takes it,
     bamio.take_carry): the sampled batches stay in HBM with an open reader for that scan.  A library caller leaves nothing behind.
     shard=(0, world): rank 0 of an N-rank job — the sample is read through the reader of rank 0's byte range, so the carry is the head
-    of that rank's own scan (same figures: the sample is a prefix of the file either way)."""
+    of that rank's own scan (same figures: the sample is a prefix of the file either way).
+    track_bin_size (with carry): the carried batches also hold the coverage records of a second histogram of that bin size, for a
+    scan that writes the coverage track (``tiddit_signal.COV_TRACK``)."""
     with quiet_gc():
-        return _statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=carry, shard=shard)
+        return _statistics(bam_file_name, ref, min_mapq, max_ins_len, n_reads, carry=carry, shard=shard, track_bin_size=track_bin_size)
