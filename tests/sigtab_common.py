@@ -2,7 +2,9 @@
 host code) and everything built on them can be tested without a GPU:
   * select_host — what ``tdt_signal_scan`` + ``tdt_signal_scan_result`` return for a decoded batch (the per-read chain of
     tiddit_signal.worker, tiddit_signal.pyx:171-221, as numpy predicates — the same expressions as the host-ingest branch of
-    tiddit_signal._scan — and the selected reads' 28-byte field records + raw BAM records);
+    tiddit_signal._scan — and the selected reads' 28-byte field records + raw BAM records); select_host is itself checked against
+    the device (test_gpu_sv_stages.py: field by field and byte for byte on adversarial batches) and against a literal per-read
+    transcription of the rules (test_sv_stage_refs_cpu.py);
   * oracle_labels — what ``tdt_cluster_columns`` returns (stable sort by posA + the oracle's DBSCAN.main per bucket).
 Test infrastructure only."""
 import numpy as np
