@@ -251,7 +251,10 @@ int64_t orc_dbscan_main(const int64_t *data, int64_t n, int64_t stride, double e
 /* ------------------------------------------------------------------------------------------
  * get_region — tiddit_variant.pyx:54-151, literal loop over ONE contig's coordinate-sorted records.
  * PARITY UNPINNED at the fetch boundary (pysam absent): samfile.fetch(chr, q_start, q_end) is taken to
- * return the records with pos < q_end and bam_endpos > q_start, in file order.
+ * return the records with pos < q_end and bam_endpos > q_start, in file order.  Pinned on the CPU to a second,
+ * independent restatement of the same lines (tests/variant_stage_cases.py: get_region_loop / get_region_numpy, compared
+ * by tests/test_variant_stage_refs_cpu.py on reads and queries on every edge of the chain) — to a restatement, still
+ * not to pysam.
  * out[7] = bases, n_reads, low_q, n_discs, n_splits, crossing_f, crossing_r.
  * ---------------------------------------------------------------------------------------- */
 void orc_get_region(const int32_t *start, const int32_t *end, const uint8_t *mapq, const uint16_t *flag,
