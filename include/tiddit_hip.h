@@ -283,6 +283,8 @@ int tdt_sigtab_sizes(void *t, int what, int64_t *out_per_contig);
 int tdt_sigtab_pwrite(void *t, int what, int contig, int fd, int64_t offset);
 int tdt_sigtab_cluster_table(void *t, int is_mp, int64_t min_contig, size_t *n_signals, int *n_buckets);
 int tdt_sigtab_cluster_columns(void *t, int32_t *posA, int32_t *posB, int64_t *bucket_off, int32_t *bucket_a, int32_t *bucket_b);
+/* one byte per row of the cluster table, in the order of tdt_sigtab_cluster_columns: 0 = discordant pair, 1 = split read */
+int tdt_sigtab_cluster_kinds(void *t, uint8_t *kind);
 int tdt_sigtab_regroup(void *t, const int32_t *labels, size_t *n_candidates, size_t *n_members, size_t *name_bytes);
 int tdt_sigtab_regroup_result(void *t, int32_t *cand4, int32_t *startA, int32_t *endA, int32_t *startB, int32_t *endB, int32_t *posA, int32_t *posB,
                               uint8_t *oriA, uint8_t *oriB, char *names);
@@ -378,6 +380,27 @@ int tdt_region_counts_packed(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contig
  * The library's stream is synchronised before the return.  TDT_E_ARG as above for other min_q / max_ins. */
 int tdt_region_counts_packed_device(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *d_queries,
                                     size_t nq, int min_q, int64_t max_ins, int64_t *d_out);
+
+/* ---- link counts of SV sites (TIDDIT_GENOTYPE) ------------------------------------------------------- *
+ * How many signals of the cluster table join the two regions of a site: for site {bucket, startA, endA, startB, endB} the rows of
+ * that (chrA, chrB) bucket with startA <= posA <= endA and startB <= posB <= endB, counted per kind — out[0] the discordant pairs
+ * (kind 0), out[1] the split reads (kind 1); rows of kind 2 (assembly contigs) are counted in neither.  Buckets and the A/B
+ * orientation of a row are those of tdt_sigtab_cluster_table, so signals on contigs below its min_contig are in no bucket and count
+ * as zero; the caller flips a site whose contigs are in the other order.
+ * tdt_links_create: host columns (pinned or not) posA / posB / kind of bucket_off[nb] signals, bucket_off = int64[nb + 1] starting
+ * at 0 and not decreasing.  The columns are uploaded, every bucket is sorted by posA on the device and ONE 8-byte record per signal
+ * {posA, posB | kind << 30} stays in HBM: TDT_E_UNSUPPORTED for a posB outside [0, 2^30) or a kind above 2, TDT_E_RANGE for 2^30
+ * signals or more.  tdt_links_count: sites = int32[ns][6] {bucket, startA, endA, startB, endB, 0} and out = int64[ns][2] on the
+ * host; one launch, one wave per site.  bucket -1 (no signals between these contigs) gives zeros.  Refused on the host, before
+ * anything is launched: start > end (TDT_E_ARG), a bucket below -1 or >= nb (TDT_E_RANGE); ns == 0 returns TDT_OK.
+ * tdt_links_count_device: sites and counts in HBM (8-byte aligned); the kernel makes the same checks — a refused site gets zeros and
+ * the call returns TDT_E_RANGE naming the first one.  Both synchronise the context's stream before they return. */
+typedef struct tdt_links tdt_links;
+int tdt_links_create(tdt_ctx *ctx, const int32_t *posA, const int32_t *posB, const uint8_t *kind, const int64_t *bucket_off, int nb,
+                     tdt_links **out);
+int tdt_links_destroy(tdt_links *h);
+int tdt_links_count(tdt_links *h, const int32_t *sites, size_t ns, int64_t *out);
+int tdt_links_count_device(tdt_links *h, const int32_t *d_sites, size_t ns, int64_t *d_out);
 
 /* ---- coverage table text (host, threaded) ----------------------------------------------------------- *
  * The row loop of print_coverage (tiddit_coverage.pyx:30-44) for one contig: kind 0 = bed rows

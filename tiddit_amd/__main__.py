@@ -15,6 +15,10 @@ same ``{o}.vcf``.  Local assembly stays out of scope.
 ``TIDDIT_COV_TRACK=Z[:Q[:bed|wig]]``: ``--sv`` also writes ``{o}.bed`` (or ``{o}.wig``), byte for byte the file ``--cov -z Z -q Q [-w]``
 writes for the same BAM — from the scan's own pass over the file: the ingest kernel writes a second coverage record per read, a second
 histogram is filled beside the 50-bp one, and no second job reads and inflates the file again.  On N ranks rank 0 writes it.
+
+``TIDDIT_GENOTYPE=sites.vcf``: ``--sv`` also writes ``{o}.genotyped.vcf`` — every record of ``sites.vcf`` with this sample's
+``GT:CN:COV:DV:RV:LQ:RR:DR`` (tiddit_amd/tiddit_genotype.py) — from the evidence store and the signal tables the scan left, with or
+without ``TIDDIT_VARIANTS=1``.  One process only: on N ranks the switch is refused before anything is started.
 """
 import argparse
 import os
@@ -190,6 +194,7 @@ def run_sv(args, version):
     except ValueError as e:
         print("error, TIDDIT_COV_TRACK={}: {}".format(os.environ.get("TIDDIT_COV_TRACK"), e))
         quit()
+    sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     if not args.skip_assembly:
         print("error, local assembly is outside this build's scope; rerun with --skip_assembly")
         quit()
@@ -228,6 +233,10 @@ def run_sv(args, version):
     # TIDDIT_FORCE_DIST=1: take the N-rank code path with whatever WORLD_SIZE says, also 1 — a one-GPU box can then run every
     # collective of the job over real RCCL (backend nccl refuses two ranks on one device; tests/test_gpu_sv_e2e.py)
     multi = world > 1 or os.environ.get("TIDDIT_FORCE_DIST") == "1"
+    if multi and sites_path is not None:
+        # (every rank, before the first collective: no rank is left waiting for another)
+        print("error, TIDDIT_GENOTYPE is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) does not genotype sites")
+        sys.exit(1)
     if multi:
         import torch
         import torch.distributed as dist
@@ -340,6 +349,22 @@ def run_sv(args, version):
                 STAGE_NOTES["batches ingested beside rank 0's statistics"] = held
     max_ins_len = args.i if args.i else library["percentile_insert_size"]
     T["library statistics"] = time.time() - t
+    genotype_job = None
+    if sites_path is not None:
+        # TIDDIT_GENOTYPE: the sites are read now (their windows need max_ins_len) — a bad file ends the job before the scan
+        from . import tiddit_genotype
+        t = time.time()
+        try:
+            meta, records = tiddit_genotype.parse_vcf(sites_path)
+            sites, rules = tiddit_genotype.sites_of(records, contig_number, contig_length, max_ins_len)
+        except tiddit_genotype.SitesError as e:
+            if gc_job is not None and "thread" in gc_job:
+                gc_job["thread"].join()                      # (no helper thread outlives the error)
+            from . import bamio
+            bamio.set_carry(None)                            # (nor the batches and the reader the statistics kept for the scan)
+            print("error, TIDDIT_GENOTYPE={}: {}".format(sites_path, e))
+            sys.exit(1)
+        genotype_job = {"path": sites_path, "meta": meta, "records": records, "sites": sites, "rules": rules, "sites (host)": time.time() - t}
     if gc_job is not None and gc_mode != "after":
         start_gc()              # (the N-rank job and TIDDIT_GC_OVERLAP=scan: beside the scan only)
 
@@ -349,7 +374,8 @@ def run_sv(args, version):
     tiddit_signal.BACKGROUND_WRITES = (not multi) and os.environ.get("TIDDIT_BACKGROUND_WRITES", "1") != "0"
     # TIDDIT_VARIANTS=1: the scan also packs every placed record into the evidence store the native variant stage reads (on N ranks:
     # every rank the records of its own shard)
-    tiddit_signal.KEEP_EVIDENCE = os.environ.get("TIDDIT_VARIANTS") == "1"
+    # TIDDIT_GENOTYPE needs the same store, with or without the variant stage
+    tiddit_signal.KEEP_EVIDENCE = os.environ.get("TIDDIT_VARIANTS") == "1" or genotype_job is not None
     if track is not None:
         # TIDDIT_COV_TRACK: the scan fills a second histogram — every contig, the track's bin size and mapq cut — from the same batches
         tiddit_signal.COV_TRACK = (track[0], track[1])
@@ -383,7 +409,8 @@ def run_sv(args, version):
         del bins
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
-                    library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False)
+                    library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,
+                    genotype_job)
     except BaseException:
         # no helper thread outlives the error: the writer thread of BACKGROUND_WRITES is joined (its own error, if any, is not the one to report)
         try:
@@ -399,8 +426,9 @@ def run_sv(args, version):
 
 
 def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, contigs, contig_length, samples, library, coverage_data, bam_header,
-                max_ins_len, min_mapq, sample_id, version, contig_number, own_group):
-    """run_sv behind the BAM scan: GC bins, ploidy table, clustering, candidates table, the signal files complete"""
+                max_ins_len, min_mapq, sample_id, version, contig_number, own_group, genotype_job=None):
+    """run_sv behind the BAM scan: GC bins, ploidy table, clustering, candidates table, the signal files complete, the variant stage
+    (TIDDIT_VARIANTS=1), the genotypes of known sites (TIDDIT_GENOTYPE)"""
     from . import tiddit_cluster, tiddit_coverage_analysis, tiddit_gc, tiddit_signal
     from .trace import stage
     if multi:
@@ -463,15 +491,21 @@ def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, con
         # ranks every rank takes part (the counts over its shard's store); rank 0 types the variants and writes the file.
         from . import tiddit_variant, tiddit_vcf_header
         t = time.time()
-        with stage("tiddit: variant typing"):
-            variant_stage(tiddit_variant, tiddit_vcf_header, prefix, contigs, bam_header, library, sample_id, version, args, sv_clusters, min_mapq,
-                          samples, coverage_data, contig_number, max_ins_len, gc_dictionary,
-                          entry=tiddit_variant.main_sharded if multi else tiddit_variant.main)
+        tiddit_variant.KEEP_STORE = genotype_job is not None         # (the store serves the genotyping behind this stage, which frees it)
+        try:
+            with stage("tiddit: variant typing"):
+                variant_stage(tiddit_variant, tiddit_vcf_header, prefix, contigs, bam_header, library, sample_id, version, args, sv_clusters,
+                              min_mapq, samples, coverage_data, contig_number, max_ins_len, gc_dictionary,
+                              entry=tiddit_variant.main_sharded if multi else tiddit_variant.main)
+        finally:
+            tiddit_variant.KEEP_STORE = False
         T["variant typing (native)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_variant.STAGE_SECONDS.items()})
         if rank == 0:
             print("analyzed clusters in")
             print(T["variant typing (native)"])
+    elif rank == 0 and genotype_job is not None:
+        pass                                                             # (TIDDIT_GENOTYPE alone: no {prefix}.vcf, the genotypes below)
     elif rank == 0:
         # Without TIDDIT_VARIANTS=1 the run stops at the candidates table.  When the reference package itself is importable (it needs
         # pysam) the candidates are handed to it, as the reference's driver does (__main__.py:193-207), so that a full installation
@@ -488,11 +522,56 @@ def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, con
         else:
             print("variant typing/filtering (tiddit_variant) is outside this build's scope; candidates written to {}.candidates.tab "
                   "(TIDDIT_VARIANTS=1 runs the native variant stage)".format(prefix))
+    if genotype_job is not None:
+        t = time.time()
+        with stage("tiddit: genotyping of known sites"):
+            genotype_stage(genotype_job, args, prefix, samples, library, coverage_data, bam_header, gc_dictionary, min_mapq, max_ins_len, sample_id,
+                           version, contig_number, T)
+        T["genotyping of known sites ({o}.genotyped.vcf)"] = time.time() - t
     if multi:
         dist.barrier()                                                   # every output file exists when any rank returns
         if own_group:
             # (a process that exits with its RCCL group alive can die in the group's watchdog thread while the HIP runtime unloads)
             dist.destroy_process_group()
+
+
+def genotype_stage(job, args, prefix, samples, library, coverage_data, bam_header, gc_dictionary, min_mapq, max_ins_len, sample_id, version,
+                   contig_number, T):
+    """TIDDIT_GENOTYPE: {prefix}.genotyped.vcf from the evidence store the scan left (after the variant stage, if that ran) and the
+    cluster table of the job's signal tables on the device (tiddit_genotype.py); both are freed here"""
+    from . import tiddit_genotype, tiddit_region, tiddit_signal, tiddit_variant, tiddit_vcf_header
+    T["  sites (host, before the scan)"] = job["sites (host)"]
+    t = time.time()
+    tables = tiddit_signal.written_tables("{}_tiddit/discordants_{}.tab".format(prefix, samples[0]), "{}_tiddit/splits_{}.tab".format(prefix, samples[0]))
+    if tables is None:
+        raise RuntimeError("TIDDIT_GENOTYPE: the signal tables of this job are gone (its .tab files changed under it)")
+    store = tiddit_variant.take_store(args.bam, min_mapq, int(max_ins_len))
+    links = None
+    try:
+        if store is None:
+            store = tiddit_region.build_store(args.bam, min_mapq, int(max_ins_len))
+            T["  evidence store (one ingest pass)"] = time.time() - t
+            t = time.time()
+        links = tiddit_genotype.links_of_tables(tables, library["mp"], args.min_contig)
+        T["  links handle (cluster table, upload + sort)"] = time.time() - t
+        columns = tiddit_genotype.genotype_sites(store, links, job["sites"], args, library, coverage_data, gc_dictionary, min_mapq, max_ins_len,
+                                                 contig_number=contig_number, rules=job["rules"])
+    finally:
+        if links is not None:
+            links.close()
+        if store is not None:
+            store.close()
+    T.update({"  " + k: v for k, v in tiddit_genotype.STAGE_SECONDS.items()})
+    t = time.time()
+    head = tiddit_genotype.header(tiddit_vcf_header.main(bam_header, library, sample_id, version), job["meta"], job["path"], max_ins_len)
+    tiddit_genotype.write_vcf(prefix + ".genotyped.vcf", head, job["records"], columns)
+    T["  header + file"] = time.time() - t
+    missed = job["rules"].count("missed")
+    STAGE_NOTES["sites genotyped"] = len(columns)
+    STAGE_NOTES["sites whose breakpoints fit their REGIONA/REGIONB in neither order (window rule)"] = missed
+    print("genotyped {} sites of {} into {}.genotyped.vcf".format(len(columns), job["path"], prefix))
+    if missed:
+        print("note: {} of them have breakpoints outside their REGIONA/REGIONB and took the window rule".format(missed))
 
 
 def main(argv=None):

@@ -98,6 +98,7 @@ SYMBOLS = {
     "tdt_sigtab_pwrite": (_i, [_P, _i, _i, _i, _i64]),
     "tdt_sigtab_cluster_table": (_i, [_P, _i, _i64, ctypes.POINTER(_sz), ctypes.POINTER(_i)]),
     "tdt_sigtab_cluster_columns": (_i, [_P, _P, _P, _P, _P, _P]),
+    "tdt_sigtab_cluster_kinds": (_i, [_P, _P]),
     "tdt_sigtab_regroup": (_i, [_P, _P, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
     "tdt_sigtab_regroup_result": (_i, [_P] * 11),
     "tdt_masked_medians": (_i, [_P, _P, _P, _P, _i, _P, _P, _P]),
@@ -114,6 +115,10 @@ SYMBOLS = {
     "tdt_evstore_spans": (_i, [_P, _P]),
     "tdt_region_counts_packed": (_i, [_P, _P, _P, _i, _P, _sz, _i, _i64, _P]),
     "tdt_region_counts_packed_device": (_i, [_P, _P, _P, _i, _P, _sz, _i, _i64, _P]),
+    "tdt_links_create": (_i, [_P, _P, _P, _P, _P, _i, _PP]),
+    "tdt_links_destroy": (_i, [_P]),
+    "tdt_links_count": (_i, [_P, _P, _sz, _P]),
+    "tdt_links_count_device": (_i, [_P, _P, _sz, _P]),
     "tdt_format_coverage": (_i, [_P, _sz, ctypes.c_char_p, _i64, _i64, _i, _P, _sz, ctypes.POINTER(_sz)]),
     "tdt_fasta_write_fai": (_i, [ctypes.c_char_p, ctypes.c_char_p]),
     "tdt_host_threads": (_i, [_i]),

@@ -1004,6 +1004,18 @@ extern "C" int tdt_sigtab_cluster_columns(void *t_, int32_t *posA, int32_t *posB
     return TDT_OK;
 }
 
+// kind: n_signals bytes, one per row of the cluster table in the order of tdt_sigtab_cluster_columns — 0 a discordant pair ("D"),
+// 1 a split read ("S") (tdt_links_create counts a site's links per kind)
+extern "C" int tdt_sigtab_cluster_kinds(void *t_, uint8_t *kind) {
+    tdt_sigtab *t = as_tab(t_);
+    if (!t || (t->sigs.size() && !kind)) {
+        tdt_set_error("tdt_sigtab_cluster_kinds: bad argument");
+        return TDT_E_ARG;
+    }
+    for (size_t i = 0; i < t->sigs.size(); i++) kind[i] = t->sigs[i].kind;
+    return TDT_OK;
+}
+
 // ---- tiddit_cluster.pyx:156-254 without the per-row Python: labels[i] = cluster of signal i (-1 = noise), as tdt_cluster_columns
 // returns them.  A candidate is a (bucket, cluster id); candidates of a bucket in the order their id first appears in signal order
 // (the insertion order of candidates[chrA][chrB], which later numbers the VCF records).

@@ -161,6 +161,12 @@ class SignalTables:
         self._check(self.lib.tdt_sigtab_cluster_columns(self._h, _native.ptr(posA), _native.ptr(posB), _native.ptr(off), _native.ptr(a), _native.ptr(b)))
         return off, a, b
 
+    def cluster_kinds(self, n):
+        """uint8[n_signals]: 0 a discordant pair, 1 a split read, row for row with the columns of :meth:`cluster_columns`"""
+        kind = numpy.zeros(n, dtype=numpy.uint8)
+        self._check(self.lib.tdt_sigtab_cluster_kinds(self._h, _native.ptr(kind)))
+        return kind
+
     def regroup(self, labels):
         """labels int32[n_signals] (-1 = noise) -> dict of arrays describing every candidate and its members (see tdt_sigtab_regroup_result)"""
         labels = numpy.ascontiguousarray(labels, dtype=numpy.int32)

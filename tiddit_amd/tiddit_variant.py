@@ -49,6 +49,14 @@ def region_tuple(counts, start, end):
     return (coverage, frac_low_q, n_discs, n_splits, crossing_f, crossing_r)
 
 
+def copy_number(chrA, covM, args, library):
+    """the CN of an intrachromosomal variant (:159-165): the coverage between the breakpoints in units of one copy of chrA"""
+    avg = library["avg_coverage_{}".format(chrA)]
+    if avg != 0:
+        return int(round(covM * library["contig_ploidy_{}".format(chrA)] / avg))
+    return int(round(covM * args.n / library["avg_coverage"]))
+
+
 def find_sv_type(chrA, chrB, inverted, non_inverted, args, sample_data, samples, library):
     """(:153-189) -> (svtype, copy number); the copy number is the last sample's"""
     if chrA != chrB:
@@ -56,10 +64,7 @@ def find_sv_type(chrA, chrB, inverted, non_inverted, args, sample_data, samples,
     p = library["contig_ploidy_{}".format(chrA)]
     avg = library["avg_coverage_{}".format(chrA)]
     for sample in samples:
-        if avg != 0:
-            cn = int(round(sample_data[sample]["covM"] * p / avg))
-        else:
-            cn = int(round(sample_data[sample]["covM"] * args.n / library["avg_coverage"]))
+        cn = copy_number(chrA, sample_data[sample]["covM"], args, library)
     if p > args.n * 10:                        # mitochondria or similar
         if cn > p * 1.05:
             return ("DUP:INV" if inverted else "DUP:TANDEM"), cn
@@ -151,7 +156,11 @@ def region_queries(chrA, chrB, c, posA, posB):
 
 def _genotype(c, sd, sample, args, n_contigs):
     """the GT every record of a candidate starts from (the three genotype blocks of define_variant)"""
-    n_sp, n_di = len(c["sample_splits"][sample]), len(c["sample_discordants"][sample])
+    return genotype_of(len(c["sample_splits"][sample]), len(c["sample_discordants"][sample]), sd, args, n_contigs)
+
+
+def genotype_of(n_sp, n_di, sd, args, n_contigs):
+    """:func:`_genotype` from the sample's two support counts"""
     GT = "./."
     if n_sp >= args.r or n_di >= args.p:
         GT = "0/1"
@@ -169,6 +178,32 @@ def _genotype(c, sd, sample, args, n_contigs):
         else:
             GT = "1/1"
     return GT
+
+
+def depth_genotype(GT, svtype, cn, ploidy):
+    """the read-depth override of the GT of a <DEL> / <DUP...> record (the record loop of define_variant); GT itself otherwise"""
+    if "DEL" in svtype:
+        return "1/1" if cn == 0 else "0/1"
+    if "DUP" in svtype:
+        return "1/1" if cn >= 2 * ploidy else "0/1"
+    return GT
+
+
+def site_evidence(chrA, chrB, posA, posB, startA, endA, startB, endB, regions, cov_between):
+    """one sample's evidence dict of a site (:290-315) from the get_region results; cov_between: covM of an intrachromosomal site
+    whose breakpoints are 1000 bp or more apart (tiddit_region.candidate_means)"""
+    covA, QA, discA, splitA, refFA, refRA = regions[(chrA, startA, endA, posA)]
+    covB, QB, discB, splitB, refFB, refRB = regions[(chrB, startB, endB, posB)]
+    sd = {"covA": covA, "QA": QA, "discA": discA, "splitA": splitA, "refRA": refRA, "refFA": refFA,
+          "covB": covB, "QB": QB, "discB": discB, "splitB": splitB, "refRB": refRB, "refFB": refFB}
+    if chrA != chrB:
+        sd["covM"] = 0
+    elif abs(posB - posA) < 1000:
+        key = (chrA, posA, posB, posA) if posA < posB else (chrA, posB, posA, posB)
+        sd["covM"] = regions[key][0]
+    else:
+        sd["covM"] = cov_between
+    return sd
 
 
 def _sample_column(GT, cn, sd, n_discordants, n_splits):
@@ -197,18 +232,8 @@ def define_variant(chrA, sv_clusters, args, library, samples, max_ins_len, conti
         var_n += 1
         sample_data = {}
         for sample in samples:
-            covA, QA, discA, splitA, refFA, refRA = regions[(chrA, c["startA"], c["endA"], posA)]
-            covB, QB, discB, splitB, refFB, refRB = regions[(chrB, c["startB"], c["endB"], posB)]
-            sd = {"covA": covA, "QA": QA, "discA": discA, "splitA": splitA, "refRA": refRA, "refFA": refFA,
-                  "covB": covB, "QB": QB, "discB": discB, "splitB": splitB, "refRB": refRB, "refFB": refFB}
-            if chrA != chrB:
-                sd["covM"] = 0
-            elif abs(posB - posA) < 1000:
-                key = (chrA, posA, posB, posA) if posA < posB else (chrA, posB, posA, posB)
-                sd["covM"] = regions[key][0]
-            else:
-                sd["covM"] = means[(chrA, chrB, cid)]["covM"]
-            sample_data[sample] = sd
+            sample_data[sample] = site_evidence(chrA, chrB, posA, posB, c["startA"], c["endA"], c["startB"], c["endB"], regions,
+                                                means[(chrA, chrB, cid)]["covM"])
         # `sample` is the last sample from here on, as in the reference
         inverted = non_inverted = 0
         pa, pb = c["positions_A"], c["positions_B"]
@@ -249,11 +274,7 @@ def define_variant(chrA, sv_clusters, args, library, samples, max_ins_len, conti
             variant = [chrA, str(posA), "SV_{}_1".format(var_n), "N", alt, ".", filt, ";".join(info), FORMAT_COL]
             for sample in samples:
                 sd = sample_data[sample]
-                GT = _genotype(c, sd, sample, args, n_contigs)
-                if "DEL" in alt:
-                    GT = "1/1" if cn == 0 else "0/1"
-                elif "DUP" in alt:
-                    GT = "1/1" if cn >= 2 * library["contig_ploidy_{}".format(chrA)] else "0/1"
+                GT = depth_genotype(_genotype(c, sd, sample, args, n_contigs), svtype, cn, library["contig_ploidy_{}".format(chrA)])
                 variant.append(_sample_column(GT, cn, sd, n_discordants, n_splits))
             variants.append([chrA, posA, variant, scoring_dict])
             continue
@@ -325,8 +346,10 @@ def vcf_body(contigs, variants):
     return "".join(lines)
 
 
-# the store the signal scan of this process filled (tiddit_signal sets it; the variant stage frees it)
+# the store the signal scan of this process filled (tiddit_signal sets it; the variant stage frees it — or, with KEEP_STORE, hands it
+# back here for the stage behind it: TIDDIT_GENOTYPE, whose driver frees it)
 LIVE_STORE = None
+KEEP_STORE = False
 STAGE_SECONDS = {}
 
 
@@ -391,7 +414,13 @@ def main(bam_file_name, sv_clusters, args, library, min_mapq, samples, coverage_
         t = time.time()
     try:
         regions = evidence(store, queries, min_mapq, int(max_ins_len))
-    finally:
+    except BaseException:
+        store.close()
+        raise
+    if KEEP_STORE:
+        global LIVE_STORE
+        LIVE_STORE = store
+    else:
         store.close()
     T["region counts (device, one launch)"] = time.time() - t
     t = time.time()
