@@ -8,7 +8,7 @@ below, and only DATA (inputs + the reference's outputs) is written here.  tiddit
 pysam for FastaFile only; a tiny in-memory stand-in (oracle-side tooling, lives in /tmp) serves
 the sequences.  Nothing in tests/, bench.py or smoke() reads /root/reference at run time.
 
-usage: python tests/golden/make_golden.py [--slow | --large | --grch38 | --only-y-labels]
+usage: python tests/golden/make_golden.py [--slow | --large | --grch38 | --only-y-labels | --only-edges]
   --slow adds the 1M-point DBSCAN run (~6 min); --large makes ONLY sv_e2e_large.json (the 240-Mb file of bench.py's sv_e2e section, ~12 min)
 """
 import hashlib
@@ -339,6 +339,51 @@ def golden_dbscan_y_labels(M, out):
     print("dbscan_y_labels:", nc, "cases")
 
 
+def golden_dbscan_edges(M, out):
+    """The real DBSCAN.py on the small aimed cases of tests/cluster_stage_cases.py (tile, route and bucket edges of the clustering
+    kernels), bucket by bucket: x_coordinate_clustering for every case and main for the cases of mode 0.  Only the labels (int32), the
+    ids per bucket and a hash of the inputs are stored; the inputs are regenerated from the case module.  -> dbscan_edges.npz"""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import cluster_stage_cases as cc
+    D = M["DBSCAN"]
+    res, names, hashes, xids = {}, [], [], []
+    for name in cc.case_names():
+        c = cc.get(name)
+        if not cc.in_golden(c):
+            continue
+        xl, ml = np.full(c["n"], -1, dtype=np.int32), np.full(c["n"], -1, dtype=np.int32)
+        xid = np.full(c["nb"], -1, dtype=np.int64)
+        for b in range(c["nb"]):
+            lo, hi = int(c["off"][b]), int(c["off"][b + 1])
+            if lo == hi:
+                continue
+            data = np.stack([c["x"][lo:hi], c["y"][lo:hi]], 1)
+            lab, cid = D.x_coordinate_clustering(data, c["eps"], c["m"])
+            xl[lo:hi], xid[b] = lab, cid
+            if c["mode"] == 0:
+                ml[lo:hi] = D.main(data, c["eps"], c["m"])
+        k = len(names)
+        names.append(name)
+        res["c%d_x" % k] = xl
+        if c["mode"] == 0:
+            res["c%d_main" % k] = ml
+        hashes.append(cc.input_hash(c))
+        xids.append(xid)
+    res["names"], res["hashes"], res["xid"] = np.array(names), np.array(hashes), np.concatenate(xids)      # (xid: nb values per case, in order)
+    np.savez_compressed(os.path.join(out, "dbscan_edges.npz"), **res)
+    print("dbscan_edges:", len(names), "cases,", os.path.getsize(os.path.join(out, "dbscan_edges.npz")), "bytes")
+
+
+def load_dbscan_only():
+    """the reference's DBSCAN.py alone (pure Python: nothing to compile)"""
+    pkg = os.path.join(BUILD, "tiddit")
+    os.makedirs(pkg, exist_ok=True)
+    with open(os.path.join(pkg, "__init__.py"), "w") as f:
+        f.write("__path__.append(%r)\n" % REF)
+    sys.path.insert(0, BUILD)
+    return {"DBSCAN": importlib.import_module("tiddit.DBSCAN")}
+
+
 # ---------------------------------------------------------------------------------- cluster
 def _jsonable(c):
     if isinstance(c, dict):
@@ -500,6 +545,9 @@ def golden_sv_e2e(M, out, params=None, name="sv_e2e.json"):
 
 def main():
     slow = "--slow" in sys.argv
+    if "--only-edges" in sys.argv:
+        golden_dbscan_edges(load_dbscan_only(), HERE)
+        return
     M = build_reference()
     if "--only-y-labels" in sys.argv:
         golden_dbscan_y_labels(M, HERE)
@@ -514,6 +562,7 @@ def main():
     golden_gc(M, HERE)
     golden_dbscan(M, HERE, slow)
     golden_dbscan_y_labels(M, HERE)
+    golden_dbscan_edges(M, HERE)
     golden_cluster(M, HERE)
     golden_sv_e2e(M, HERE)
     golden_sv_e2e(M, HERE, params={"total_mb": 3, "seed": 11, "sv_per_mb": 8.0, "n_reads_stats": 300000}, name="sv_e2e_small.json")

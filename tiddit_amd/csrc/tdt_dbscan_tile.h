@@ -704,7 +704,9 @@ __global__ __launch_bounds__(256) void dbt_finish1(const unsigned short *__restr
                 if (c[k] == DT_C_MINUS1) continue;
                 const int j = tl + 1 - (int)((c[k] & DT_C_PREV) != 0);     // the owner tile's prefix (the point's own tile, or the one before it)
                 const unsigned v = c[k] & DT_C_INDEX;
-                id[k] = (c[k] & DT_C_LITERAL) ? (double)xlab[i + k] : (c[k] & DT_C_EXTRA) ? (double)(R1 + (long long)(pE[j] + v)) : (double)(pR[j] + v);
+                // (xlab: the members of a cluster too large for this path get no code, so when the pass does not stand this kernel
+                // decodes whatever an earlier call left there — a literal code of a caller-labels call must not reach a null xlab)
+                id[k] = (xlab && (c[k] & DT_C_LITERAL)) ? (double)xlab[i + k] : (c[k] & DT_C_EXTRA) ? (double)(R1 + (long long)(pE[j] + v)) : (double)(pR[j] + v);
             }
             if (i + 2 <= n && al) *reinterpret_cast<double2 *>(lab + i) = make_double2(id[0], id[1]);
             else {
