@@ -8,7 +8,7 @@ below, and only DATA (inputs + the reference's outputs) is written here.  tiddit
 pysam for FastaFile only; a tiny in-memory stand-in (oracle-side tooling, lives in /tmp) serves
 the sequences.  Nothing in tests/, bench.py or smoke() reads /root/reference at run time.
 
-usage: python tests/golden/make_golden.py [--slow | --large | --grch38 | --only-y-labels | --only-edges]
+usage: python tests/golden/make_golden.py [--slow | --large | --grch38 | --only-y-labels | --only-edges | --only-coverage-edges]
   --slow adds the 1M-point DBSCAN run (~6 min); --large makes ONLY sv_e2e_large.json (the 240-Mb file of bench.py's sv_e2e section, ~12 min)
 """
 import hashlib
@@ -374,6 +374,50 @@ def golden_dbscan_edges(M, out):
     print("dbscan_edges:", len(names), "cases,", os.path.getsize(os.path.join(out, "dbscan_edges.npz")), "bytes")
 
 
+def write_npz(path, arrays):
+    """np.savez_compressed with fixed member dates: the same arrays give the same bytes"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue())
+
+
+def golden_coverage_edges(M, out):
+    """The real update_coverage, read by read behind the filter of __main__.py:231-235, on the small aimed cases of
+    tests/coverage_stage_cases.py (window, table and contig-end edges of the coverage kernels).  Stored sparse — the indices and values
+    of the nonzero bins of every contig — with a hash of the inputs, which are regenerated from the case module.  -> coverage_edges.npz"""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import coverage_stage_cases as cc
+    cov = M["tiddit_coverage"]
+    res, names, hashes = {}, [], []
+    for name in cc.case_names():
+        c = cc.get(name)
+        if not cc.in_golden(c):
+            continue
+        k = len(names)
+        for ci, ((sn, LN), (start, end, mapq, flag)) in enumerate(zip(c["contigs"], c["cols"])):
+            arr = np.zeros(0)
+            if LN:
+                arr, ebs = cov.create_coverage({"SQ": [{"SN": sn, "LN": LN}]}, c["z"], sn)
+            for s, e, q, f in zip(start.tolist(), end.tolist(), mapq.tolist(), flag.tolist()):
+                if f & 0x4 or f & 0x400 or q < c["min_q"]:
+                    continue
+                arr = cov.update_coverage(s, e, c["z"], arr, ebs)
+            nz = np.flatnonzero(arr)
+            res["k%d_c%d_idx" % (k, ci)], res["k%d_c%d_val" % (k, ci)] = nz.astype(np.int32), arr[nz].astype("<f8")
+        names.append(name)
+        hashes.append(cc.input_hash(c))
+    res["names"], res["hashes"] = np.array(names), np.array(hashes)
+    write_npz(os.path.join(out, "coverage_edges.npz"), res)
+    print("coverage_edges:", len(names), "cases,", os.path.getsize(os.path.join(out, "coverage_edges.npz")), "bytes")
+
+
 def load_dbscan_only():
     """the reference's DBSCAN.py alone (pure Python: nothing to compile)"""
     pkg = os.path.join(BUILD, "tiddit")
@@ -549,6 +593,9 @@ def main():
         golden_dbscan_edges(load_dbscan_only(), HERE)
         return
     M = build_reference()
+    if "--only-coverage-edges" in sys.argv:
+        golden_coverage_edges(M, HERE)
+        return
     if "--only-y-labels" in sys.argv:
         golden_dbscan_y_labels(M, HERE)
         return
@@ -563,6 +610,7 @@ def main():
     golden_dbscan(M, HERE, slow)
     golden_dbscan_y_labels(M, HERE)
     golden_dbscan_edges(M, HERE)
+    golden_coverage_edges(M, HERE)
     golden_cluster(M, HERE)
     golden_sv_e2e(M, HERE)
     golden_sv_e2e(M, HERE, params={"total_mb": 3, "seed": 11, "sv_per_mb": 8.0, "n_reads_stats": 300000}, name="sv_e2e_small.json")

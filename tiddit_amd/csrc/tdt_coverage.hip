@@ -1070,13 +1070,16 @@ extern "C" int tdt_cov_create(tdt_ctx *ctx, const int64_t *contig_len, int n_con
         const int ebs = c->end_bin_size[i] > 0 ? c->end_bin_size[i] : bin_size;
         // b/ebs >= b/bin_size, so the quotient never needs more fraction bits than the main table.
         // Entries with b >= ebs are only read for reads overhanging the contig end inside its last
-        // bin (the reference then really divides by end_bin_size, :69); they are exact too.
+        // bin (the reference then really divides by end_bin_size, :69); they are exact too — while
+        // they fit: a quotient of 2^53 units or more (bin sizes above 2^14 with a short end bin) is
+        // stored as 2^53, so the bin that receives it fails cov_finalize's test (TDT_E_INEXACT)
+        // instead of silently missing the contribution.
         const double scale = ldexp(1.0, c->S);
         for (size_t b = 0; b < lut_n; b++) {
             volatile float q = (float)b / (float)ebs;
             double f = (double)q * scale;
-            unsigned long long fx = (f < 1.8e19) ? (unsigned long long)f : 0ull;
-            t[b] = ((double)fx == f) ? fx : 0ull;
+            unsigned long long fx = (f < 9007199254740992.0) ? (unsigned long long)f : 0ull;
+            t[b] = (f < 9007199254740992.0 && (double)fx == f) ? fx : (1ull << 53);
         }
         memcpy(&lute[(size_t)i * lut_n], t.data(), lut_n * sizeof(unsigned long long));
     }
