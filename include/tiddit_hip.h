@@ -381,6 +381,30 @@ int tdt_region_counts_packed(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contig
 int tdt_region_counts_packed_device(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *d_queries,
                                     size_t nq, int min_q, int64_t max_ins, int64_t *d_out);
 
+/* ---- order statistics for the depth fold-changes of genotyped sites (TIDDIT_GENOTYPE_DEPTH) ------------ *
+ * cov / gc are the concatenated float64 coverage bins / int8 GC bins (n of them, n < 2^31 - 1; coverage is non-negative, -0.0 reads
+ * as +0.0).  Radix select on the bit patterns (csrc/tdt_depth.hip): lower / upper are the two middle order statistics (equal for an
+ * odd count, 0 for an empty selection), count the number of values selected — numpy.median is numpy.mean([lower, upper]).
+ * tdt_window_medians: table = int64[nq][6] rows {off, first1, last1, first2, last2, cls}: the bins off + first1 .. off + last1 and
+ * off + first2 .. off + last2 (inclusive; {-1, -1} = no such range) as ONE set, of which the bins with gc != -1 are selected (zero
+ * coverage counts).  cls == -1: the values are cov[bin]; 0 <= cls < ncls: the values are class_med[cls][gc[bin]] (class_med =
+ * float64[ncls][101], e.g. tdt_gc_class_medians' medians) and a bin whose entry is NaN is not selected either.  Windows of at most
+ * DP_WINDOW_LIMIT bins are answered by one wavefront each, all in one launch; longer ones by one workgroup each in a second.
+ * Refused before anything is launched: a null or misaligned (8 bytes) pointer and first > last (TDT_E_ARG), an offset, bin or class
+ * row outside the arrays (TDT_E_RANGE); nq == 0 returns TDT_OK whatever the pointers.  tdt_window_medians_device: everything in HBM;
+ * the kernel makes the range checks — a refused window gets zeros and the call returns TDT_E_RANGE naming the first one.
+ * tdt_gc_class_medians: seg = int64[nseg][2] {offset, bins} (a HOST array in both entries); for segment s and class g = 0 .. 100
+ * the values { cov[i] : gc[i] == g and cov[i] > 0 }; outputs [nseg][101].  One workgroup per segment and middle, a [101][256]
+ * histogram in LDS, 8 passes over the segment.  All four synchronise the context's stream before they return. */
+int tdt_window_medians(tdt_ctx *ctx, const double *cov, const int8_t *gc, int64_t n, const int64_t *table, size_t nq, const double *class_med,
+                       int ncls, double *lower, double *upper, int64_t *count);
+int tdt_window_medians_device(tdt_ctx *ctx, const double *d_cov, const int8_t *d_gc, int64_t n, const int64_t *d_table, size_t nq,
+                              const double *d_class_med, int ncls, double *d_lower, double *d_upper, int64_t *d_count);
+int tdt_gc_class_medians(tdt_ctx *ctx, const double *cov, const int8_t *gc, int64_t n, const int64_t *seg, int nseg, double *lower,
+                         double *upper, int64_t *count);
+int tdt_gc_class_medians_device(tdt_ctx *ctx, const double *d_cov, const int8_t *d_gc, int64_t n, const int64_t *seg, int nseg,
+                                double *d_lower, double *d_upper, int64_t *d_count);
+
 /* ---- link counts of SV sites (TIDDIT_GENOTYPE) ------------------------------------------------------- *
  * How many signals of the cluster table join the two regions of a site: for site {bucket, startA, endA, startB, endB} the rows of
  * that (chrA, chrB) bucket with startA <= posA <= endA and startB <= posB <= endB, counted per kind — out[0] the discordant pairs

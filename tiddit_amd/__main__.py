@@ -195,6 +195,11 @@ def run_sv(args, version):
         print("error, TIDDIT_COV_TRACK={}: {}".format(os.environ.get("TIDDIT_COV_TRACK"), e))
         quit()
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
+    genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
+    if genotype_depth and sites_path is None:
+        # (before anything is read or made: no {o}_tiddit is left behind)
+        print("error, TIDDIT_GENOTYPE_DEPTH=1 annotates the sites of TIDDIT_GENOTYPE=sites.vcf, which is not set")
+        sys.exit(1)
     if not args.skip_assembly:
         print("error, local assembly is outside this build's scope; rerun with --skip_assembly")
         quit()
@@ -364,7 +369,8 @@ def run_sv(args, version):
             bamio.set_carry(None)                            # (nor the batches and the reader the statistics kept for the scan)
             print("error, TIDDIT_GENOTYPE={}: {}".format(sites_path, e))
             sys.exit(1)
-        genotype_job = {"path": sites_path, "meta": meta, "records": records, "sites": sites, "rules": rules, "sites (host)": time.time() - t}
+        genotype_job = {"path": sites_path, "meta": meta, "records": records, "sites": sites, "rules": rules, "sites (host)": time.time() - t,
+                        "depth": genotype_depth}
     if gc_job is not None and gc_mode != "after":
         start_gc()              # (the N-rank job and TIDDIT_GC_OVERLAP=scan: beside the scan only)
 
@@ -555,7 +561,7 @@ def genotype_stage(job, args, prefix, samples, library, coverage_data, bam_heade
         links = tiddit_genotype.links_of_tables(tables, library["mp"], args.min_contig)
         T["  links handle (cluster table, upload + sort)"] = time.time() - t
         columns = tiddit_genotype.genotype_sites(store, links, job["sites"], args, library, coverage_data, gc_dictionary, min_mapq, max_ins_len,
-                                                 contig_number=contig_number, rules=job["rules"])
+                                                 contig_number=contig_number, rules=job["rules"], depth=job["depth"])
     finally:
         if links is not None:
             links.close()
@@ -563,8 +569,9 @@ def genotype_stage(job, args, prefix, samples, library, coverage_data, bam_heade
             store.close()
     T.update({"  " + k: v for k, v in tiddit_genotype.STAGE_SECONDS.items()})
     t = time.time()
-    head = tiddit_genotype.header(tiddit_vcf_header.main(bam_header, library, sample_id, version), job["meta"], job["path"], max_ins_len)
-    tiddit_genotype.write_vcf(prefix + ".genotyped.vcf", head, job["records"], columns)
+    head = tiddit_genotype.header(tiddit_vcf_header.main(bam_header, library, sample_id, version), job["meta"], job["path"], max_ins_len,
+                                  depth=job["depth"])
+    tiddit_genotype.write_vcf(prefix + ".genotyped.vcf", head, job["records"], columns, depth=job["depth"])
     T["  header + file"] = time.time() - t
     missed = job["rules"].count("missed")
     STAGE_NOTES["sites genotyped"] = len(columns)

@@ -103,6 +103,10 @@ SYMBOLS = {
     "tdt_sigtab_regroup_result": (_i, [_P] * 11),
     "tdt_masked_medians": (_i, [_P, _P, _P, _P, _i, _P, _P, _P]),
     "tdt_masked_medians_parts": (_i, [_P, _P, _P, _P, _i, _P, _P, _P]),
+    "tdt_window_medians": (_i, [_P, _P, _P, _i64, _P, _sz, _P, _i, _P, _P, _P]),
+    "tdt_window_medians_device": (_i, [_P, _P, _P, _i64, _P, _sz, _P, _i, _P, _P, _P]),
+    "tdt_gc_class_medians": (_i, [_P, _P, _P, _i64, _P, _i, _P, _P, _P]),
+    "tdt_gc_class_medians_device": (_i, [_P, _P, _P, _i64, _P, _i, _P, _P, _P]),
     "tdt_segment_means": (_i, [_P, _P, _P, _i64, _P, _P, _P, _sz, _P, _P]),
     "tdt_segment_means_device": (_i, [_P, _P, _P, _P, _P, _P, _sz, _P, _P]),
     "tdt_region_counts": (_i, [_P] * 9 + [_sz, _i, _i64, _P, _P, _P, _sz, _i, _i64, _P]),

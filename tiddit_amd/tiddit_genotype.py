@@ -25,13 +25,16 @@ orients them — with ``startA <= posA <= endA`` and ``startB <= posB <= endB``.
 before it is sent; a window-rule site on one contig is sent with its lower breakpoint as A, the order of a pair's two reads.
 
 CN, GT and the number formats are ``tiddit_variant``'s (``copy_number``, ``genotype_of`` with n_contigs = 0, ``depth_genotype`` by the
-input's SVTYPE, ``_sample_column``); the SV type is the input's, sites are not retyped."""
+input's SVTYPE, ``_sample_column``); the SV type is the input's, sites are not retyped.
+
+``TIDDIT_GENOTYPE_DEPTH=1`` appends ``DHFC:DHBFC:DHFFC`` to FORMAT and to every column: the site's depth fold-changes against the
+contig, the bins of equal GC content and the flanks (``tiddit_depth``); the eight sub-fields in front of them do not change."""
 import ctypes
 import re
 
 import numpy
 
-from . import _native, tiddit_variant
+from . import _native, tiddit_depth, tiddit_variant
 
 STAGE_SECONDS = {}
 _BND = re.compile(r"^(?:[A-Za-z.]+([\[\]])(?P<c1>[^\[\]]+):(?P<p1>[0-9]+)\1|([\[\]])(?P<c2>[^\[\]]+):(?P<p2>[0-9]+)\4[A-Za-z.]+)$")
@@ -165,9 +168,13 @@ def sample_column(site, regions, cov_between, dv, rv, args, library):
     return tiddit_variant._sample_column(GT, cn, sd, dv, rv)
 
 
-def sample_columns(sites, regions, means, counts, args, library):
-    """every site's column; means[i] = cov_between of site i, counts[i] = (DV, RV)"""
-    return [sample_column(s, regions, means[i], int(counts[i][0]), int(counts[i][1]), args, library) for i, s in enumerate(sites)]
+def sample_columns(sites, regions, means, counts, args, library, depth=None):
+    """every site's column; means[i] = cov_between of site i, counts[i] = (DV, RV), depth[i] = its (DHFC, DHBFC, DHFFC) strings
+    (tiddit_depth.depth_fields; None: the eight sub-fields alone)"""
+    cols = [sample_column(s, regions, means[i], int(counts[i][0]), int(counts[i][1]), args, library) for i, s in enumerate(sites)]
+    if depth is not None:
+        cols = [c + ":" + ":".join(d) for c, d in zip(cols, depth)]
+    return cols
 
 
 # ---- link counts on the device ------------------------------------------------------------------------------------------------
@@ -248,9 +255,10 @@ def _lower_first(sites, rules):
     return out
 
 
-def genotype_sites(store, links, sites, args, library, coverage_data, gc, min_mapq, max_ins_len, contig_number=None, rules=None):
+def genotype_sites(store, links, sites, args, library, coverage_data, gc, min_mapq, max_ins_len, contig_number=None, rules=None, depth=False):
     """-> the sample column of every site.  store: the evidence store (tiddit_region.EvidenceStore); links: :class:`Links` with its
-    bucket map; rules[i]: the rule site i took (:func:`sites_of`; default: all "regions").  Two launches: the region counts, the link counts."""
+    bucket map; rules[i]: the rule site i took (:func:`sites_of`; default: all "regions").  Two launches: the region counts, the link counts.
+    depth: the columns end with the depth fold-changes (tiddit_depth.depth_fields)."""
     import time
     from . import tiddit_region
     T = STAGE_SECONDS
@@ -271,15 +279,24 @@ def genotype_sites(store, links, sites, args, library, coverage_data, gc, min_ma
     sent = sites if rules is None else _lower_first(sites, rules)
     counts = links.count(link_rows(sent, links.bucket, contig_number))
     T["link counts (device, one launch)"] = time.time() - t
+    fields = None
+    if depth:
+        t = time.time()
+        fields = tiddit_depth.depth_fields(sites, coverage_data, gc)
+        T["depth fold-changes (device)"] = time.time() - t
     t = time.time()
-    cols = sample_columns(sites, regions, means, counts, args, library)
+    cols = sample_columns(sites, regions, means, counts, args, library, depth=fields)
     T["column text (host)"] = time.time() - t
     return cols
 
 
-def header(vcf_header, meta, path, max_ins_len):
+def format_col(depth=False):
+    return tiddit_variant.FORMAT_COL + (":" + tiddit_depth.FORMAT_COL if depth else "")
+
+
+def header(vcf_header, meta, path, max_ins_len, depth=False):
     """this sample's header (tiddit_vcf_header.main) with the input's ##INFO / ##ALT / ##FILTER lines whose ID it lacks and the
-    ##TIDDITgenotype line in front of the #CHROM line"""
+    ##TIDDITgenotype line in front of the #CHROM line; depth: the three ##FORMAT lines of the fold-changes in front of that line"""
     lines = vcf_header.split("\n")
     chrom = next(i for i, l in enumerate(lines) if l.startswith("#CHROM"))
     ident = re.compile(r"^##(INFO|ALT|FILTER)=<ID=([^,>]+)")
@@ -291,11 +308,14 @@ def header(vcf_header, meta, path, max_ins_len):
             have.add(m.groups())
             extra.append(l)
     note = "##TIDDITgenotype=<sites={},window=\"REGIONA/REGIONB of the record, else pos-{w}..pos+{w} clipped to 1..contig length\">".format(path, w=int(max_ins_len))
+    if depth:
+        extra = extra + list(tiddit_depth.FORMAT_LINES)
     return "\n".join(lines[:chrom] + extra + [note] + lines[chrom:])
 
 
-def write_vcf(path, head, records, columns):
+def write_vcf(path, head, records, columns, depth=False):
+    fmt = format_col(depth)
     with open(path, "w") as f:
         f.write(head + "\n")
         for (_, cols), col in zip(records, columns):
-            f.write("\t".join(cols[:8] + [tiddit_variant.FORMAT_COL, col]) + "\n")
+            f.write("\t".join(cols[:8] + [fmt, col]) + "\n")
