@@ -186,6 +186,43 @@ def test_call_to_call_state_on_one_context(nat):
             own.close()
 
 
+def test_callers_of_the_tile_pass_share_one_state(nat):
+    """The tile-resident pass has ONE driver and ONE layout of its per-call arrays for tdt_dbscan_device and tdt_dbscan_y: what one of
+    them leaves behind (codes, group sums, the status word) is what the other finds.  One fresh context, 3 * DT_T points (three tiles,
+    two seams): caller-labels, several buckets, caller-labels, one bucket, one bucket falling through to route 2 (ONE cluster of all
+    points), caller-labels — every call compared exactly with the reference.  Then the same on a second fresh context after one extra
+    one-bucket call: every call on the other parity of the group sums."""
+    n = 3 * cc.DT_T
+    x, y, _, _ = cc.build_layout([("c", 100)] * (n // 101) + [("g", n % 101)], 3, seed=1)
+    lab = cc._case("labels", "E", x, y, cc.EPS, 3, entries=["device"])
+    cut = cc._case("buckets", "E", x, y, cc.EPS, 3, off=[0, cc.DT_T - 3, cc.DT_T - 3, 2 * cc.DT_T + 50, n], entries=["device"])
+    one = cc._case("one_cluster", "E", np.arange(n), np.zeros(n), cc.EPS, 3, entries=["device"])
+    assert lab["n"] == n and cut["nb"] == 4 and cc.properties(one)["largest"] > cc.DB_SMALL
+    xl, xid = cc.reference(lab, mode=1)
+    want = {c["name"]: cc.reference(c) for c in (lab, cut, one)}
+    data = np.ascontiguousarray(np.stack([x, y], 1))
+
+    def caller_labels(own):
+        got, last = xl.copy(), ctypes.c_int64(-7)
+        nat.check(own.lib.tdt_dbscan_y(own.handle, nat.ptr(data), n, 2, float(cc.EPS), 3, int(xid[0]), nat.ptr(got), ctypes.byref(last)))
+        return got, np.array([last.value], dtype=np.int64)
+
+    def device(c):
+        return lambda own: device_call(nat, own, c["x"], c["y"], c["off"], c["eps"], c["m"], 0)
+
+    calls = [("labels", caller_labels), ("buckets", device(cut)), ("labels", caller_labels), ("labels", device(lab)),
+             ("one_cluster", device(one)), ("labels", caller_labels)]
+    for prefix in ([], [("labels", device(lab))]):
+        own = nat.Context(0)
+        try:
+            for step, (name, call) in enumerate(prefix + calls):
+                got, last = call(own)
+                assert _first_bad(got, want[name][0]) is None, (len(prefix), step, name, _first_bad(got, want[name][0]))
+                assert np.array_equal(last, want[name][1]), (len(prefix), step, name, last, want[name][1])
+        finally:
+            own.close()
+
+
 def test_too_large_cluster_after_a_caller_labels_call(nat):
     """The reduced form of what b_mixed_4095_m3 met after the caller-labels calls of family A: the members of a cluster too large for
     the tile-resident pass get no code, so its finish kernel decodes what an earlier call left in the code array before the call

@@ -1,5 +1,6 @@
 // Internal shared definitions for libtiddit_hip.so (gfx950 only; no portability layer).
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -64,6 +65,53 @@ static inline int tdt_ceil_log2_u64(uint64_t v) {
     int l = 0;
     while ((1ull << l) < v) l++;
     return l;
+}
+
+// ---- one description of a workspace serves its size AND its pointers.  A layout is a struct of pointers with a
+// `size_t lay(void *base, ...)` that takes its arrays from a tdt_carver in order and returns the carver's size: run on a null base it
+// only measures, run on the allocation it hands the pointers out (tdt_scratch_layout does both), so the two cannot disagree.
+struct tdt_carver {
+    char *base;
+    size_t size = 0;
+    explicit tdt_carver(void *b) : base((char *)b) {}
+    template <class T> T *take(size_t count) {             // `count` elements of T, starting on a 256-byte boundary
+        T *r = base ? (T *)(base + size) : nullptr;
+        size += (count * sizeof(T) + 255) & ~(size_t)255;
+        return r;
+    }
+};
+template <class L, class... A> static inline int tdt_scratch_layout(tdt_ctx *ctx, int slot, L &l, A... a) {
+    void *base = nullptr;
+    const int rc = tdt_scratch(ctx, slot, l.lay(nullptr, a...), &base);
+    if (rc == TDT_OK) l.lay(base, a...);
+    return rc;
+}
+
+// ---- internal entry points used across translation units
+// tdt_sort.hip.  Stable sort of n (u64 key, u32 value) pairs by the key bits set in `bitmask`.  PRECONDITION: the key bits outside the
+// mask are equal in all keys (callers pass tdt_sort_mask of what can differ) — and the sort relies on it: when no mask bit lies above
+// bit 31 and more than one digit is sorted (narrow mode), the keys travel as 32-bit words between the first and the last digit and the
+// high word of every output key is rebuilt from keys[0].  keys/vals and the *_tmp buffers ping-pong; where the result lies comes back
+// through out_keys / out_vals.
+int tdt_radix_sort_pairs(tdt_ctx *ctx, unsigned long long *keys, unsigned *vals, unsigned long long *keys_tmp, unsigned *vals_tmp,
+                         size_t n, unsigned long long bitmask, unsigned long long **out_keys, unsigned **out_vals);
+// the bits that can differ among keys `hi << 32 | lo` with lo < lo_values <= 2^32 and hi < hi_values <= 2^31
+static inline unsigned long long tdt_sort_mask(uint64_t lo_values, uint64_t hi_values) {
+    return ((1ull << tdt_ceil_log2_u64(lo_values)) - 1ull) | (((1ull << tdt_ceil_log2_u64(hi_values)) - 1ull) << 32);
+}
+// tdt_dbscan.hip.  In-place inclusive scan of d_v[0..n); d_tsum: ceil(n / 1024) words of scratch.
+int tdt_scan_u32_inclusive(tdt_ctx *ctx, unsigned *d_v, int n, unsigned *d_tsum);
+
+// ---- what every clustering entry of host int64 columns applies: device coordinates are uint32 offsets from the column minimum
+static inline int tdt_check_span(const char *who, int64_t lo, int64_t hi) {
+    if ((unsigned __int128)((__int128)hi - lo) <= 0xfffffffeull) return TDT_OK;
+    tdt_set_error("%s: coordinate span >= 2^32 is outside the device path's domain", who);
+    return TDT_E_UNSUPPORTED;
+}
+// ... and eps as the integer bound of the window test.  numpy: int64 distance < python number  <=>  d < ceil(eps) for integer d >= 0
+static inline uint64_t tdt_eps_u64(double eps) {
+    if (!(eps > 0)) return 0;  // also NaN: nothing is ever < NaN
+    return eps >= 8589934592.0 ? 1ull << 33 : (uint64_t)ceil(eps);
 }
 
 #include "tdt_cov_record.h"      // the 8-byte coverage records (packed / binned): their own header, so that the profiles know when they changed

@@ -42,8 +42,6 @@ const char *const tdt_variant_dbscan = ""
 #define DB_TILE (DB_THREADS * DB_ITEMS)
 #define DB_SMALL 128  // x-clusters up to this many members are y-sorted by in-kernel rank counting
 
-int tdt_radix_sort_pairs(tdt_ctx *ctx, unsigned long long *keys, unsigned *vals, unsigned long long *keys_tmp, unsigned *vals_tmp,
-                         size_t n, unsigned long long bitmask, unsigned long long **out_keys, unsigned **out_vals);   // tdt_sort.hip
 
 // The bucket of position i when the wave's lanes hold positions inside [first, last] (first / last the same in every lane): the search
 // is done ONCE, on the scalar unit, for `first`; a wave of 64-128 consecutive positions almost never contains a bucket boundary (300
@@ -373,9 +371,7 @@ __global__ __launch_bounds__(DB_THREADS) void dby_final(const int *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------ host
-static inline size_t db_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-static int db_scan_inplace(tdt_ctx *ctx, unsigned *d_v, int n, unsigned *d_tsum) {
+int tdt_scan_u32_inclusive(tdt_ctx *ctx, unsigned *d_v, int n, unsigned *d_tsum) {
     const int nt = (n + DB_TILE - 1) / DB_TILE;
     hipLaunchKernelGGL(scan_reduce, dim3(nt), dim3(DB_THREADS), 0, ctx->stream, (const unsigned *)d_v, n, d_tsum);
     hipLaunchKernelGGL(scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, d_tsum, nt);
@@ -384,34 +380,337 @@ static int db_scan_inplace(tdt_ctx *ctx, unsigned *d_v, int n, unsigned *d_tsum)
     return TDT_OK;
 }
 
-int tdt_scan_u32_inclusive(tdt_ctx *ctx, unsigned *d_v, int n, unsigned *d_tsum) { return db_scan_inplace(ctx, d_v, n, d_tsum); }
+// ---- the pinned status block of the context, {value, sequence number}: one word back from the device without a stream
+// synchronisation (a hipStreamSynchronize wake-up costs ~40 us, a third of a 5 M-point pass).  The host picks a sequence number and
+// clears the block (db_word_arm), a kernel of the pass stores the value, a system fence and then the number (dt_signal_host,
+// db_signal_host), and the host spins on the number (db_word_wait).
+struct DbHostWord {
+    volatile unsigned *w = nullptr;
+    unsigned seq = 0;
+};
 
-// y-sort of the clusters larger than DB_SMALL (runs only when dby_rank flagged any)
-static int db_sort_large(tdt_ctx *ctx, const int *d_xlab, const unsigned *d_y, int n, unsigned *d_lflag, unsigned *d_tsum,
-                         unsigned long long *d_k0, unsigned long long *d_k1, unsigned *d_v0, unsigned *d_v1, unsigned *d_cpos,
-                         unsigned *d_ys, unsigned *d_ord) {
+static int db_word_arm(tdt_ctx *ctx, DbHostWord *hw) {
+    static std::atomic<unsigned> counter{0};
+    void *hp = nullptr;
+    const int rc = tdt_pinned(ctx, 2, 64, &hp);
+    if (rc) return rc;
+    hw->w = (volatile unsigned *)hp;
+    hw->seq = ++counter;
+    if (hw->seq == 0) hw->seq = ++counter;              // never 0: that is what the block is cleared to
+    hw->w[1] = 0;
+    return TDT_OK;
+}
+
+static int db_word_wait(tdt_ctx *ctx, const DbHostWord &hw, unsigned *value) {
+    bool seen = false;
+    for (long spin = 0; spin < 4000000; spin++) {       // a few milliseconds at most, then the ordinary wait
+        if (hw.w[1] == hw.seq) {
+            seen = true;
+            break;
+        }
+        __builtin_ia32_pause();
+    }
+    if (!seen) TDT_HIP(hipStreamSynchronize(ctx->stream));
+    *value = hw.w[0];
+    return TDT_OK;
+}
+
+// ---- workspaces (tdt_carver: size and pointers from the one list)
+// slot 3: the bucket offsets and everything routes 2 and 3 keep per point.  Every call asks for it up front, whichever route it
+// takes, so the buffers a context holds after a call do not depend on the route.
+struct DbWork {
+    int *boff;
+    unsigned *runbase, *cnt, *tsum;
+    unsigned char *px, *py;
+    unsigned *sx, *sy, *ex;
+    int *xlab, *seg0, *seg1;
+    unsigned *ys, *ord;
+    unsigned long long *key, *ksorted;           // the large clusters' sort: keys in / out, values in / out, positions, flags
+    unsigned *v0, *v1, *cpos, *lflag;
+    size_t lay(void *base, int n, int nb) {
+        tdt_carver c(base);
+        const size_t N = (size_t)(n ? n : 1);
+        boff = c.take<int>((size_t)nb + 1), runbase = c.take<unsigned>((size_t)nb + 1), cnt = c.take<unsigned>(64);
+        tsum = c.take<unsigned>((N + DB_TILE - 1) / DB_TILE);
+        px = c.take<unsigned char>(N), py = c.take<unsigned char>(N);
+        sx = c.take<unsigned>(N), sy = c.take<unsigned>(N), ex = c.take<unsigned>(N);
+        xlab = c.take<int>(N), seg0 = c.take<int>(N), seg1 = c.take<int>(N);
+        ys = c.take<unsigned>(N), ord = c.take<unsigned>(N);
+        key = c.take<unsigned long long>(N), ksorted = c.take<unsigned long long>(N);
+        v0 = c.take<unsigned>(N), v1 = c.take<unsigned>(N), cpos = c.take<unsigned>(N), lflag = c.take<unsigned>(N);
+        return c.size;
+    }
+};
+
+// slot 20: what the tile-resident pass keeps from call to call — the status block its kernels re-zero themselves and the two
+// group-sum arrays that alternate by call parity.  A fixed size, so the block never moves once it exists.
+struct DtState {
+    unsigned *flags, *grp[2];
+    size_t lay(void *base) {
+        tdt_carver c(base);
+        flags = c.take<unsigned>(64), grp[0] = c.take<unsigned>((size_t)2 * DT_GRPMAX), grp[1] = c.take<unsigned>((size_t)2 * DT_GRPMAX);
+        return c.size;
+    }
+};
+
+// slot 21: the tile-resident pass's arrays of one call.  ONE layout for every caller: the finish kernel of a pass that does not
+// stand decodes whatever an earlier call left in `code`.
+struct DtWork {
+    unsigned short *code;
+    unsigned *brun, *bext, *aggR, *aggE, *runbase, *extbase;
+    size_t lay(void *base, int n, int nb) {
+        tdt_carver c(base);
+        const size_t ntt = ((size_t)n + DT_T - 1) / DT_T;
+        code = c.take<unsigned short>((size_t)n + 8);
+        brun = c.take<unsigned>((size_t)nb + 1), bext = c.take<unsigned>((size_t)nb + 1);
+        aggR = c.take<unsigned>(ntt), aggE = c.take<unsigned>(ntt);
+        runbase = c.take<unsigned>((size_t)nb + 1), extbase = c.take<unsigned>((size_t)nb + 1);
+        return c.size;
+    }
+};
+
+// slot 8: the ballot masks of route 2.  Whole tiles: its kernels store all 64 words of their tile (+ 2 guard words).
+struct DbfWork {
+    DbfCtl *ctl;
+    ull *agg_x, *agg_1, *agg_2, *PM, *PY, *HM, *BM, *EM, *S1M, *FM;
+    size_t lay(void *base, int ntf) {
+        tdt_carver c(base);
+        const size_t nw = (size_t)ntf * DBF_WORDS + 2;
+        ctl = c.take<DbfCtl>(1);
+        agg_x = c.take<ull>(ntf), agg_1 = c.take<ull>(ntf), agg_2 = c.take<ull>(ntf);
+        PM = c.take<ull>(nw), PY = c.take<ull>(nw), HM = c.take<ull>(nw), BM = c.take<ull>(nw);
+        EM = c.take<ull>(nw), S1M = c.take<ull>(nw), FM = c.take<ull>(nw);
+        return c.size;
+    }
+};
+
+// ---- route 1: the tile-resident pass (tdt_dbscan_tile.h) — dbt_tile, then dbt_finish1 (one bucket) or dbt_scan + dbt_finish.
+// The one driver of both its users: tdt_dbscan_device, and tdt_dbscan_y_device with caller-supplied x labels in place of x (d_xlab
+// non-null: one bucket, extra sub-runs numbered from id_base).  d_boff is read by the kernels for nb > 1 only.
+// *stands == false: an x-cluster was too large for this pass — the labels were NOT produced and the caller takes another route.
+// Only one-bucket calls (caller-labels calls are such) use the group sums, so only they flip the parity of ctx->tile_calls.
+static int db_tile_pass(tdt_ctx *ctx, const unsigned *d_x, const unsigned *d_y, int n, const int *d_boff, int nb, uint64_t eps, int m,
+                        int mode, const int *d_xlab, long long id_base, double *d_labels, long long *d_last_id, bool *stands) {
     hipStream_t st = ctx->stream;
-    int rc = db_scan_inplace(ctx, d_lflag, n, d_tsum);
+    const int ntt = (n + DT_T - 1) / DT_T;
+    DtState S;
+    DtWork W;
+    int rc = tdt_scratch_layout(ctx, 20, S);
     if (rc) return rc;
-    unsigned nl = 0;
-    TDT_HIP(hipMemcpyAsync(&nl, d_lflag + (n - 1), 4, hipMemcpyDeviceToHost, st));
-    TDT_HIP(hipStreamSynchronize(st));
-    if (!nl) return TDT_OK;
-    const int blocks1 = (n + DB_THREADS - 1) / DB_THREADS;
-    hipLaunchKernelGGL(dby_large_compact, dim3(blocks1), dim3(DB_THREADS), 0, st, d_xlab, d_y, n, (const unsigned *)d_lflag, d_k0, d_v0, d_cpos);
+    rc = tdt_scratch_layout(ctx, 21, W, n, nb);
+    if (rc) return rc;
+    if (ctx->tile_flags_zeroed != S.flags) {       // first use of this block; afterwards the kernel that reports the status re-zeroes it
+        TDT_HIP(hipMemsetAsync(S.flags, 0, DtState().lay(nullptr), st));
+        ctx->tile_flags_zeroed = S.flags;
+    }
+    const bool odd = nb == 1 && (ctx->tile_calls++ & 1u) != 0;
+    DtParams TP;
+    TP.x = d_xlab ? (const unsigned *)d_xlab : d_x, TP.y = d_y, TP.n = n;
+    TP.boff = d_boff, TP.nb = nb;
+    TP.eps32 = eps > 0xffffffffull ? 0xffffffffu : (unsigned)eps, TP.wide = eps > 0xffffffffull, TP.m = m;
+    TP.code = W.code, TP.aggR = W.aggR, TP.aggE = W.aggE, TP.brun = W.brun, TP.bext = W.bext;
+    TP.flags = S.flags, TP.grp = S.grp[odd];
+    DbHostWord hw;
+    rc = db_word_arm(ctx, &hw);
+    if (rc) return rc;
+    if (d_xlab) hipLaunchKernelGGL((dbt_tile<true, false, true>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
+    else if (nb == 1 && mode == 0) hipLaunchKernelGGL((dbt_tile<true, false>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
+    else if (nb == 1) hipLaunchKernelGGL((dbt_tile<true, true>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
+    else if (mode == 0) hipLaunchKernelGGL((dbt_tile<false, false>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
+    else hipLaunchKernelGGL((dbt_tile<false, true>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
     TDT_CHECK_LAUNCH();
-    unsigned long long mask = 0xffffffffull;                                 // y: all 32 bits
-    mask |= ((1ull << tdt_ceil_log2_u64((uint64_t)n + 1)) - 1ull) << 32;     // cluster id < number of runs <= n
-    unsigned long long *ks = nullptr;
-    unsigned *vs = nullptr;
-    rc = tdt_radix_sort_pairs(ctx, d_k0, d_v0, d_k1, d_v1, nl, mask, &ks, &vs);
+    // the kernel behind dbt_tile stores the word that says whether the pass stands as soon as the tile kernel is done
+    if (nb == 1) {
+        ctx->tile_groups_max = std::max(ctx->tile_groups_max, (ntt + DT_GRP - 1) / DT_GRP);
+        hipLaunchKernelGGL(dbt_finish1, dim3((ntt + DT_FTPB - 1) / DT_FTPB), dim3(256), 0, st, (const unsigned short *)W.code, d_labels, n, d_xlab,
+                           (const unsigned *)W.aggR, (const unsigned *)W.aggE, ntt, (const unsigned *)TP.grp, S.grp[!odd], ctx->tile_groups_max,
+                           d_last_id, id_base, d_xlab ? 1 : 0, S.flags, hw.w, hw.seq);
+    } else {
+        hipLaunchKernelGGL(dbt_scan, dim3(1), dim3(1024), 0, st, W.aggR, W.aggE, ntt, d_boff, nb, n, (const unsigned *)W.brun,
+                           (const unsigned *)W.bext, W.runbase, W.extbase, d_last_id, mode, S.flags, hw.w, hw.seq);
+        hipLaunchKernelGGL(dbt_finish, dim3((n + 1023) / 1024), dim3(256), 0, st, (const unsigned short *)W.code, d_labels, n, (const unsigned *)W.aggR,
+                           (const unsigned *)W.aggE, d_boff, nb, (const unsigned *)W.runbase, (const unsigned *)W.extbase);
+    }
+    TDT_CHECK_LAUNCH();
+    unsigned too_large = 0;
+    rc = db_word_wait(ctx, hw, &too_large);
+    *stands = too_large == 0;
+    return rc;
+}
+
+// ---- what one tdt_dbscan_device call works on: its arguments, the arrays of slot 3, and whether the bucket offsets are uploaded yet
+struct DbCall {
+    tdt_ctx *ctx;
+    const unsigned *x, *y;
+    int n;
+    const int64_t *bucket_off;
+    int nb;
+    unsigned long long eps;
+    int m, mode;
+    double *labels;
+    long long *last_id;
+    DbWork w;
+    bool staged;                     // db_stage_buckets has run
+    int blocks1() const { return n ? (n + DB_THREADS - 1) / DB_THREADS : 1; }            // a thread per point
+    int blocks_nb() const { return (std::max(n, nb) + DB_THREADS - 1) / DB_THREADS; }    // ... or per bucket, whichever are more
+};
+
+// bucket offsets to the device, staged through pinned memory so that the copy is truly asynchronous; run bases and counters zeroed.
+// (Not needed by the one-bucket tile-resident pass, which therefore never waits for the stream.)
+static int db_stage_buckets(DbCall &c) {
+    if (c.staged) return TDT_OK;
+    c.staged = true;
+    hipStream_t st = c.ctx->stream;
+    const size_t bytes = (size_t)(c.nb + 1) * 4;
+    void *h_stage = nullptr;
+    const int rc = tdt_pinned(c.ctx, 0, bytes + 64, &h_stage);
     if (rc) return rc;
-    hipLaunchKernelGGL(dby_large_scatter, dim3((nl + DB_THREADS - 1) / DB_THREADS), dim3(DB_THREADS), 0, st, (const unsigned long long *)ks,
-                       (const unsigned *)vs, (const unsigned *)d_cpos, (int)nl, d_ys, d_ord);
+    TDT_HIP(hipStreamSynchronize(st));  // previous call may still be reading the pinned block
+    int *h_boff = (int *)h_stage;
+    for (int b = 0; b <= c.nb; b++) h_boff[b] = (int)c.bucket_off[b];
+    TDT_HIP(hipMemcpyAsync(c.w.boff, h_boff, bytes, hipMemcpyHostToDevice, st));
+    TDT_HIP(hipMemsetAsync(c.w.runbase, 0, bytes, st));
+    TDT_HIP(hipMemsetAsync(c.w.cnt, 0, 256, st));
+    return TDT_OK;
+}
+
+// the x-only result from the x labels of route 2 or 3 (n_labelled = 0: an empty input, every bucket reports cluster_id -1)
+static int db_x_result(const DbCall &c, int n_labelled) {
+    hipLaunchKernelGGL(dbx_final, dim3(c.blocks_nb()), dim3(DB_THREADS), 0, c.ctx->stream, (const int *)c.w.xlab, n_labelled, (const int *)c.w.boff,
+                       c.nb, (const unsigned *)c.w.runbase, c.labels, c.last_id);
     TDT_CHECK_LAUNCH();
     return TDT_OK;
 }
 
+// y-sort of the clusters larger than DB_SMALL (runs only when dby_rank flagged any)
+static int db_sort_large(const DbCall &c) {
+    tdt_ctx *ctx = c.ctx;
+    hipStream_t st = ctx->stream;
+    const DbWork &w = c.w;
+    const int n = c.n;
+    int rc = tdt_scan_u32_inclusive(ctx, w.lflag, n, w.tsum);
+    if (rc) return rc;
+    unsigned nl = 0;
+    TDT_HIP(hipMemcpyAsync(&nl, w.lflag + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    TDT_HIP(hipStreamSynchronize(st));
+    if (!nl) return TDT_OK;
+    hipLaunchKernelGGL(dby_large_compact, dim3(c.blocks1()), dim3(DB_THREADS), 0, st, (const int *)w.xlab, c.y, n, (const unsigned *)w.lflag, w.key, w.v0,
+                       w.cpos);
+    TDT_CHECK_LAUNCH();
+    unsigned long long *ks = nullptr;
+    unsigned *vs = nullptr;
+    // y: all 32 bits; cluster id < number of runs <= n
+    rc = tdt_radix_sort_pairs(ctx, w.key, w.v0, w.ksorted, w.v1, nl, tdt_sort_mask(1ull << 32, (uint64_t)n + 1), &ks, &vs);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dby_large_scatter, dim3((nl + DB_THREADS - 1) / DB_THREADS), dim3(DB_THREADS), 0, st, (const unsigned long long *)ks,
+                       (const unsigned *)vs, (const unsigned *)w.cpos, (int)nl, w.ys, w.ord);
+    TDT_CHECK_LAUNCH();
+    return TDT_OK;
+}
+
+// ---- route 2: ballot-mask tiles (tdt_dbscan_fused.h), cross-tile prefixes from a one-workgroup scan between launches.  Takes what
+// route 1 does not: an x-cluster of more than DB_SMALL members, n >= 0x7fff0000.
+static int db_route_masks(const DbCall &c) {
+    tdt_ctx *ctx = c.ctx;
+    hipStream_t st = ctx->stream;
+    const DbWork &w = c.w;
+    const int n = c.n, nb = c.nb, m = c.m;
+    const int ntf = (n + DBF_TILE - 1) / DBF_TILE;
+    const dim3 grid(ntf), block(DBF_THREADS);
+    DbfWork F;
+    int rc = tdt_scratch_layout(ctx, 8, F, ntf);
+    if (rc) return rc;
+    // (the control word and the three guard words of the mask arrays are zeroed by tile 0 of dbm_x_masks)
+    if (nb == 1 && m <= 4)
+        hipLaunchKernelGGL(dbm_x_masks<true>, grid, block, 0, st, c.x, n, (const int *)w.boff, nb, c.eps, m, F.PM, F.agg_x, F.PY, F.ctl);
+    else
+        hipLaunchKernelGGL(dbm_x_masks<false>, grid, block, 0, st, c.x, n, (const int *)w.boff, nb, c.eps, m, F.PM, F.agg_x, F.PY, F.ctl);
+    if (ntf > DBM_INLINE_PREFIX_MAX) hipLaunchKernelGGL(tile_scan, dim3(1), dim3(1024), 0, st, F.agg_x, ntf);
+    hipLaunchKernelGGL(dbm_x_labels, grid, block, 0, st, (const ull *)F.PM, (const ull *)F.agg_x, n, (const int *)w.boff, nb, m, w.xlab, w.runbase,
+                       w.seg0, w.seg1);
+    TDT_CHECK_LAUNCH();
+    if (c.mode == 1) return db_x_result(c, n);
+    hipLaunchKernelGGL(dby_rank, dim3(c.blocks1()), dim3(DB_THREADS), 0, st, (const int *)w.xlab, c.y, n, (const int *)w.seg0, (const int *)w.seg1,
+                       w.ys, w.ord, w.lflag, &F.ctl->nlarge);
+    TDT_CHECK_LAUNCH();
+    // The y pass is enqueued right away on the assumption that no x-cluster exceeded DB_SMALL members (the
+    // usual case), so the GPU never idles on a mid-pipeline readback; the counter is checked afterwards
+    // and only then are the large clusters sorted and the y pass repeated.
+    for (int attempt = 0; attempt < 2; attempt++) {
+        hipLaunchKernelGGL(dbm_y_masks, grid, block, 0, st, (const int *)w.xlab, (const unsigned *)w.ys, n, (const int *)w.boff, nb, c.eps, m, F.PY,
+                           F.HM, F.BM, F.agg_1);
+        if (ntf > DBM_INLINE_PREFIX_MAX) hipLaunchKernelGGL(tile_scan, dim3(1), dim3(1024), 0, st, F.agg_1, ntf);
+        hipLaunchKernelGGL(dbm_y_mid, grid, block, 0, st, (const ull *)F.PY, (const ull *)F.HM, (const ull *)F.BM, (const ull *)F.agg_1, n, m, F.EM,
+                           F.S1M, F.FM, F.agg_2);
+        if (ntf > DBM_INLINE_PREFIX_MAX) hipLaunchKernelGGL(tile_scan, dim3(1), dim3(1024), 0, st, F.agg_2, ntf);
+        hipLaunchKernelGGL(dbm_y_final, grid, block, 0, st, (const int *)w.xlab, (const unsigned *)w.ord, (const ull *)F.BM, (const ull *)F.EM,
+                           (const ull *)F.S1M, (const ull *)F.FM, (const ull *)F.agg_2, n, (const int *)w.boff, nb, (const unsigned *)w.runbase,
+                           c.labels, c.last_id);
+        TDT_CHECK_LAUNCH();
+        if (attempt == 1) break;
+        DbHostWord hw;
+        rc = db_word_arm(ctx, &hw);
+        if (rc) return rc;
+        hipLaunchKernelGGL(db_signal_host, dim3(1), dim3(1), 0, st, (const unsigned *)&F.ctl->nlarge, hw.w, hw.seq);
+        TDT_CHECK_LAUNCH();
+        unsigned nlarge = 0;
+        rc = db_word_wait(ctx, hw, &nlarge);
+        if (rc) return rc;
+        if (!nlarge) break;
+        rc = db_sort_large(c);
+        if (rc) return rc;
+    }
+    if (c.last_id && nb > 1)
+        hipLaunchKernelGGL(dbf_empty_buckets, dim3((nb + 255) / 256), dim3(256), 0, st, (const int *)w.boff, nb, c.last_id);
+    TDT_CHECK_LAUNCH();
+    return TDT_OK;
+}
+
+// ---- route 3: m > DBF_M_MAX — byte flags, a launch per step, three global scans
+static int db_route_scans(const DbCall &c) {
+    tdt_ctx *ctx = c.ctx;
+    hipStream_t st = ctx->stream;
+    const DbWork &w = c.w;
+    const int n = c.n, nb = c.nb, m = c.m;
+    const dim3 grid1(c.blocks1()), grid4((n + DB_TILE - 1) / DB_TILE), block(DB_THREADS);
+    hipLaunchKernelGGL(dbx_flags, grid4, block, 0, st, c.x, n, (const int *)w.boff, nb, c.eps, m, w.px, w.sx);
+    TDT_CHECK_LAUNCH();
+    int rc = tdt_scan_u32_inclusive(ctx, w.sx, n, w.tsum);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dbx_labels, grid1, block, 0, st, (const unsigned char *)w.px, (const unsigned *)w.sx, n, m, (const int *)w.boff, nb, w.xlab,
+                       w.runbase);
+    TDT_CHECK_LAUNCH();
+    if (c.mode == 1) return db_x_result(c, n);
+    hipLaunchKernelGGL(db_segments, grid1, block, 0, st, (const int *)w.xlab, n, w.seg0, w.seg1);
+    hipLaunchKernelGGL(dby_rank, grid1, block, 0, st, (const int *)w.xlab, c.y, n, (const int *)w.seg0, (const int *)w.seg1, w.ys, w.ord, w.lflag,
+                       w.cnt);
+    TDT_CHECK_LAUNCH();
+    // x-clusters larger than DB_SMALL: one 4-byte readback decides whether the radix sort runs
+    unsigned nlarge = 0;
+    TDT_HIP(hipMemcpyAsync(&nlarge, w.cnt, 4, hipMemcpyDeviceToHost, st));
+    TDT_HIP(hipStreamSynchronize(st));
+    if (nlarge) {
+        rc = db_sort_large(c);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(dby_flags, grid1, block, 0, st, (const int *)w.xlab, n, (const int *)w.seg0, (const int *)w.seg1, (const unsigned *)w.ys, c.eps,
+                       m, w.py, w.sy);
+    TDT_CHECK_LAUNCH();
+    rc = tdt_scan_u32_inclusive(ctx, w.sy, n, w.tsum);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dby_extras, grid1, block, 0, st, (const int *)w.xlab, n, (const int *)w.seg0, (const int *)w.seg1, (const unsigned *)w.sy,
+                       w.ex);
+    TDT_CHECK_LAUNCH();
+    rc = tdt_scan_u32_inclusive(ctx, w.ex, n, w.tsum);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dby_final, dim3(c.blocks_nb()), block, 0, st, (const int *)w.xlab, n, m, (const int *)w.seg0, (const unsigned char *)w.py,
+                       (const unsigned *)w.sy, (const unsigned *)w.ex, (const unsigned *)w.ord, (const int *)w.boff, nb,
+                       (const unsigned *)w.runbase, c.labels, c.last_id);
+    TDT_CHECK_LAUNCH();
+    return TDT_OK;
+}
+
+// validation, the empty input, and the dispatch: route 1 where it applies — and stands —, else route 2, or route 3 for m > DBF_M_MAX
 extern "C" int tdt_dbscan_device(tdt_ctx *ctx, const uint32_t *d_x, const uint32_t *d_y, size_t n_, const int64_t *bucket_off,
                                  int nb, uint64_t eps, int m, int mode, double *d_labels, int64_t *d_last_id) {
     if (!ctx || nb < 1 || !bucket_off || m < 2 || (mode != 0 && mode != 1)) {
@@ -433,303 +732,61 @@ extern "C" int tdt_dbscan_device(tdt_ctx *ctx, const uint32_t *d_x, const uint32
             return TDT_E_ARG;
         }
     TDT_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // small control block first (needed even for n == 0)
-    const size_t sz_boff = db_align((size_t)(nb + 1) * 4);
-    const size_t sz_rb = db_align((size_t)(nb + 1) * 4);
-    const int nt = n ? (n + DB_TILE - 1) / DB_TILE : 1;
-    const size_t N = (size_t)(n ? n : 1);
-    const size_t nlarge_cap = N / DB_SMALL + 1;
-    size_t total = sz_boff + sz_rb + db_align(256) /*counters*/ + db_align((size_t)nt * 4) +
-                   2 * db_align(N) /*px,py*/ + 3 * db_align(N * 4) /*sx,sy,ex*/ + 3 * db_align(N * 4) /*xlab,seg_start,seg_end*/ +
-                   2 * db_align(N * 4) /*ys,ord*/ + 2 * db_align(N * 8) /*sort keys in/out*/ + 4 * db_align(N * 4) /*sort vals, cpos, lflag*/ +
-                   0 * nlarge_cap;
-    void *base = nullptr;
-    int rc = tdt_scratch(ctx, 3, total, &base);
+    DbCall c{ctx, d_x, d_y, n, bucket_off, nb, eps, m, mode, d_labels, (long long *)d_last_id, {}, false};
+    int rc = tdt_scratch_layout(ctx, 3, c.w, n, nb);
     if (rc) return rc;
-    char *p = (char *)base;
-    auto carve = [&](size_t bytes) {
-        void *r = p;
-        p += db_align(bytes);
-        return r;
-    };
-    int *d_boff = (int *)carve((size_t)(nb + 1) * 4);
-    unsigned *d_runbase = (unsigned *)carve((size_t)(nb + 1) * 4);
-    unsigned *d_cnt = (unsigned *)carve(256);
-    unsigned *d_tsum = (unsigned *)carve((size_t)nt * 4);
-    unsigned char *d_px = (unsigned char *)carve(N);
-    unsigned char *d_py = (unsigned char *)carve(N);
-    unsigned *d_sx = (unsigned *)carve(N * 4);
-    unsigned *d_sy = (unsigned *)carve(N * 4);
-    unsigned *d_ex = (unsigned *)carve(N * 4);
-    int *d_xlab = (int *)carve(N * 4);
-    int *d_seg0 = (int *)carve(N * 4);
-    int *d_seg1 = (int *)carve(N * 4);
-    unsigned *d_ys = (unsigned *)carve(N * 4);
-    unsigned *d_ord = (unsigned *)carve(N * 4);
-    unsigned long long *d_key = (unsigned long long *)carve(N * 8);
-    unsigned long long *d_ksorted = (unsigned long long *)carve(N * 8);
-    unsigned *d_v0 = (unsigned *)carve(N * 4);
-    unsigned *d_v1 = (unsigned *)carve(N * 4);
-    unsigned *d_cpos = (unsigned *)carve(N * 4);
-    unsigned *d_lflag = (unsigned *)carve(N * 4);
-
-    // bucket offsets: stage through pinned memory so the copy is truly asynchronous.  (Not needed by the one-bucket tile path,
-    // which therefore never waits for the stream.)
-    bool prologue_done = false;
-    auto prologue = [&]() -> int {
-        if (prologue_done) return TDT_OK;
-        prologue_done = true;
-        void *h_stage = nullptr;
-        int rc2 = tdt_pinned(ctx, 0, (size_t)(nb + 1) * 4 + 64, &h_stage);
-        if (rc2) return rc2;
-        TDT_HIP(hipStreamSynchronize(st));  // previous call may still be reading the pinned block
-        int *h_boff = (int *)h_stage;
-        for (int b = 0; b <= nb; b++) h_boff[b] = (int)bucket_off[b];
-        TDT_HIP(hipMemcpyAsync(d_boff, h_boff, (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, st));
-        TDT_HIP(hipMemsetAsync(d_runbase, 0, (size_t)(nb + 1) * 4, st));
-        TDT_HIP(hipMemsetAsync(d_cnt, 0, 256, st));
-        return TDT_OK;
-    };
-
-    const int blocks1 = n ? (n + DB_THREADS - 1) / DB_THREADS : 1;
-    const int blocks4 = n ? (n + DB_TILE - 1) / DB_TILE : 1;
-    const int blocks_nb = (std::max(n, nb) + DB_THREADS - 1) / DB_THREADS;
     if (n == 0) {
-        // empty input: every bucket reports cluster_id -1
-        rc = prologue();
-        if (rc) return rc;
-        hipLaunchKernelGGL(dbx_final, dim3(blocks_nb), dim3(DB_THREADS), 0, st, (const int *)d_xlab, 0, (const int *)d_boff, nb,
-                           (const unsigned *)d_runbase, d_labels, (long long *)d_last_id);
-        TDT_CHECK_LAUNCH();
-        return TDT_OK;
+        rc = db_stage_buckets(c);
+        return rc ? rc : db_x_result(c, 0);
     }
     const bool fused = m <= DBF_M_MAX;
     if (fused && n < 0x7fff0000) {
-        // tile-resident pass (tdt_dbscan_tile.h): three launches; falls through to the multi-launch path below when an
-        // x-cluster is too large for it
-        const int ntt = (n + DT_T - 1) / DT_T;
-        const size_t sz_flags = 256, sz_agg = db_align((size_t)ntt * 4), sz_b = db_align((size_t)(nb + 1) * 4);
-        void *tb = nullptr;
-        const size_t sz_grp = db_align((size_t)2 * DT_GRPMAX * 4);
-        // the status block and the two group-sum arrays keep their contents from call to call: their own fixed-size allocation
-        void *ts = nullptr;
-        rc = tdt_scratch(ctx, 20, sz_flags + 2 * sz_grp, &ts);
-        if (rc) return rc;
-        unsigned *t_flags = (unsigned *)ts;
-        unsigned *t_grp0 = (unsigned *)((char *)ts + sz_flags);
-        unsigned *t_grp1 = (unsigned *)((char *)ts + sz_flags + sz_grp);
-        const size_t sz_code = db_align((size_t)n * 2 + 16);
-        rc = tdt_scratch(ctx, 21, 4 * sz_b + 2 * sz_agg + sz_code, &tb);
-        if (rc) return rc;
-        char *q = (char *)tb;
-        unsigned short *t_code = (unsigned short *)q; q += sz_code;
-        unsigned *t_brun = (unsigned *)q; q += sz_b;
-        unsigned *t_bext = (unsigned *)q; q += sz_b;
-        unsigned *t_aggR = (unsigned *)q; q += sz_agg;
-        unsigned *t_aggE = (unsigned *)q; q += sz_agg;
-        unsigned *t_runbase = (unsigned *)q; q += sz_b;
-        unsigned *t_extbase = (unsigned *)q; q += sz_b;
         if (nb > 1) {
-            rc = prologue();
+            rc = db_stage_buckets(c);
             if (rc) return rc;
         }
-        if (ctx->tile_flags_zeroed != ts) {       // first use of this block; afterwards the kernel that reports the status re-zeroes it
-            TDT_HIP(hipMemsetAsync(t_flags, 0, sz_flags, st));
-            TDT_HIP(hipMemsetAsync(t_grp0, 0, 2 * sz_grp, st));
-            ctx->tile_flags_zeroed = ts;
-        }
-        DtParams TP;
-        TP.x = d_x;
-        TP.y = d_y;
-        TP.n = n;
-        TP.boff = d_boff;
-        TP.nb = nb;
-        TP.eps32 = eps > 0xffffffffull ? 0xffffffffu : (unsigned)eps;
-        TP.wide = eps > 0xffffffffull;
-        TP.m = m;
-        TP.code = t_code;
-        TP.aggR = t_aggR;
-        TP.aggE = t_aggE;
-        TP.brun = t_brun;
-        TP.bext = t_bext;
-        TP.flags = t_flags;
-        const bool odd = nb == 1 && (ctx->tile_calls++ & 1u) != 0;     // (only the one-bucket kernels touch the group sums)
-        TP.grp = odd ? t_grp1 : t_grp0;
-        void *hp = nullptr;
-        rc = tdt_pinned(ctx, 2, 64, &hp);
-        if (rc) return rc;
-        volatile unsigned *hw = (volatile unsigned *)hp;
-        static std::atomic<unsigned> tile_seq{0};
-        unsigned seq = ++tile_seq;
-        if (seq == 0) seq = ++tile_seq;                                    // never 0
-        hw[1] = 0;
-        if (nb == 1 && mode == 0) hipLaunchKernelGGL((dbt_tile<true, false>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
-        else if (nb == 1) hipLaunchKernelGGL((dbt_tile<true, true>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
-        else if (mode == 0) hipLaunchKernelGGL((dbt_tile<false, false>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
-        else hipLaunchKernelGGL((dbt_tile<false, true>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
-        TDT_CHECK_LAUNCH();
-        if (nb == 1) {
-            ctx->tile_groups_max = std::max(ctx->tile_groups_max, (ntt + DT_GRP - 1) / DT_GRP);
-            hipLaunchKernelGGL(dbt_finish1, dim3((ntt + DT_FTPB - 1) / DT_FTPB), dim3(256), 0, st, (const unsigned short *)t_code, d_labels, n, (const int *)nullptr,
-                               (const unsigned *)t_aggR, (const unsigned *)t_aggE, ntt, (const unsigned *)TP.grp, odd ? t_grp0 : t_grp1, ctx->tile_groups_max,
-                               (long long *)d_last_id, 0ll, 0, t_flags, hw, seq);
-        } else {
-            hipLaunchKernelGGL(dbt_scan, dim3(1), dim3(1024), 0, st, t_aggR, t_aggE, ntt, (const int *)d_boff, nb, n, (const unsigned *)t_brun,
-                               (const unsigned *)t_bext, t_runbase, t_extbase, (long long *)d_last_id, mode, t_flags, hw, seq);
-            hipLaunchKernelGGL(dbt_finish, dim3((n + 1023) / 1024), dim3(256), 0, st, (const unsigned short *)t_code, d_labels, n, (const unsigned *)t_aggR,
-                               (const unsigned *)t_aggE, (const int *)d_boff, nb, (const unsigned *)t_runbase, (const unsigned *)t_extbase);
-        }
-        TDT_CHECK_LAUNCH();
-        // the one word that says whether the pass stands comes back through pinned memory (a hipStreamSynchronize wake-up costs
-        // more than the whole pass); dbt_scan stores it as soon as the tile kernel is done
-        bool seen = false;
-        for (long spin = 0; spin < 4000000; spin++) {
-            if (hw[1] == seq) {
-                seen = true;
-                break;
-            }
-            __builtin_ia32_pause();
-        }
-        if (!seen) TDT_HIP(hipStreamSynchronize(st));
-        if (hw[0] == 0) return TDT_OK;
+        bool stands = false;
+        rc = db_tile_pass(ctx, d_x, d_y, n, c.w.boff, nb, eps, m, mode, nullptr, 0ll, d_labels, c.last_id, &stands);
+        if (rc || stands) return rc;
     }
-    rc = prologue();
+    rc = db_stage_buckets(c);
     if (rc) return rc;
-    if (fused) {
-        // ballot-mask tiles; cross-tile prefixes from a one-workgroup scan between launches
-        const int ntf = (n + DBF_TILE - 1) / DBF_TILE;
-        const size_t nw = (size_t)ntf * DBF_WORDS + 2;   // whole tiles: kernels store all 64 words of their tile
-        const size_t mask_bytes = db_align(nw * 8);
-        const size_t ctl_bytes = db_align(sizeof(DbfCtl)) + 3 * db_align((size_t)ntf * 8) + 7 * mask_bytes;
-        void *cb = nullptr;
-        rc = tdt_scratch(ctx, 8, ctl_bytes, &cb);
-        if (rc) return rc;
-        char *q = (char *)cb;
-        DbfCtl *ctl = (DbfCtl *)q; q += db_align(sizeof(DbfCtl));
-        ull *agg_x = (ull *)q; q += db_align((size_t)ntf * 8);
-        ull *agg_1 = (ull *)q; q += db_align((size_t)ntf * 8);
-        ull *agg_2 = (ull *)q; q += db_align((size_t)ntf * 8);
-        ull *PM = (ull *)q; q += mask_bytes;
-        ull *PY = (ull *)q; q += mask_bytes;
-        ull *HM = (ull *)q; q += mask_bytes;
-        ull *BM = (ull *)q; q += mask_bytes;
-        ull *EM = (ull *)q; q += mask_bytes;
-        ull *S1M = (ull *)q; q += mask_bytes;
-        ull *FM = (ull *)q; q += mask_bytes;
-        // (the control word and the three guard words of the mask arrays are zeroed by tile 0 of dbm_x_masks)
-        if (nb == 1 && m <= 4)
-            hipLaunchKernelGGL(dbm_x_masks<true>, dim3(ntf), dim3(DBF_THREADS), 0, st, d_x, n, (const int *)d_boff, nb, (ull)eps, m, PM, agg_x, PY, ctl);
-        else
-            hipLaunchKernelGGL(dbm_x_masks<false>, dim3(ntf), dim3(DBF_THREADS), 0, st, d_x, n, (const int *)d_boff, nb, (ull)eps, m, PM, agg_x, PY, ctl);
-        if (ntf > DBM_INLINE_PREFIX_MAX) hipLaunchKernelGGL(tile_scan, dim3(1), dim3(1024), 0, st, agg_x, ntf);
-        hipLaunchKernelGGL(dbm_x_labels, dim3(ntf), dim3(DBF_THREADS), 0, st, (const ull *)PM, (const ull *)agg_x, n, (const int *)d_boff, nb,
-                           m, d_xlab, d_runbase, d_seg0, d_seg1);
-        TDT_CHECK_LAUNCH();
-        if (mode == 1) {
-            hipLaunchKernelGGL(dbx_final, dim3(blocks_nb), dim3(DB_THREADS), 0, st, (const int *)d_xlab, n, (const int *)d_boff, nb,
-                               (const unsigned *)d_runbase, d_labels, (long long *)d_last_id);
-            TDT_CHECK_LAUNCH();
-            return TDT_OK;
-        }
-        hipLaunchKernelGGL(dby_rank, dim3(blocks1), dim3(DB_THREADS), 0, st, (const int *)d_xlab, d_y, n, (const int *)d_seg0,
-                           (const int *)d_seg1, d_ys, d_ord, d_lflag, &ctl->nlarge);
-        TDT_CHECK_LAUNCH();
-        // The y pass is enqueued right away on the assumption that no x-cluster exceeded DB_SMALL members (the
-        // usual case), so the GPU never idles on a mid-pipeline readback; the counter is checked afterwards
-        // and only then are the large clusters sorted and the y pass repeated.
-        for (int attempt = 0; attempt < 2; attempt++) {
-            hipLaunchKernelGGL(dbm_y_masks, dim3(ntf), dim3(DBF_THREADS), 0, st, (const int *)d_xlab, (const unsigned *)d_ys, n,
-                               (const int *)d_boff, nb, (ull)eps, m, PY, HM, BM, agg_1);
-            if (ntf > DBM_INLINE_PREFIX_MAX) hipLaunchKernelGGL(tile_scan, dim3(1), dim3(1024), 0, st, agg_1, ntf);
-            hipLaunchKernelGGL(dbm_y_mid, dim3(ntf), dim3(DBF_THREADS), 0, st, (const ull *)PY, (const ull *)HM, (const ull *)BM,
-                               (const ull *)agg_1, n, m, EM, S1M, FM, agg_2);
-            if (ntf > DBM_INLINE_PREFIX_MAX) hipLaunchKernelGGL(tile_scan, dim3(1), dim3(1024), 0, st, agg_2, ntf);
-            hipLaunchKernelGGL(dbm_y_final, dim3(ntf), dim3(DBF_THREADS), 0, st, (const int *)d_xlab, (const unsigned *)d_ord, (const ull *)BM,
-                               (const ull *)EM, (const ull *)S1M, (const ull *)FM, (const ull *)agg_2, n, (const int *)d_boff, nb,
-                               (const unsigned *)d_runbase, d_labels, (long long *)d_last_id);
-            TDT_CHECK_LAUNCH();
-            if (attempt == 1) break;
-            unsigned nlarge = 0;
-            {
-                void *hp = nullptr;
-                rc = tdt_pinned(ctx, 2, 64, &hp);
-                if (rc) return rc;
-                volatile unsigned *hw = (volatile unsigned *)hp;
-                static std::atomic<unsigned> seq_counter{0};
-                unsigned seq = ++seq_counter;
-                if (seq == 0) seq = ++seq_counter;                                    // never 0
-                hw[1] = 0;
-                hipLaunchKernelGGL(db_signal_host, dim3(1), dim3(1), 0, st, (const unsigned *)&ctl->nlarge, hw, seq);
-                TDT_CHECK_LAUNCH();
-                bool seen = false;
-                for (long spin = 0; spin < 4000000; spin++) {     // a few milliseconds at most, then the ordinary wait
-                    if (hw[1] == seq) {
-                        seen = true;
-                        break;
-                    }
-                    __builtin_ia32_pause();
-                }
-                if (!seen) TDT_HIP(hipStreamSynchronize(st));
-                nlarge = hw[0];
-            }
-            if (!nlarge) break;
-            rc = db_sort_large(ctx, d_xlab, d_y, n, d_lflag, d_tsum, d_key, d_ksorted, d_v0, d_v1, d_cpos, d_ys, d_ord);
-            if (rc) return rc;
-        }
-        if (d_last_id && nb > 1)
-            hipLaunchKernelGGL(dbf_empty_buckets, dim3((nb + 255) / 256), dim3(256), 0, st, (const int *)d_boff, nb, (long long *)d_last_id);
-        TDT_CHECK_LAUNCH();
-        return TDT_OK;
+    return fused ? db_route_masks(c) : db_route_scans(c);
+}
+
+// ---- what the host entries of int64 columns share: device coordinates are uint32 offsets from the column minimum
+static void db_column_range(const int64_t *col, size_t n, size_t stride, int64_t *lo, int64_t *hi) {
+    *lo = *hi = col[0];
+    for (size_t i = 0; i < n; i++) {
+        *lo = std::min(*lo, col[i * stride]);
+        *hi = std::max(*hi, col[i * stride]);
     }
-    hipLaunchKernelGGL(dbx_flags, dim3(blocks4), dim3(DB_THREADS), 0, st, d_x, n, (const int *)d_boff, nb,
-                       (unsigned long long)eps, m, d_px, d_sx);
-    TDT_CHECK_LAUNCH();
-    rc = db_scan_inplace(ctx, d_sx, n, d_tsum);
+}
+
+// two 32-bit columns of n values, fill(i, a, b) giving row i, through pinned block 1 to the head of scratch slot 5 (dev_bytes in all)
+template <class F>
+static int db_stage_columns(tdt_ctx *ctx, size_t n, size_t dev_bytes, F &&fill, uint32_t **d0, uint32_t **d1) {
+    void *h = nullptr, *d = nullptr;
+    int rc = tdt_pinned(ctx, 1, n * 8 + 64, &h);
     if (rc) return rc;
-    hipLaunchKernelGGL(dbx_labels, dim3(blocks1), dim3(DB_THREADS), 0, st, (const unsigned char *)d_px, (const unsigned *)d_sx, n, m,
-                       (const int *)d_boff, nb, d_xlab, d_runbase);
-    TDT_CHECK_LAUNCH();
-    if (mode == 1) {
-        hipLaunchKernelGGL(dbx_final, dim3(blocks_nb), dim3(DB_THREADS), 0, st, (const int *)d_xlab, n, (const int *)d_boff, nb,
-                           (const unsigned *)d_runbase, d_labels, (long long *)d_last_id);
-        TDT_CHECK_LAUNCH();
-        return TDT_OK;
-    }
-    hipLaunchKernelGGL(db_segments, dim3(blocks1), dim3(DB_THREADS), 0, st, (const int *)d_xlab, n, d_seg0, d_seg1);
-    hipLaunchKernelGGL(dby_rank, dim3(blocks1), dim3(DB_THREADS), 0, st, (const int *)d_xlab, d_y, n, (const int *)d_seg0,
-                       (const int *)d_seg1, d_ys, d_ord, d_lflag, d_cnt);
-    TDT_CHECK_LAUNCH();
-    // x-clusters larger than DB_SMALL: one 4-byte readback decides whether the radix sort runs
-    unsigned nlarge = 0;
-    TDT_HIP(hipMemcpyAsync(&nlarge, d_cnt, 4, hipMemcpyDeviceToHost, st));
-    TDT_HIP(hipStreamSynchronize(st));
-    if (nlarge) {
-        rc = db_sort_large(ctx, d_xlab, d_y, n, d_lflag, d_tsum, d_key, d_ksorted, d_v0, d_v1, d_cpos, d_ys, d_ord);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(dby_flags, dim3(blocks1), dim3(DB_THREADS), 0, st, (const int *)d_xlab, n, (const int *)d_seg0,
-                       (const int *)d_seg1, (const unsigned *)d_ys, (unsigned long long)eps, m, d_py, d_sy);
-    TDT_CHECK_LAUNCH();
-    rc = db_scan_inplace(ctx, d_sy, n, d_tsum);
+    rc = tdt_scratch(ctx, 5, dev_bytes, &d);
     if (rc) return rc;
-    hipLaunchKernelGGL(dby_extras, dim3(blocks1), dim3(DB_THREADS), 0, st, (const int *)d_xlab, n, (const int *)d_seg0,
-                       (const int *)d_seg1, (const unsigned *)d_sy, d_ex);
-    TDT_CHECK_LAUNCH();
-    rc = db_scan_inplace(ctx, d_ex, n, d_tsum);
-    if (rc) return rc;
-    hipLaunchKernelGGL(dby_final, dim3(blocks_nb), dim3(DB_THREADS), 0, st, (const int *)d_xlab, n, m, (const int *)d_seg0,
-                       (const unsigned char *)d_py, (const unsigned *)d_sy, (const unsigned *)d_ex, (const unsigned *)d_ord,
-                       (const int *)d_boff, nb, (const unsigned *)d_runbase, d_labels, (long long *)d_last_id);
-    TDT_CHECK_LAUNCH();
+    uint32_t *h0 = (uint32_t *)h, *h1 = h0 + n;
+    for (size_t i = 0; i < n; i++) fill(i, h0[i], h1[i]);
+    *d0 = (uint32_t *)d;
+    *d1 = *d0 + n;
+    TDT_HIP(hipMemcpyAsync(d, h, n * 8, hipMemcpyHostToDevice, ctx->stream));
     return TDT_OK;
 }
 
-static uint64_t db_eps_u64(double eps) {
-    // numpy: int64 distance < python number  <=>  d < ceil(eps) for integer d >= 0
-    if (!(eps > 0)) return 0;  // also NaN: nothing is ever < NaN
-    if (eps >= 8589934592.0) return 1ull << 33;
-    return (uint64_t)ceil(eps);
+// the labels and the last id, home once the stream is done
+static int db_result_home(tdt_ctx *ctx, const double *d_labels, size_t n, const void *d_last, double *labels, int64_t *last_id) {
+    long long lid = -1;
+    TDT_HIP(hipStreamSynchronize(ctx->stream));
+    TDT_HIP(hipMemcpy(labels, d_labels, n * 8, hipMemcpyDeviceToHost));
+    TDT_HIP(hipMemcpy(&lid, d_last, 8, hipMemcpyDeviceToHost));
+    if (last_id) *last_id = lid;
+    return TDT_OK;
 }
 
 extern "C" int tdt_dbscan(tdt_ctx *ctx, const int64_t *data, size_t n, size_t stride, double eps, int m, int mode,
@@ -747,49 +804,27 @@ extern "C" int tdt_dbscan(tdt_ctx *ctx, const int64_t *data, size_t n, size_t st
         if (last_id) *last_id = -1;
         return TDT_OK;
     }
-    // device coordinates are uint32 offsets from the column minimum
-    int64_t xmin = data[0], xmax = data[0], ymin = 0, ymax = 0;
-    if (stride >= 2) ymin = ymax = data[1];
-    for (size_t i = 0; i < n; i++) {
-        const int64_t xv = data[i * stride];
-        xmin = xv < xmin ? xv : xmin;
-        xmax = xv > xmax ? xv : xmax;
-        if (stride >= 2) {
-            const int64_t yv = data[i * stride + 1];
-            ymin = yv < ymin ? yv : ymin;
-            ymax = yv > ymax ? yv : ymax;
-        }
-    }
-    if ((unsigned __int128)((__int128)xmax - xmin) > 0xfffffffeull || (unsigned __int128)((__int128)ymax - ymin) > 0xfffffffeull) {
-        tdt_set_error("tdt_dbscan: coordinate span >= 2^32 is outside the device path's domain");
-        return TDT_E_UNSUPPORTED;
-    }
-    void *h = nullptr, *d = nullptr;
-    int rc = tdt_pinned(ctx, 1, n * 8 + n * 8 + 64, &h);
+    int64_t xmin, xmax, ymin = 0, ymax = 0;
+    db_column_range(data, n, stride, &xmin, &xmax);
+    if (stride >= 2) db_column_range(data + 1, n, stride, &ymin, &ymax);
+    int rc = tdt_check_span("tdt_dbscan", xmin, xmax);
+    if (!rc) rc = tdt_check_span("tdt_dbscan", ymin, ymax);
     if (rc) return rc;
-    rc = tdt_scratch(ctx, 5, n * 8 + n * 8 + 64, &d);
+    uint32_t *dx = nullptr, *dy = nullptr;
+    rc = db_stage_columns(ctx, n, n * 16 + 64, [&](size_t i, uint32_t &a, uint32_t &b) {
+        a = (uint32_t)(data[i * stride] - xmin);
+        b = stride >= 2 ? (uint32_t)(data[i * stride + 1] - ymin) : 0u;
+    }, &dx, &dy);
     if (rc) return rc;
-    uint32_t *hx = (uint32_t *)h, *hy = hx + n;
-    for (size_t i = 0; i < n; i++) {
-        hx[i] = (uint32_t)(data[i * stride] - xmin);
-        hy[i] = stride >= 2 ? (uint32_t)(data[i * stride + 1] - ymin) : 0u;
-    }
-    uint32_t *dx = (uint32_t *)d, *dy = dx + n;
-    TDT_HIP(hipMemcpyAsync(dx, hx, n * 8, hipMemcpyHostToDevice, ctx->stream));
     const int64_t boff[2] = {0, (int64_t)n};
     void *dlast = nullptr;
     rc = tdt_scratch(ctx, 6, n * 8 + 64, &dlast);
     if (rc) return rc;
     double *dl = (double *)dlast;
-    long long *dlid = (long long *)((char *)dlast + n * 8);
-    rc = tdt_dbscan_device(ctx, dx, dy, n, boff, 1, db_eps_u64(eps), m, mode, dl, (int64_t *)dlid);
+    int64_t *dlid = (int64_t *)((char *)dlast + n * 8);
+    rc = tdt_dbscan_device(ctx, dx, dy, n, boff, 1, tdt_eps_u64(eps), m, mode, dl, dlid);
     if (rc) return rc;
-    TDT_HIP(hipStreamSynchronize(ctx->stream));
-    long long lid = -1;
-    TDT_HIP(hipMemcpy(labels, dl, n * 8, hipMemcpyDeviceToHost));
-    TDT_HIP(hipMemcpy(&lid, dlid, 8, hipMemcpyDeviceToHost));
-    if (last_id) *last_id = lid;
-    return TDT_OK;
+    return db_result_home(ctx, dl, n, dlid, labels, last_id);
 }
 
 // ---- y pass on caller-supplied x labels (DBSCAN.y_coordinate_clustering, DBSCAN.py:66-123) -------------------------------------
@@ -810,64 +845,11 @@ extern "C" int tdt_dbscan_y_device(tdt_ctx *ctx, const int32_t *d_xlab, const ui
     }
     if (n_ == 0) return TDT_OK;
     TDT_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int n = (int)n_;
-    const int ntt = (n + DT_T - 1) / DT_T;
-    const size_t sz_flags = 256, sz_agg = db_align((size_t)ntt * 4), sz_grp = db_align((size_t)2 * DT_GRPMAX * 4);
-    void *ts = nullptr, *tb = nullptr;
-    int rc = tdt_scratch(ctx, 20, sz_flags + 2 * sz_grp, &ts);
+    bool stands = false;
+    const int rc = db_tile_pass(ctx, nullptr, d_y, (int)n_, nullptr, 1, eps, m, 0, d_xlab, (long long)cluster_id, d_labels, (long long *)d_last_id,
+                                &stands);
     if (rc) return rc;
-    const size_t sz_code = db_align((size_t)n * 2 + 16);
-    rc = tdt_scratch(ctx, 21, 2 * sz_agg + 1024 + sz_code, &tb);
-    if (rc) return rc;
-    unsigned short *t_code = (unsigned short *)((char *)tb + 2 * sz_agg + 1024);
-    unsigned *t_flags = (unsigned *)ts;
-    unsigned *t_grp0 = (unsigned *)((char *)ts + sz_flags), *t_grp1 = (unsigned *)((char *)ts + sz_flags + sz_grp);
-    unsigned *t_aggR = (unsigned *)tb, *t_aggE = (unsigned *)((char *)tb + sz_agg);
-    if (ctx->tile_flags_zeroed != ts) {
-        TDT_HIP(hipMemsetAsync(t_flags, 0, sz_flags, st));
-        TDT_HIP(hipMemsetAsync(t_grp0, 0, 2 * sz_grp, st));
-        ctx->tile_flags_zeroed = ts;
-    }
-    DtParams TP;
-    TP.x = (const unsigned *)d_xlab;
-    TP.y = d_y;
-    TP.n = n;
-    TP.boff = nullptr;
-    TP.nb = 1;
-    TP.eps32 = eps > 0xffffffffull ? 0xffffffffu : (unsigned)eps;
-    TP.wide = eps > 0xffffffffull;
-    TP.m = m;
-    TP.code = t_code;
-    TP.aggR = t_aggR;
-    TP.aggE = t_aggE;
-    TP.brun = TP.bext = nullptr;
-    TP.flags = t_flags;
-    const bool odd = (ctx->tile_calls++ & 1u) != 0;
-    TP.grp = odd ? t_grp1 : t_grp0;
-    void *hp = nullptr;
-    rc = tdt_pinned(ctx, 2, 64, &hp);
-    if (rc) return rc;
-    volatile unsigned *hw = (volatile unsigned *)hp;
-    static std::atomic<unsigned> y_seq{0x40000000u};
-    const unsigned seq = ++y_seq | 0x40000000u;
-    hw[1] = 0;
-    hipLaunchKernelGGL((dbt_tile<true, false, true>), dim3(ntt), dim3(DT_THREADS), 0, st, TP);
-    ctx->tile_groups_max = std::max(ctx->tile_groups_max, (ntt + DT_GRP - 1) / DT_GRP);
-    hipLaunchKernelGGL(dbt_finish1, dim3((ntt + DT_FTPB - 1) / DT_FTPB), dim3(256), 0, st, (const unsigned short *)t_code, d_labels, n, (const int *)d_xlab,
-                       (const unsigned *)t_aggR, (const unsigned *)t_aggE, ntt, (const unsigned *)TP.grp, odd ? t_grp0 : t_grp1, ctx->tile_groups_max,
-                       (long long *)d_last_id, (long long)cluster_id, 1, t_flags, hw, seq);
-    TDT_CHECK_LAUNCH();
-    bool seen = false;
-    for (long spin = 0; spin < 4000000; spin++) {
-        if (hw[1] == seq) {
-            seen = true;
-            break;
-        }
-        __builtin_ia32_pause();
-    }
-    if (!seen) TDT_HIP(hipStreamSynchronize(st));
-    if (hw[0]) *too_large = 1;
+    if (!stands) *too_large = 1;
     return TDT_OK;
 }
 
@@ -915,52 +897,32 @@ extern "C" int tdt_dbscan_y(tdt_ctx *ctx, const int64_t *data, size_t n, size_t 
                       (long long)cluster_id, next - 1);
         return TDT_E_UNSUPPORTED;
     }
-    int64_t ymin = data[1], ymax = data[1];
-    for (size_t i = 0; i < n; i++) {
-        ymin = std::min(ymin, data[i * stride + 1]);
-        ymax = std::max(ymax, data[i * stride + 1]);
-    }
-    if ((unsigned __int128)((__int128)ymax - ymin) > 0xfffffffeull) {
-        tdt_set_error("tdt_dbscan_y: coordinate span >= 2^32 is outside the device path's domain");
-        return TDT_E_UNSUPPORTED;
-    }
-    void *h = nullptr, *d = nullptr;
-    int rc = tdt_pinned(ctx, 1, n * 8 + 64, &h);
+    int64_t ymin, ymax;
+    db_column_range(data + 1, n, stride, &ymin, &ymax);
+    int rc = tdt_check_span("tdt_dbscan_y", ymin, ymax);
     if (rc) return rc;
-    rc = tdt_scratch(ctx, 5, n * 16 + 256, &d);
+    // slot 5: the y column and the labels as int32, then the float64 labels of the result
+    uint32_t *dy = nullptr, *dl = nullptr;
+    rc = db_stage_columns(ctx, n, n * 16 + 256, [&](size_t i, uint32_t &a, uint32_t &b) {
+        a = (uint32_t)(data[i * stride + 1] - ymin);
+        b = (uint32_t)(int32_t)labels[i];
+    }, &dy, &dl);
     if (rc) return rc;
-    uint32_t *hy = (uint32_t *)h;
-    int32_t *hl = (int32_t *)(hy + n);
-    for (size_t i = 0; i < n; i++) {
-        hy[i] = (uint32_t)(data[i * stride + 1] - ymin);
-        hl[i] = (int32_t)labels[i];
-    }
-    uint32_t *dy = (uint32_t *)d;
-    int32_t *dl = (int32_t *)(dy + n);
-    double *dlab = (double *)((char *)d + ((n * 8 + 255) & ~(size_t)255));
-    hipStream_t st = ctx->stream;
-    TDT_HIP(hipMemcpyAsync(dy, hy, n * 8, hipMemcpyHostToDevice, st));
+    double *dlab = (double *)((char *)dy + ((n * 8 + 255) & ~(size_t)255));
     void *dlast = nullptr;
     rc = tdt_scratch(ctx, 6, 64, &dlast);
     if (rc) return rc;
     int large = 0;
-    rc = tdt_dbscan_y_device(ctx, dl, dy, n, db_eps_u64(eps), m, cluster_id, dlab, (int64_t *)dlast, &large);
+    rc = tdt_dbscan_y_device(ctx, (const int32_t *)dl, dy, n, tdt_eps_u64(eps), m, cluster_id, dlab, (int64_t *)dlast, &large);
     if (rc) return rc;
     if (large) {
         tdt_set_error("tdt_dbscan_y: an x-cluster has more than %d members (or m > %d): not on the caller-supplied-labels path", DB_SMALL, DBF_M_MAX);
         return TDT_E_UNSUPPORTED;
     }
-    TDT_HIP(hipStreamSynchronize(st));
-    long long lid = cluster_id;
-    TDT_HIP(hipMemcpy(labels, dlab, n * 8, hipMemcpyDeviceToHost));
-    TDT_HIP(hipMemcpy(&lid, dlast, 8, hipMemcpyDeviceToHost));
-    if (last_id) *last_id = lid;
-    return TDT_OK;
+    return db_result_home(ctx, dlab, n, dlast, labels, last_id);
 }
 
 // -------------------------------------------------------------------- sort + cluster in one call
-extern "C" int tdt_sort_dbscan_ex(tdt_ctx *ctx, const int64_t *posA, const int64_t *posB, size_t n, const int64_t *bucket_off, int nb,
-                                  double eps, int m, uint32_t *perm_out, double *labels_out, int64_t *runs_out, int64_t *last_out);
 __global__ __launch_bounds__(DB_THREADS) void sd_make_keys(const unsigned *__restrict__ x, int n, const int *__restrict__ boff, int nb,
                                                            unsigned long long *__restrict__ key, unsigned *__restrict__ val) {
     const int i = blockIdx.x * DB_THREADS + threadIdx.x;
@@ -987,6 +949,88 @@ __global__ __launch_bounds__(DB_THREADS) void sd_labels_i32(const double *__rest
     if (i < n) out[i] = (int)lab[i];
 }
 
+// ---- what the two sort-then-cluster entries (tdt_sort_dbscan_ex, tdt_cluster_columns) share
+// the argument checks; *empty: no signals — every bucket reports no runs and cluster_id -1, and the call is done
+static int sc_check(const char *who, bool pointers_ok, size_t n, const int64_t *bucket_off, int nb, int m, int64_t *runs_out, int64_t *last_out,
+                    bool *empty) {
+    if (!pointers_ok || nb < 1 || !bucket_off) {
+        tdt_set_error("%s: bad argument", who);
+        return TDT_E_ARG;
+    }
+    if (m < 2) {
+        tdt_set_error("%s: m must be >= 2", who);
+        return TDT_E_ARG;
+    }
+    if (n >= 0x7fffffffull || bucket_off[0] != 0 || bucket_off[nb] != (int64_t)n) {
+        tdt_set_error("%s: bad bucket offsets / n", who);
+        return TDT_E_ARG;
+    }
+    *empty = n == 0;
+    for (int b = 0; *empty && b < nb; b++) {
+        if (runs_out) runs_out[b] = 0;
+        if (last_out) last_out[b] = -1;
+    }
+    return TDT_OK;
+}
+
+// slot 5 of the two entries: the two columns as they arrive, the sorted columns, the sort's pairs, `aux` (the order, or the int32
+// labels in signal order), the float64 labels, the bucket offsets and, where asked for, per bucket the x pass's and the full pass's
+// last id.  (The last 256 bytes are slack these requests have always had.)
+struct ScWork {
+    unsigned *in0, *in1, *xs, *ys, *v0, *v1, *aux;
+    unsigned long long *k0, *k1;
+    double *lab;
+    int *boff;
+    long long *cnt;
+    size_t lay(void *base, size_t n, int nb, bool counts) {
+        tdt_carver c(base);
+        in0 = c.take<unsigned>(n), in1 = c.take<unsigned>(n), xs = c.take<unsigned>(n), ys = c.take<unsigned>(n);
+        v0 = c.take<unsigned>(n), v1 = c.take<unsigned>(n), aux = c.take<unsigned>(n);
+        k0 = c.take<unsigned long long>(n), k1 = c.take<unsigned long long>(n);
+        lab = c.take<double>(n);
+        boff = c.take<int>((size_t)nb + 1);
+        cnt = counts ? c.take<long long>((size_t)nb * 2 + 8) : nullptr;
+        c.take<char>(256);
+        return c.size;
+    }
+};
+
+// [0, n) cut into nth ranges, fn(t, i0, i1) on a host thread each (the caller's own takes the first)
+static int sc_host_threads(size_t n, size_t grain) {
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)tdt_host_thread_count(), n / grain + 1));
+}
+template <class F>
+static void sc_host_ranges(size_t n, int nth, F &&fn) {
+    std::vector<std::thread> th;
+    for (int t = 1; t < nth; t++) th.emplace_back([&fn, n, nth, t] { fn(t, n * (size_t)t / nth, n * (size_t)(t + 1) / nth); });
+    fn(0, 0, n / nth);
+    for (auto &x : th) x.join();
+}
+
+// cluster the sorted columns.  d_cnt (null: the caller wants neither) gets per bucket the last id of the x pass alone — run only
+// where `runs` are wanted: its cluster_id is the number of x-runs - 1 (DBSCAN.py:33-64) — and behind them the last ids of the full pass
+static int sc_cluster_sorted(tdt_ctx *ctx, const unsigned *d_xs, const unsigned *d_ys, size_t n, const int64_t *bucket_off, int nb, double eps, int m,
+                             bool runs, double *d_lab, long long *d_cnt) {
+    if (runs) {
+        const int rc = tdt_dbscan_device(ctx, d_xs, d_ys, n, bucket_off, nb, tdt_eps_u64(eps), m, 1, d_lab, (int64_t *)d_cnt);
+        if (rc) return rc;
+    }
+    return tdt_dbscan_device(ctx, d_xs, d_ys, n, bucket_off, nb, tdt_eps_u64(eps), m, 0, d_lab, d_cnt ? (int64_t *)(d_cnt + nb) : nullptr);
+}
+
+// the counts' way home: their copy is enqueued (sc_counts_fetch), and once the stream has been waited for they go to the caller
+static int sc_counts_fetch(tdt_ctx *ctx, const long long *d_cnt, int nb, std::vector<long long> &hc) {
+    hc.assign((size_t)nb * 2, 0);
+    if (d_cnt) TDT_HIP(hipMemcpyAsync(hc.data(), d_cnt, (size_t)nb * 16, hipMemcpyDeviceToHost, ctx->stream));
+    return TDT_OK;
+}
+static void sc_counts_report(const std::vector<long long> &hc, int nb, int64_t *runs_out, int64_t *last_out) {
+    for (int b = 0; b < nb; b++) {
+        if (runs_out) runs_out[b] = hc[b] + 1;
+        if (last_out) last_out[b] = hc[nb + b];
+    }
+}
+
 extern "C" int tdt_sort_dbscan(tdt_ctx *ctx, const int64_t *posA, const int64_t *posB, size_t n, const int64_t *bucket_off, int nb,
                                double eps, int m, uint32_t *perm_out, double *labels_out) {
     return tdt_sort_dbscan_ex(ctx, posA, posB, n, bucket_off, nb, eps, m, perm_out, labels_out, nullptr, nullptr);
@@ -996,36 +1040,14 @@ extern "C" int tdt_sort_dbscan(tdt_ctx *ctx, const int64_t *posA, const int64_t 
 // cluster_id of DBSCAN.main — what a caller that cut one bucket into pieces needs to re-base the pieces' ids (dist.py)
 extern "C" int tdt_sort_dbscan_ex(tdt_ctx *ctx, const int64_t *posA, const int64_t *posB, size_t n, const int64_t *bucket_off, int nb,
                                   double eps, int m, uint32_t *perm_out, double *labels_out, int64_t *runs_out, int64_t *last_out) {
-    if (!ctx || nb < 1 || !bucket_off || (n && (!posA || !posB || !perm_out || !labels_out))) {
-        tdt_set_error("tdt_sort_dbscan: bad argument");
-        return TDT_E_ARG;
-    }
-    if (m < 2) {
-        tdt_set_error("tdt_sort_dbscan: m must be >= 2");
-        return TDT_E_ARG;
-    }
-    if (n >= 0x7fffffffull || bucket_off[0] != 0 || bucket_off[nb] != (int64_t)n) {
-        tdt_set_error("tdt_sort_dbscan: bad bucket offsets / n");
-        return TDT_E_ARG;
-    }
-    if (n == 0) {
-        for (int b = 0; b < nb; b++) {
-            if (runs_out) runs_out[b] = 0;
-            if (last_out) last_out[b] = -1;
-        }
-        return TDT_OK;
-    }
+    bool empty = false;
+    int rc = sc_check("tdt_sort_dbscan", ctx && (!n || (posA && posB && perm_out && labels_out)), n, bucket_off, nb, m, runs_out, last_out, &empty);
+    if (rc || empty) return rc;
     TDT_HIP(hipSetDevice(ctx->device));
     // column ranges and the 32-bit offsets: host passes over n elements, spread over the host threads
-    const int nth = (int)std::max<size_t>(1, std::min<size_t>((size_t)tdt_host_thread_count(), n / (1u << 16) + 1));
-    auto par = [&](auto &&fn) {
-        std::vector<std::thread> th;
-        for (int t = 1; t < nth; t++) th.emplace_back([&, t] { fn(t, n * (size_t)t / nth, n * (size_t)(t + 1) / nth); });
-        fn(0, 0, n / nth);
-        for (auto &x : th) x.join();
-    };
-    std::vector<int64_t> lo_a(nth, posA[0]), hi_a(nth, posA[0]), lo_b(nth, posB[0]), hi_b(nth, posB[0]);
-    par([&](int t, size_t i0, size_t i1) {
+    const int nth = sc_host_threads(n, 1u << 16);
+    std::vector<int64_t> lo_a(nth), hi_a(nth), lo_b(nth), hi_b(nth);
+    sc_host_ranges(n, nth, [&](int t, size_t i0, size_t i1) {
         int64_t a0 = posA[0], a1 = posA[0], b0 = posB[0], b1 = posB[0];
         for (size_t i = i0; i < i1; i++) {
             a0 = std::min(a0, posA[i]);
@@ -1037,55 +1059,39 @@ extern "C" int tdt_sort_dbscan_ex(tdt_ctx *ctx, const int64_t *posA, const int64
     });
     const int64_t amin = *std::min_element(lo_a.begin(), lo_a.end()), amax = *std::max_element(hi_a.begin(), hi_a.end());
     const int64_t bmin = *std::min_element(lo_b.begin(), lo_b.end()), bmax = *std::max_element(hi_b.begin(), hi_b.end());
-    if ((unsigned __int128)((__int128)amax - amin) > 0xfffffffeull || (unsigned __int128)((__int128)bmax - bmin) > 0xfffffffeull) {
-        tdt_set_error("tdt_sort_dbscan: coordinate span >= 2^32 is outside the device path's domain");
-        return TDT_E_UNSUPPORTED;
-    }
+    rc = tdt_check_span("tdt_sort_dbscan", amin, amax);
+    if (!rc) rc = tdt_check_span("tdt_sort_dbscan", bmin, bmax);
+    if (rc) return rc;
     hipStream_t st = ctx->stream;
-    void *h = nullptr, *d = nullptr;
+    void *h = nullptr;
     const size_t hb = n * 12 + (size_t)(nb + 1) * 4 + 64;     // in: two 32-bit columns; out: labels (8 B) + order (4 B) per signal
-    int rc = tdt_pinned(ctx, 1, hb, &h);
+    rc = tdt_pinned(ctx, 1, hb, &h);
     if (rc) return rc;
-    // device: x,y (in), xs,ys (sorted), perm, keys in/out, labels, boff
-    const size_t szN4 = db_align(n * 4), szN8 = db_align(n * 8);
-    rc = tdt_scratch(ctx, 5, 7 * szN4 + 3 * szN8 + db_align((size_t)(nb + 1) * 4) + 256, &d);
+    ScWork W;                                                 // aux: the order
+    rc = tdt_scratch_layout(ctx, 5, W, n, nb, false);
     if (rc) return rc;
-    char *p = (char *)d;
-    unsigned *dx = (unsigned *)p; p += szN4;
-    unsigned *dy = (unsigned *)p; p += szN4;
-    unsigned *dxs = (unsigned *)p; p += szN4;
-    unsigned *dys = (unsigned *)p; p += szN4;
-    unsigned *dperm = (unsigned *)p; p += szN4;
-    unsigned *dv0 = (unsigned *)p; p += szN4;
-    unsigned *dv1 = (unsigned *)p; p += szN4;
-    unsigned long long *dk = (unsigned long long *)p; p += szN8;
-    unsigned long long *dks = (unsigned long long *)p; p += szN8;
-    double *dlab = (double *)p; p += szN8;
-    int *dboff = (int *)p;
     uint32_t *hx = (uint32_t *)h, *hy = hx + n;
     int *hboff = (int *)((char *)h + n * 12);
-    par([&](int, size_t i0, size_t i1) {
+    sc_host_ranges(n, nth, [&](int, size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; i++) {
             hx[i] = (uint32_t)(posA[i] - amin);
             hy[i] = (uint32_t)(posB[i] - bmin);
         }
     });
     for (int b = 0; b <= nb; b++) hboff[b] = (int)bucket_off[b];
-    TDT_HIP(hipMemcpyAsync(dx, hx, n * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(dy, hy, n * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(dboff, hboff, (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, st));
+    TDT_HIP(hipMemcpyAsync(W.in0, hx, n * 4, hipMemcpyHostToDevice, st));
+    TDT_HIP(hipMemcpyAsync(W.in1, hy, n * 4, hipMemcpyHostToDevice, st));
+    TDT_HIP(hipMemcpyAsync(W.boff, hboff, (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, st));
     const int blocks = ((int)n + DB_THREADS - 1) / DB_THREADS;
-    hipLaunchKernelGGL(sd_make_keys, dim3(blocks), dim3(DB_THREADS), 0, st, (const unsigned *)dx, (int)n, (const int *)dboff, nb, dk, dv0);
+    hipLaunchKernelGGL(sd_make_keys, dim3(blocks), dim3(DB_THREADS), 0, st, (const unsigned *)W.in0, (int)n, (const int *)W.boff, nb, W.k0, W.v0);
     TDT_CHECK_LAUNCH();
     // only the digits that can differ are sorted: the posA span and the bucket index
-    unsigned long long mask = amax > amin ? ((1ull << tdt_ceil_log2_u64((uint64_t)(amax - amin) + 1)) - 1ull) : 0ull;
-    if (nb > 1) mask |= ((1ull << tdt_ceil_log2_u64((uint64_t)nb)) - 1ull) << 32;
     unsigned long long *ks = nullptr;
     unsigned *vs = nullptr;
-    rc = tdt_radix_sort_pairs(ctx, dk, dv0, dks, dv1, n, mask, &ks, &vs);
+    rc = tdt_radix_sort_pairs(ctx, W.k0, W.v0, W.k1, W.v1, n, tdt_sort_mask((uint64_t)(amax - amin) + 1, (uint64_t)nb), &ks, &vs);
     if (rc) return rc;
     hipLaunchKernelGGL(sd_unpack, dim3(blocks), dim3(DB_THREADS), 0, st, (const unsigned long long *)ks, (const unsigned *)vs,
-                       (const unsigned *)dy, (int)n, dxs, dys, dperm);
+                       (const unsigned *)W.in1, (int)n, W.xs, W.ys, W.aux);
     TDT_CHECK_LAUNCH();
     long long *dcnt = nullptr;
     if (runs_out || last_out) {
@@ -1093,39 +1099,29 @@ extern "C" int tdt_sort_dbscan_ex(tdt_ctx *ctx, const int64_t *posA, const int64
         rc = tdt_scratch(ctx, 6, (size_t)nb * 16 + 64, &dc);
         if (rc) return rc;
         dcnt = (long long *)dc;
-        if (runs_out) {                      // the x pass alone: its cluster_id is the number of x-runs - 1
-            rc = tdt_dbscan_device(ctx, dxs, dys, n, bucket_off, nb, db_eps_u64(eps), m, 1, dlab, (int64_t *)dcnt);
-            if (rc) return rc;
-        }
     }
-    rc = tdt_dbscan_device(ctx, dxs, dys, n, bucket_off, nb, db_eps_u64(eps), m, 0, dlab, dcnt ? (int64_t *)(dcnt + nb) : nullptr);
+    rc = sc_cluster_sorted(ctx, W.xs, W.ys, n, bucket_off, nb, eps, m, runs_out != nullptr, W.lab, dcnt);
     if (rc) return rc;
-    if (dcnt) {
-        std::vector<long long> hc((size_t)nb * 2);
-        TDT_HIP(hipMemcpyAsync(hc.data(), dcnt, (size_t)nb * 16, hipMemcpyDeviceToHost, st));
-        TDT_HIP(hipStreamSynchronize(st));
-        for (int b = 0; b < nb; b++) {
-            if (runs_out) runs_out[b] = hc[b] + 1;
-            if (last_out) last_out[b] = hc[nb + b];
-        }
-    }
-    // results come back through the pinned block (its input columns are consumed by now), labels as int32 (dv0 is free again), then go
+    // results come back through the pinned block (its input columns are consumed by now), labels as int32 (v0 is free again), then go
     // to the caller's arrays on the host threads
-    int *dlab32 = (int *)dv0;
-    hipLaunchKernelGGL(sd_labels_i32, dim3(blocks), dim3(DB_THREADS), 0, st, (const double *)dlab, (int)n, dlab32);
+    int *dlab32 = (int *)W.v0;
+    hipLaunchKernelGGL(sd_labels_i32, dim3(blocks), dim3(DB_THREADS), 0, st, (const double *)W.lab, (int)n, dlab32);
     TDT_CHECK_LAUNCH();
     int *hlab = (int *)h;
     uint32_t *hperm = (uint32_t *)((char *)h + n * 4);
+    std::vector<long long> hc;
     TDT_HIP(hipMemcpyAsync(hlab, dlab32, n * 4, hipMemcpyDeviceToHost, st));
-    TDT_HIP(hipMemcpyAsync(hperm, dperm, n * 4, hipMemcpyDeviceToHost, st));
+    TDT_HIP(hipMemcpyAsync(hperm, W.aux, n * 4, hipMemcpyDeviceToHost, st));
+    rc = sc_counts_fetch(ctx, dcnt, nb, hc);
+    if (rc) return rc;
     TDT_HIP(hipStreamSynchronize(st));
-    par([&](int, size_t i0, size_t i1) {
+    sc_counts_report(hc, nb, runs_out, last_out);
+    sc_host_ranges(n, nth, [&](int, size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; i++) labels_out[i] = (double)hlab[i];
         memcpy(perm_out + i0, hperm + i0, (i1 - i0) * 4);
     });
     return TDT_OK;
 }
-
 
 // ---- the same, without host passes: 32-bit columns in (straight from the parsed signal tables), int32 labels in SIGNAL order out.
 // Keys are (bucket << 32 | posA biased to unsigned); only the digits that can differ are sorted (max_pos bounds posA, e.g. the longest
@@ -1166,25 +1162,9 @@ static bool sc_is_pinned(const void *p) {
 
 extern "C" int tdt_cluster_columns(tdt_ctx *ctx, const int32_t *posA, const int32_t *posB, size_t n, const int64_t *bucket_off, int nb,
                                    double eps, int m, int64_t max_pos, int32_t *labels_by_signal, int64_t *runs_out, int64_t *last_out) {
-    if (!ctx || nb < 1 || !bucket_off || (n && (!posA || !posB || !labels_by_signal))) {
-        tdt_set_error("tdt_cluster_columns: bad argument");
-        return TDT_E_ARG;
-    }
-    if (m < 2) {
-        tdt_set_error("tdt_cluster_columns: m must be >= 2");
-        return TDT_E_ARG;
-    }
-    if (n >= 0x7fffffffull || bucket_off[0] != 0 || bucket_off[nb] != (int64_t)n) {
-        tdt_set_error("tdt_cluster_columns: bad bucket offsets / n");
-        return TDT_E_ARG;
-    }
-    if (n == 0) {
-        for (int b = 0; b < nb; b++) {
-            if (runs_out) runs_out[b] = 0;
-            if (last_out) last_out[b] = -1;
-        }
-        return TDT_OK;
-    }
+    bool empty = false;
+    int rc = sc_check("tdt_cluster_columns", ctx && (!n || (posA && posB && labels_by_signal)), n, bucket_off, nb, m, runs_out, last_out, &empty);
+    if (rc || empty) return rc;
     TDT_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream, cs = ctx->copy_stream;
     static const bool cc_timing = getenv("TIDDIT_CC_TIMING") != nullptr;          // host clock at the call's seams, to stderr
@@ -1194,23 +1174,11 @@ extern "C" int tdt_cluster_columns(tdt_ctx *ctx, const int32_t *posA, const int3
         if (cc_timing && ntm < 12) tm[ntm++] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
     };
     mark();
-    const size_t szN4 = db_align(n * 4), szN8 = db_align(n * 8);
-    void *d = nullptr;
-    int rc = tdt_scratch(ctx, 5, 7 * szN4 + 3 * szN8 + db_align((size_t)(nb + 1) * 4) + db_align((size_t)nb * 16 + 64) + 256, &d);
+    ScWork W;                                                 // aux: the int32 labels in signal order
+    rc = tdt_scratch_layout(ctx, 5, W, n, nb, true);
     if (rc) return rc;
-    char *p = (char *)d;
-    int *da = (int *)p; p += szN4;
-    int *db = (int *)p; p += szN4;
-    unsigned *dxs = (unsigned *)p; p += szN4;
-    unsigned *dys = (unsigned *)p; p += szN4;
-    unsigned *dv0 = (unsigned *)p; p += szN4;
-    unsigned *dv1 = (unsigned *)p; p += szN4;
-    int *dlab32 = (int *)p; p += szN4;
-    unsigned long long *dk = (unsigned long long *)p; p += szN8;
-    unsigned long long *dks = (unsigned long long *)p; p += szN8;
-    double *dlab = (double *)p; p += szN8;
-    int *dboff = (int *)p; p += db_align((size_t)(nb + 1) * 4);
-    long long *dcnt = (long long *)p;
+    const int *da = (const int *)W.in0, *db = (const int *)W.in1;
+    long long *dcnt = (runs_out || last_out) ? W.cnt : nullptr;
     // staging only for pageable caller memory
     mark();
     const bool pin_in = sc_is_pinned(posA) && sc_is_pinned(posB), pin_out = sc_is_pinned(labels_by_signal);
@@ -1224,66 +1192,52 @@ extern "C" int tdt_cluster_columns(tdt_ctx *ctx, const int32_t *posA, const int3
     for (int b = 0; b <= nb; b++) hboff[b] = (int)bucket_off[b];
     const int32_t *srcA = posA, *srcB = posB;
     if (!pin_in) {
-        const int nth = (int)std::max<size_t>(1, std::min<size_t>((size_t)tdt_host_thread_count(), n / (1u << 18) + 1));
-        std::vector<std::thread> th;
-        auto part = [&](int t) {
-            const size_t i0 = n * (size_t)t / nth, i1 = n * (size_t)(t + 1) / nth;
+        sc_host_ranges(n, sc_host_threads(n, 1u << 18), [&](int, size_t i0, size_t i1) {
             memcpy((int *)h + i0, posA + i0, (i1 - i0) * 4);
             memcpy((int *)h + n + i0, posB + i0, (i1 - i0) * 4);
-        };
-        for (int t = 1; t < nth; t++) th.emplace_back(part, t);
-        part(0);
-        for (auto &x : th) x.join();
+        });
         srcA = (const int32_t *)h;
         srcB = (const int32_t *)h + n;
     }
-    TDT_HIP(hipMemcpyAsync(dboff, hboff, (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(da, srcA, n * 4, hipMemcpyHostToDevice, st));
+    TDT_HIP(hipMemcpyAsync(W.boff, hboff, (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, st));
+    TDT_HIP(hipMemcpyAsync(W.in0, srcA, n * 4, hipMemcpyHostToDevice, st));
     // posB rides along with the sort of the posA digits — but only once posA has crossed: two copies in the same direction share the
     // link, and the sort waits for posA alone (started together both took 0.70 ms per 20 MB; in sequence posA is there after 0.36)
     TDT_HIP(hipEventRecord(ctx->ev[2], st));
     TDT_HIP(hipStreamWaitEvent(cs, ctx->ev[2], 0));
-    TDT_HIP(hipMemcpyAsync(db, srcB, n * 4, hipMemcpyHostToDevice, cs));
+    TDT_HIP(hipMemcpyAsync(W.in1, srcB, n * 4, hipMemcpyHostToDevice, cs));
     TDT_HIP(hipEventRecord(ctx->ev[3], cs));
     mark();
     const int blocks = ((int)n + DB_THREADS - 1) / DB_THREADS;
-    hipLaunchKernelGGL(sc_make_keys, dim3(blocks), dim3(DB_THREADS), 0, st, (const int *)da, (int)n, (const int *)dboff, nb, dk, dv0);
+    hipLaunchKernelGGL(sc_make_keys, dim3(blocks), dim3(DB_THREADS), 0, st, da, (int)n, (const int *)W.boff, nb, W.k0, W.v0);
     TDT_CHECK_LAUNCH();
-    const uint64_t span = max_pos > 0 && max_pos < 0x7fffffffll ? (uint64_t)max_pos + 1 : 0x80000000ull;
-    // biased keys: non-negative positions are 0x80000000 + pos, so the top bit is constant and only the span's digits differ
-    unsigned long long mask = (1ull << tdt_ceil_log2_u64(span)) - 1ull;
-    if (max_pos <= 0) mask = 0xffffffffull;                  // no bound given: all 32 bits (negative values included)
-    if (nb > 1) mask |= ((1ull << tdt_ceil_log2_u64((uint64_t)nb)) - 1ull) << 32;
+    // biased keys: non-negative positions are 0x80000000 + pos, so the top bit is constant and only the digits of the bound's span
+    // differ; no bound given: all 32 bits (negative values included)
+    const uint64_t span = max_pos <= 0 ? 1ull << 32 : max_pos < 0x7fffffffll ? (uint64_t)max_pos + 1 : 0x80000000ull;
     unsigned long long *ks = nullptr;
     unsigned *vs = nullptr;
-    rc = tdt_radix_sort_pairs(ctx, dk, dv0, dks, dv1, n, mask, &ks, &vs);
+    rc = tdt_radix_sort_pairs(ctx, W.k0, W.v0, W.k1, W.v1, n, tdt_sort_mask(span, (uint64_t)nb), &ks, &vs);
     if (rc) return rc;
     mark();
     TDT_HIP(hipStreamWaitEvent(st, ctx->ev[3], 0));
-    hipLaunchKernelGGL(sc_unpack, dim3(blocks), dim3(DB_THREADS), 0, st, (const unsigned long long *)ks, (const unsigned *)vs, (const int *)db, (int)n,
-                       dxs, dys);
+    hipLaunchKernelGGL(sc_unpack, dim3(blocks), dim3(DB_THREADS), 0, st, (const unsigned long long *)ks, (const unsigned *)vs, db, (int)n, W.xs, W.ys);
     TDT_CHECK_LAUNCH();
-    if (runs_out) {
-        rc = tdt_dbscan_device(ctx, dxs, dys, n, bucket_off, nb, db_eps_u64(eps), m, 1, dlab, (int64_t *)dcnt);
-        if (rc) return rc;
-    }
-    rc = tdt_dbscan_device(ctx, dxs, dys, n, bucket_off, nb, db_eps_u64(eps), m, 0, dlab, (runs_out || last_out) ? (int64_t *)(dcnt + nb) : nullptr);
+    rc = sc_cluster_sorted(ctx, W.xs, W.ys, n, bucket_off, nb, eps, m, runs_out != nullptr, W.lab, dcnt);
     if (rc) return rc;
     mark();
-    hipLaunchKernelGGL(sc_scatter_labels, dim3(blocks), dim3(DB_THREADS), 0, st, (const double *)dlab, (const unsigned *)vs, (int)n, dlab32);
+    int *dlab32 = (int *)W.aux;
+    hipLaunchKernelGGL(sc_scatter_labels, dim3(blocks), dim3(DB_THREADS), 0, st, (const double *)W.lab, (const unsigned *)vs, (int)n, dlab32);
     TDT_CHECK_LAUNCH();
     int *dst = pin_out ? labels_by_signal : (int *)h;
     TDT_HIP(hipMemcpyAsync(dst, dlab32, n * 4, hipMemcpyDeviceToHost, st));
-    std::vector<long long> hc((size_t)nb * 2);
-    if (runs_out || last_out) TDT_HIP(hipMemcpyAsync(hc.data(), dcnt, (size_t)nb * 16, hipMemcpyDeviceToHost, st));
+    std::vector<long long> hc;
+    rc = sc_counts_fetch(ctx, dcnt, nb, hc);
+    if (rc) return rc;
     mark();
     TDT_HIP(hipStreamSynchronize(st));
     mark();
     if (!pin_out) memcpy(labels_by_signal, h, n * 4);
-    for (int b = 0; b < nb; b++) {
-        if (runs_out) runs_out[b] = hc[b] + 1;
-        if (last_out) last_out[b] = hc[nb + b];
-    }
+    sc_counts_report(hc, nb, runs_out, last_out);
     if (cc_timing) {
         fprintf(stderr, "tdt_cluster_columns n=%zu nb=%d us:", n, nb);
         for (int i = 1; i < ntm; i++) fprintf(stderr, " %.0f", tm[i] - tm[i - 1]);

@@ -21,10 +21,6 @@
 
 typedef unsigned long long ull;
 
-int tdt_radix_sort_pairs(tdt_ctx *ctx, ull *keys, unsigned *vals, ull *keys_tmp, unsigned *vals_tmp, size_t n, ull bitmask, ull **out_keys,
-                         unsigned **out_vals);                                             // tdt_sort.hip
-int tdt_scan_u32_inclusive(tdt_ctx *ctx, unsigned *d_v, int n, unsigned *d_tsum);        // tdt_dbscan.hip
-
 #define YS_THREADS 256
 
 __global__ __launch_bounds__(YS_THREADS) void ys_keys(const unsigned *__restrict__ y, const int *__restrict__ seg, int n, ull *__restrict__ key,
@@ -89,6 +85,28 @@ __global__ __launch_bounds__(YS_THREADS) void ys_final(const ull *__restrict__ k
     out[i] = r;
 }
 
+// slot 5 of this entry: the members' columns as they arrive, the result, the sort's pairs, the two scanned arrays, per segment its
+// bounds and extra sub-runs, the tile sums of the scans (over members, then over segments) and the last id
+struct YsWork {
+    unsigned *y;
+    int *seg;
+    double *keep, *out;
+    ull *k0, *k1;
+    unsigned *v0, *v1, *P, *S;
+    int *lo, *hi;
+    unsigned *ex, *exi, *ts;
+    long long *last;
+    size_t lay(void *base, size_t N, size_t G, size_t tiles) {
+        tdt_carver c(base);
+        y = c.take<unsigned>(N), seg = c.take<int>(N), keep = c.take<double>(N), out = c.take<double>(N);
+        k0 = c.take<ull>(N), k1 = c.take<ull>(N), v0 = c.take<unsigned>(N), v1 = c.take<unsigned>(N);
+        P = c.take<unsigned>(N), S = c.take<unsigned>(N);
+        lo = c.take<int>(G + 1), hi = c.take<int>(G + 1), ex = c.take<unsigned>(G + 1), exi = c.take<unsigned>(G + 1);
+        ts = c.take<unsigned>(tiles + 16), last = c.take<long long>(8);
+        return c.size;
+    }
+};
+
 extern "C" int tdt_dbscan_y_segments(tdt_ctx *ctx, const int64_t *y, const int32_t *seg, const double *keep, size_t n_, int nseg, double eps,
                                      int m, int64_t cluster_id, double *out, int64_t *last_id) {
     if (!ctx || nseg < 0 || (n_ && (!y || !seg || !keep || !out))) {
@@ -115,42 +133,19 @@ extern "C" int tdt_dbscan_y_segments(tdt_ctx *ctx, const int64_t *y, const int32
             return TDT_E_ARG;
         }
     }
-    if ((unsigned __int128)((__int128)ymax - ymin) > 0xfffffffeull) {
-        tdt_set_error("tdt_dbscan_y_segments: coordinate span >= 2^32 is outside the device path's domain");
-        return TDT_E_UNSUPPORTED;
-    }
-    // numpy: int64 distance < python number  <=>  d < ceil(eps) for integer d >= 0
-    ull e = 0;
-    if (eps > 0) e = eps >= 8589934592.0 ? (1ull << 33) : (ull)std::ceil(eps);
+    int rc = tdt_check_span("tdt_dbscan_y_segments", ymin, ymax);
+    if (rc) return rc;
+    const ull e = tdt_eps_u64(eps);
     TDT_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t N = (size_t)n, G = (size_t)nseg;
-    void *h = nullptr, *d = nullptr;
-    int rc = tdt_pinned(ctx, 1, N * 16 + 64, &h);
+    void *h = nullptr;
+    rc = tdt_pinned(ctx, 1, N * 16 + 64, &h);
     if (rc) return rc;
     const int ntile = (n + 1023) / 1024 + 1, gtile = (nseg + 1023) / 1024 + 1;
-    const size_t total = 2 * al(N * 4) /*y, seg*/ + 2 * al(N * 8) /*keep, out*/ + 2 * al(N * 8) /*keys*/ + 2 * al(N * 4) /*vals*/ + 2 * al(N * 4) /*P,S*/ +
-                         4 * al(G * 4 + 4) /*lo, hi, extras, extras_incl*/ + al((size_t)(ntile + gtile) * 4 + 64) + 256;
-    rc = tdt_scratch(ctx, 5, total, &d);
+    YsWork W;
+    rc = tdt_scratch_layout(ctx, 5, W, N, G, (size_t)(ntile + gtile));
     if (rc) return rc;
-    char *p = (char *)d;
-    auto carve = [&](size_t b) {
-        void *r = p;
-        p += al(b);
-        return r;
-    };
-    unsigned *dy = (unsigned *)carve(N * 4);
-    int *dseg = (int *)carve(N * 4);
-    double *dkeep = (double *)carve(N * 8);
-    double *dout = (double *)carve(N * 8);
-    ull *dk0 = (ull *)carve(N * 8), *dk1 = (ull *)carve(N * 8);
-    unsigned *dv0 = (unsigned *)carve(N * 4), *dv1 = (unsigned *)carve(N * 4);
-    unsigned *dP = (unsigned *)carve(N * 4), *dS = (unsigned *)carve(N * 4);
-    int *dlo = (int *)carve(G * 4 + 4), *dhi = (int *)carve(G * 4 + 4);
-    unsigned *dex = (unsigned *)carve(G * 4 + 4), *dexi = (unsigned *)carve(G * 4 + 4);
-    unsigned *dts = (unsigned *)carve((size_t)(ntile + gtile) * 4 + 64);
-    long long *dlast = (long long *)carve(64);
     TDT_HIP(hipStreamSynchronize(st));                      // an earlier call may still be reading the pinned block
     unsigned *hy = (unsigned *)h;
     int *hs = (int *)(hy + N);
@@ -160,40 +155,38 @@ extern "C" int tdt_dbscan_y_segments(tdt_ctx *ctx, const int64_t *y, const int32
         hs[i] = seg[i];
         hk[i] = keep[i];
     }
-    TDT_HIP(hipMemcpyAsync(dy, hy, N * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(dseg, hs, N * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(dkeep, hk, N * 8, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemsetAsync(dlo, 0, al(G * 4 + 4) * 2, st));                  // segments without members: lo = hi = 0
+    TDT_HIP(hipMemcpyAsync(W.y, hy, N * 4, hipMemcpyHostToDevice, st));
+    TDT_HIP(hipMemcpyAsync(W.seg, hs, N * 4, hipMemcpyHostToDevice, st));
+    TDT_HIP(hipMemcpyAsync(W.keep, hk, N * 8, hipMemcpyHostToDevice, st));
+    TDT_HIP(hipMemsetAsync(W.lo, 0, (char *)W.ex - (char *)W.lo, st));     // lo and hi; segments without members: lo = hi = 0
     const int blocks = (n + YS_THREADS - 1) / YS_THREADS;
-    hipLaunchKernelGGL(ys_keys, dim3(blocks), dim3(YS_THREADS), 0, st, (const unsigned *)dy, (const int *)dseg, n, dk0, dv0);
+    hipLaunchKernelGGL(ys_keys, dim3(blocks), dim3(YS_THREADS), 0, st, (const unsigned *)W.y, (const int *)W.seg, n, W.k0, W.v0);
     TDT_CHECK_LAUNCH();
-    ull mask = ymax > ymin ? ((1ull << tdt_ceil_log2_u64((uint64_t)(ymax - ymin) + 1)) - 1ull) : 0ull;
-    if (nseg > 1) mask |= ((1ull << tdt_ceil_log2_u64((uint64_t)nseg)) - 1ull) << 32;
     ull *ks = nullptr;
     unsigned *vs = nullptr;
-    rc = tdt_radix_sort_pairs(ctx, dk0, dv0, dk1, dv1, N, mask, &ks, &vs);
+    rc = tdt_radix_sort_pairs(ctx, W.k0, W.v0, W.k1, W.v1, N, tdt_sort_mask((uint64_t)(ymax - ymin) + 1, G), &ks, &vs);
     if (rc) return rc;
-    hipLaunchKernelGGL(ys_flags, dim3(blocks), dim3(YS_THREADS), 0, st, (const ull *)ks, n, m, e, dP, dS, dlo, dhi);
+    hipLaunchKernelGGL(ys_flags, dim3(blocks), dim3(YS_THREADS), 0, st, (const ull *)ks, n, m, e, W.P, W.S, W.lo, W.hi);
     TDT_CHECK_LAUNCH();
-    rc = tdt_scan_u32_inclusive(ctx, dP, n, dts);
+    rc = tdt_scan_u32_inclusive(ctx, W.P, n, W.ts);
     if (rc) return rc;
-    rc = tdt_scan_u32_inclusive(ctx, dS, n, dts);
+    rc = tdt_scan_u32_inclusive(ctx, W.S, n, W.ts);
     if (rc) return rc;
     if (nseg) {
-        hipLaunchKernelGGL(ys_extras, dim3((nseg + YS_THREADS - 1) / YS_THREADS), dim3(YS_THREADS), 0, st, (const unsigned *)dS, (const int *)dlo,
-                           (const int *)dhi, nseg, dex);
+        hipLaunchKernelGGL(ys_extras, dim3((nseg + YS_THREADS - 1) / YS_THREADS), dim3(YS_THREADS), 0, st, (const unsigned *)W.S, (const int *)W.lo,
+                           (const int *)W.hi, nseg, W.ex);
         TDT_CHECK_LAUNCH();
-        TDT_HIP(hipMemcpyAsync(dexi, dex, G * 4, hipMemcpyDeviceToDevice, st));
-        rc = tdt_scan_u32_inclusive(ctx, dexi, nseg, dts + ntile);
+        TDT_HIP(hipMemcpyAsync(W.exi, W.ex, G * 4, hipMemcpyDeviceToDevice, st));
+        rc = tdt_scan_u32_inclusive(ctx, W.exi, nseg, W.ts + ntile);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(ys_final, dim3(blocks), dim3(YS_THREADS), 0, st, (const ull *)ks, (const unsigned *)vs, n, m, (const unsigned *)dP,
-                       (const unsigned *)dS, (const int *)dlo, (const unsigned *)dexi, (const unsigned *)dex, nseg, (const double *)dkeep,
-                       (long long)cluster_id, dout, dlast);
+    hipLaunchKernelGGL(ys_final, dim3(blocks), dim3(YS_THREADS), 0, st, (const ull *)ks, (const unsigned *)vs, n, m, (const unsigned *)W.P,
+                       (const unsigned *)W.S, (const int *)W.lo, (const unsigned *)W.exi, (const unsigned *)W.ex, nseg, (const double *)W.keep,
+                       (long long)cluster_id, W.out, W.last);
     TDT_CHECK_LAUNCH();
     long long lid = cluster_id;
-    TDT_HIP(hipMemcpyAsync(out, dout, N * 8, hipMemcpyDeviceToHost, st));
-    TDT_HIP(hipMemcpyAsync(&lid, dlast, 8, hipMemcpyDeviceToHost, st));
+    TDT_HIP(hipMemcpyAsync(out, W.out, N * 8, hipMemcpyDeviceToHost, st));
+    TDT_HIP(hipMemcpyAsync(&lid, W.last, 8, hipMemcpyDeviceToHost, st));
     TDT_HIP(hipStreamSynchronize(st));
     if (last_id) *last_id = lid;
     return TDT_OK;

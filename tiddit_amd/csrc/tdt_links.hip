@@ -12,8 +12,6 @@
 #include "tdt_search.h"
 
 typedef unsigned long long ull;
-int tdt_radix_sort_pairs(tdt_ctx *ctx, ull *keys, unsigned *vals, ull *keys_tmp, unsigned *vals_tmp, size_t n, ull bitmask, ull **out_keys,
-                         unsigned **out_vals);
 
 #define LK_POS_BITS 30
 #define LK_POS_MASK ((1 << LK_POS_BITS) - 1)
@@ -176,11 +174,9 @@ extern "C" int tdt_links_create(tdt_ctx *ctx, const int32_t *posA, const int32_t
             // only the bits that can differ are sorted: the posA span and the bucket index.  tdt_radix_sort_pairs rebuilds the high key
             // word from keys[0] when no mask bit lies above bit 31 (its narrow mode): that is the case here only for nb <= 1, where
             // every key's high word is the one bucket index 0 — equal in all keys, as the sort requires.
-            ull mask = amax > amin ? ((1ull << tdt_ceil_log2_u64((uint64_t)(amax - amin) + 1)) - 1ull) : 0ull;
-            if (nb > 1) mask |= ((1ull << tdt_ceil_log2_u64((uint64_t)nb)) - 1ull) << 32;
             ull *ks = nullptr;
             unsigned *vs = nullptr;
-            int r = tdt_radix_sort_pairs(ctx, dk0, dv0, dk1, dv1, n, mask, &ks, &vs);
+            int r = tdt_radix_sort_pairs(ctx, dk0, dv0, dk1, dv1, n, tdt_sort_mask((uint64_t)(amax - amin) + 1, (uint64_t)nb), &ks, &vs);
             if (r) return r;
             hipLaunchKernelGGL(lk_pack, dim3(blocks), dim3(256), 0, st, (const ull *)ks, (const unsigned *)vs, (const int32_t *)db,
                                (const uint8_t *)dkind, (int)n, amin, h->rec);

@@ -169,7 +169,6 @@ extern "C" int tdt_signal_select(tdt_ctx *ctx, const uint16_t *flag, const uint8
 //   bit 3 (8): a discordant-pair row is appended (:204-221)
 // — the reads with any bit set compacted in stream order, and everything the host needs to build their rows (fields, raw record
 // bytes: names, CIGARs, sequences, SA strings) gathered into compact arrays, so that the host touches only those few per cent.
-int tdt_scan_u32_inclusive(tdt_ctx *ctx, unsigned *d_v, int n, unsigned *d_tsum);   // tdt_dbscan.hip
 
 struct ScanParams {
     const uint16_t *flag;

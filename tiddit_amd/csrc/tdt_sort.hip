@@ -258,8 +258,7 @@ static RsPlan rs_plan(ull bitmask) {
     return plan;
 }
 
-// Sort n pairs by the key bits selected in `bitmask`; the key bits outside it must be equal in all keys (they are: callers pass the
-// mask of the bits that can differ).  keys/vals and the *_tmp buffers ping-pong; the final location is returned through out_keys/out_vals.
+// Sort n pairs by the key bits selected in `bitmask` (contract and precondition: at the declaration in tdt_common.h).
 int tdt_radix_sort_pairs(tdt_ctx *ctx, ull *keys, unsigned *vals, ull *keys_tmp, unsigned *vals_tmp, size_t n_, ull bitmask,
                          ull **out_keys, unsigned **out_vals) {
     *out_keys = keys;

@@ -22,7 +22,6 @@
 
 typedef unsigned long long ull;
 
-int tdt_scan_u32_inclusive(tdt_ctx *ctx, unsigned *d_v, int n, unsigned *d_tsum);                                   // tdt_dbscan.hip
 int tdt_np_sum_device(tdt_ctx *ctx, const double *d_a, size_t n, double *d_csums, double *d_out);                   // tdt_means.hip
 
 #define ST_THREADS 256
