@@ -381,6 +381,18 @@ int tdt_region_counts_packed(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contig
 int tdt_region_counts_packed_device(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *d_queries,
                                     size_t nq, int min_q, int64_t max_ins, int64_t *d_out);
 
+/* ---- per-contig depth distributions from the evidence store (TIDDIT_DEPTH_DIST) ------------------------------- *
+ * The depth of base b (0 <= b < LN) of a contig is the number of its records with none of TDT_EV_UNMAPPED, TDT_EV_DUPLICATE,
+ * TDT_EV_LOW_Q and start <= b < min(end, LN) — the store's end is the exclusive reference end; a record with end <= start covers
+ * nothing.  contigs = int64[n_contigs][5] (offset, n, max span, tid, contig length), the table of tdt_region_counts_packed, validated
+ * the same way; out = int64[n_contigs][cap + 4] on the host, per row: the bases at depth exactly d for d < cap, the bases at depth
+ * cap or more, the uncapped sum of all depths, the maximum depth, the minimum depth (a row of no records: out[0] = LN, the rest 0).
+ * One launch over all contigs, one workgroup per tile of DD_TILE bases: a difference array and a histogram in LDS, 64-bit atomics
+ * into the contig's row (csrc/tdt_depth_dist.hip).  cap must be the library's DD_CAP (1000).  TDT_E_ARG for a null pointer or another
+ * cap, TDT_E_RANGE for a row outside the store, a negative length or 2^31 - 1 tiles or more — all before anything is launched, the
+ * output untouched; n_contigs == 0 returns TDT_OK.  The context's stream is synchronised before the return. */
+int tdt_depth_dist(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, int cap, int64_t *out);
+
 /* ---- order statistics for the depth fold-changes of genotyped sites (TIDDIT_GENOTYPE_DEPTH) ------------ *
  * cov / gc are the concatenated float64 coverage bins / int8 GC bins (n of them, n < 2^31 - 1; coverage is non-negative, -0.0 reads
  * as +0.0).  Radix select on the bit patterns (csrc/tdt_depth.hip): lower / upper are the two middle order statistics (equal for an

@@ -19,6 +19,10 @@ histogram is filled beside the 50-bp one, and no second job reads and inflates t
 ``TIDDIT_GENOTYPE=sites.vcf``: ``--sv`` also writes ``{o}.genotyped.vcf`` — every record of ``sites.vcf`` with this sample's
 ``GT:CN:COV:DV:RV:LQ:RR:DR`` (tiddit_amd/tiddit_genotype.py) — from the evidence store and the signal tables the scan left, with or
 without ``TIDDIT_VARIANTS=1``.  One process only: on N ranks the switch is refused before anything is started.
+
+``TIDDIT_DEPTH_DIST=1``: ``--sv`` also writes ``{o}.depth_dist.tab`` and ``{o}.depth_summary.tab`` — per contig and in total, the bases
+covered at exactly d x and at d x or more, and the mean / min / max depth per base (tiddit_amd/tiddit_depth_dist.py) — from the evidence
+store in one launch behind the candidates table.  One process only, refused on N ranks like ``TIDDIT_GENOTYPE``.
 """
 import argparse
 import os
@@ -194,6 +198,13 @@ def run_sv(args, version):
     except ValueError as e:
         print("error, TIDDIT_COV_TRACK={}: {}".format(os.environ.get("TIDDIT_COV_TRACK"), e))
         quit()
+    try:
+        from . import tiddit_depth_dist
+        depth_dist = tiddit_depth_dist.parse_switch(os.environ.get("TIDDIT_DEPTH_DIST"))
+    except ValueError as e:
+        # (before anything is read or made: no {o}_tiddit is left behind)
+        print("error, TIDDIT_DEPTH_DIST={}: {}".format(os.environ.get("TIDDIT_DEPTH_DIST"), e))
+        sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
     if genotype_depth and sites_path is None:
@@ -241,6 +252,11 @@ def run_sv(args, version):
     if multi and sites_path is not None:
         # (every rank, before the first collective: no rank is left waiting for another)
         print("error, TIDDIT_GENOTYPE is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) does not genotype sites")
+        sys.exit(1)
+    if multi and depth_dist:
+        # (the same: a base near a shard seam is covered by two shards' reads, and per-shard histograms of depth do not add up)
+        print("error, TIDDIT_DEPTH_DIST is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
+              "reads on another rank")
         sys.exit(1)
     if multi:
         import torch
@@ -381,7 +397,8 @@ def run_sv(args, version):
     # TIDDIT_VARIANTS=1: the scan also packs every placed record into the evidence store the native variant stage reads (on N ranks:
     # every rank the records of its own shard)
     # TIDDIT_GENOTYPE needs the same store, with or without the variant stage
-    tiddit_signal.KEEP_EVIDENCE = os.environ.get("TIDDIT_VARIANTS") == "1" or genotype_job is not None
+    # ... and so does TIDDIT_DEPTH_DIST
+    tiddit_signal.KEEP_EVIDENCE = os.environ.get("TIDDIT_VARIANTS") == "1" or genotype_job is not None or depth_dist
     if track is not None:
         # TIDDIT_COV_TRACK: the scan fills a second histogram — every contig, the track's bin size and mapq cut — from the same batches
         tiddit_signal.COV_TRACK = (track[0], track[1])
@@ -416,7 +433,7 @@ def run_sv(args, version):
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,
-                    genotype_job)
+                    genotype_job, depth_dist)
     except BaseException:
         # no helper thread outlives the error: the writer thread of BACKGROUND_WRITES is joined (its own error, if any, is not the one to report)
         try:
@@ -432,9 +449,9 @@ def run_sv(args, version):
 
 
 def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, contigs, contig_length, samples, library, coverage_data, bam_header,
-                max_ins_len, min_mapq, sample_id, version, contig_number, own_group, genotype_job=None):
-    """run_sv behind the BAM scan: GC bins, ploidy table, clustering, candidates table, the signal files complete, the variant stage
-    (TIDDIT_VARIANTS=1), the genotypes of known sites (TIDDIT_GENOTYPE)"""
+                max_ins_len, min_mapq, sample_id, version, contig_number, own_group, genotype_job=None, depth_dist=False):
+    """run_sv behind the BAM scan: GC bins, ploidy table, clustering, candidates table, the signal files complete, the depth
+    distributions (TIDDIT_DEPTH_DIST=1), the variant stage (TIDDIT_VARIANTS=1), the genotypes of known sites (TIDDIT_GENOTYPE)"""
     from . import tiddit_cluster, tiddit_coverage_analysis, tiddit_gc, tiddit_signal
     from .trace import stage
     if multi:
@@ -492,6 +509,17 @@ def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, con
     if tiddit_signal.WRITE_SECONDS:
         T["signal files placed (writer thread, beside ploidy and clustering)"] = tiddit_signal.WRITE_SECONDS["writer thread"]
         T["  waited for the writer thread"] = tiddit_signal.WRITE_SECONDS["waited for it"]
+    if depth_dist:
+        # TIDDIT_DEPTH_DIST: one launch over the store the scan left, which stays where it is for the stages below (a store nobody
+        # takes afterwards is freed by run_sv)
+        from . import tiddit_depth_dist, tiddit_variant
+        if tiddit_variant.LIVE_STORE is None:
+            raise RuntimeError("TIDDIT_DEPTH_DIST: the scan left no evidence store")
+        t = time.time()
+        with stage("tiddit: depth distribution"):
+            tiddit_depth_dist.main(tiddit_variant.LIVE_STORE, prefix, chromosomes, [contig_length[c] for c in chromosomes])
+        T["depth distribution ({o}.depth_dist.tab, {o}.depth_summary.tab)"] = time.time() - t
+        T.update({"  " + k: v for k, v in tiddit_depth_dist.STAGE_SECONDS.items()})
     if os.environ.get("TIDDIT_VARIANTS") == "1":
         # the native variant stage (tiddit_variant.py over the evidence store the scan filled, tiddit_vcf_header.py): {prefix}.vcf.  On N
         # ranks every rank takes part (the counts over its shard's store); rank 0 types the variants and writes the file.

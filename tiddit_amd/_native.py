@@ -119,6 +119,7 @@ SYMBOLS = {
     "tdt_evstore_spans": (_i, [_P, _P]),
     "tdt_region_counts_packed": (_i, [_P, _P, _P, _i, _P, _sz, _i, _i64, _P]),
     "tdt_region_counts_packed_device": (_i, [_P, _P, _P, _i, _P, _sz, _i, _i64, _P]),
+    "tdt_depth_dist": (_i, [_P, _P, _P, _i, _i, _P]),
     "tdt_links_create": (_i, [_P, _P, _P, _P, _P, _i, _PP]),
     "tdt_links_destroy": (_i, [_P]),
     "tdt_links_count": (_i, [_P, _P, _sz, _P]),

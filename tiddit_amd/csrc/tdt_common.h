@@ -32,7 +32,7 @@ struct tdt_buf {
     size_t cap = 0;
 };
 
-enum { TDT_NSCRATCH = 28, TDT_NPINNED = 4 };
+enum { TDT_NSCRATCH = 29, TDT_NPINNED = 4 };
 
 struct tdt_ctx {
     int device = 0;
@@ -101,6 +101,18 @@ static inline unsigned long long tdt_sort_mask(uint64_t lo_values, uint64_t hi_v
 }
 // tdt_dbscan.hip.  In-place inclusive scan of d_v[0..n); d_tsum: ceil(n / 1024) words of scratch.
 int tdt_scan_u32_inclusive(tdt_ctx *ctx, unsigned *d_v, int n, unsigned *d_tsum);
+// tdt_region.hip.  The evidence store: every placed record of the scan as int4 {start, end, mate_pos, bits}, in file order.
+struct tdt_evstore {
+    tdt_ctx *ctx;
+    int n_contigs;
+    int min_q;
+    long long max_ins;
+    int4 *rec;
+    size_t n, cap;
+    int *d_span;      // per contig: max(end - start) over its records (atomicMax in the pack kernel)
+};
+// every row {offset, n, max span, tid, contig length} of a contig table lies inside the store, else TDT_E_RANGE naming `fn`
+int tdt_evstore_check_rows(const char *fn, const tdt_evstore *s, const int64_t *contigs, int n_contigs);
 
 // ---- what every clustering entry of host int64 columns applies: device coordinates are uint32 offsets from the column minimum
 static inline int tdt_check_span(const char *who, int64_t lo, int64_t hi) {

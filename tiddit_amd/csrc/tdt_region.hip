@@ -161,15 +161,7 @@ extern "C" int tdt_region_counts(tdt_ctx *ctx, const int32_t *start, const int32
 // One record = int4 {start, end, mate_pos, bits}; bits (low byte; the three upper bytes are zero padding) carry every predicate of
 // get_region that does not depend on the query: the flag bits it tests, the SA tag, and the two comparisons against the scan's own
 // min_q / max_ins.  A coordinate-sorted file appends each contig as one contiguous, sorted range.
-struct tdt_evstore {
-    tdt_ctx *ctx;
-    int n_contigs;
-    int min_q;
-    long long max_ins;
-    int4 *rec;
-    size_t n, cap;
-    int *d_span;      // per contig: max(end - start) over its records (atomicMax in the pack kernel)
-};
+// (struct tdt_evstore: tdt_common.h — the depth distribution, tdt_depth_dist.hip, reads the same records)
 
 __global__ __launch_bounds__(256) void evidence_pack(const int32_t *__restrict__ tid, const int32_t *__restrict__ pos,
                                                      const int32_t *__restrict__ end, const uint8_t *__restrict__ mapq,
@@ -408,13 +400,8 @@ __global__ __launch_bounds__(256) void region_counts_packed(const int4 *__restri
     }
 }
 
-// the checks both entries make on the host: the store's parameters, and every contig row inside the store
-static int packed_check(const char *fn, tdt_evstore *s, const int64_t *contigs, int n_contigs, int min_q, int64_t max_ins) {
-    if (min_q != s->min_q || (long long)max_ins != s->max_ins) {
-        tdt_set_error("%s: the store was packed with min_q %d / max_ins %lld, the queries ask for %d / %lld", fn, s->min_q, s->max_ins,
-                      min_q, (long long)max_ins);
-        return TDT_E_ARG;
-    }
+// every contig row of a table inside the store (what every kernel over the store is allowed to touch)
+int tdt_evstore_check_rows(const char *fn, const tdt_evstore *s, const int64_t *contigs, int n_contigs) {
     for (int c = 0; c < n_contigs; c++) {          // every range the kernel may touch lies inside the store
         const int64_t *C = contigs + 5 * (size_t)c;
         if (C[0] < 0 || C[1] < 0 || C[1] >= 0x7fffffffll || (size_t)(C[0] + C[1]) > s->n || C[2] < 0 || C[4] < 0) {
@@ -424,6 +411,16 @@ static int packed_check(const char *fn, tdt_evstore *s, const int64_t *contigs, 
         }
     }
     return TDT_OK;
+}
+
+// the checks both entries make on the host: the store's parameters, and every contig row inside the store
+static int packed_check(const char *fn, tdt_evstore *s, const int64_t *contigs, int n_contigs, int min_q, int64_t max_ins) {
+    if (min_q != s->min_q || (long long)max_ins != s->max_ins) {
+        tdt_set_error("%s: the store was packed with min_q %d / max_ins %lld, the queries ask for %d / %lld", fn, s->min_q, s->max_ins,
+                      min_q, (long long)max_ins);
+        return TDT_E_ARG;
+    }
+    return tdt_evstore_check_rows(fn, s, contigs, n_contigs);
 }
 
 extern "C" int tdt_region_counts_packed(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *queries,

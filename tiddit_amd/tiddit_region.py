@@ -277,6 +277,17 @@ class EvidenceStore:
         _native.check(ctx.lib.tdt_region_counts_packed_device(ctx.handle, self.handle, _native.ptr(tab), len(tab), d_queries, int(nq),
                                                               int(min_q), int(max_ins), d_out))
 
+    def depth_dist(self, table=None, ctx=None):
+        """-> int64[n_contigs, DD_CAP + 4] in header order (rows of ``table`` when one is given): the bases at depth exactly d for
+        d < DD_CAP, the bases at DD_CAP or more, the uncapped sum of depths, the maximum and the minimum depth — per base, from the
+        records' exact start / end, all contigs in ONE launch (tiddit_depth_dist.py has the definition)."""
+        from .tiddit_depth_dist import DD_CAP
+        ctx = ctx or self.ctx
+        tab = numpy.ascontiguousarray(self.contig_table() if table is None else table, dtype=numpy.int64).reshape(-1, 5)
+        out = numpy.zeros((len(tab), DD_CAP + 4), dtype=numpy.int64)
+        _native.check(ctx.lib.tdt_depth_dist(ctx.handle, self.handle, _native.ptr(tab), len(tab), DD_CAP, _native.ptr(out)))
+        return out
+
     def close(self):
         if getattr(self, "handle", None):
             self.ctx.lib.tdt_evstore_destroy(self.handle)
