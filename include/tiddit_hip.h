@@ -417,6 +417,34 @@ int tdt_gc_class_medians(tdt_ctx *ctx, const double *cov, const int8_t *gc, int6
 int tdt_gc_class_medians_device(tdt_ctx *ctx, const double *d_cov, const int8_t *d_gc, int64_t n, const int64_t *seg, int nseg,
                                 double *d_lower, double *d_upper, int64_t *d_count);
 
+/* ---- copy-number segments from the depth bins (TIDDIT_CNV; tiddit_amd/tiddit_cnv.py has the definition) ------------- *
+ * tdt_cnv_bins: cov / gc are the concatenated float64 coverage bins / int8 GC bins of the processed contigs (n of them, n < 2^31 - 1);
+ * table = int64[nseg][5] rows {off, nb, K, P, toff} (a HOST array in both entries): the contig's bins off .. off + nb - 1, K of them
+ * (1 .. 64) to a CNV bin, its ploidy P (1 .. 6), and toff = the index of its first CNV bin in x, which must be the sum of
+ * ceil(nb / K) over the rows before it.  E = float64[nseg][101]: the expected depth of a 50-bp bin of GC class g of row s.  CNV bin
+ * t of a row covers its bins tK .. min((t + 1)K, nb) - 1; the usable ones have gc in 0 .. 100 (n_t of them).  2 n_t < K: x = -1.
+ * Otherwise x = min(8 unit, (int)rint((obs / exp) * (double)(P unit))) with obs / exp the float64 sums of cov / E[s][gc] over the
+ * usable bins, added left to right by one lane.  x = int32[sum of ceil(nb / K)].
+ * tdt_cnv_viterbi: x as above (x < 0 = masked), n = its length; table = int64[nseg][3] rows {toff, T, P} (HOST), contiguous from 0
+ * and summing to n, P in 0 .. 7.  state = int8[n]: for every row the minimum-cost path over the states 0 .. 7 of the chain
+ * V_0(k) = e_0(k) + (k == P ? 0 : lambda), V_t(k) = e_t(k) + min(V_{t-1}(k), min_i V_{t-1}(i) + lambda), e_t(k) =
+ * min(cap, (x_t - unit k)^2) or 0 for a masked bin, end cost V_{T-1}(k) + (k == P ? 0 : lambda); ties go to staying
+ * (V_{t-1}(k) <= m + lambda) and to the lowest state.  int64 costs; the chain is cut into chunks of CNV_CHUNK bins whose (min,+)
+ * matrices are stitched, which gives the sequential result exactly (csrc/tdt_cnv.hip).  unit in 1 .. 2^20, cap and lambda in
+ * 0 .. 2^28.  All contigs in one call.
+ * All four: TDT_E_ARG for a null context, a negative count, a parameter outside its range and — unless n == 0 or nseg == 0, which
+ * return TDT_OK — a null or misaligned pointer (8 bytes for float64 / int64, 4 for int32); TDT_E_RANGE for a row outside the
+ * arrays or not following the row before it; all before anything is launched, the outputs untouched.  The _device entries take
+ * cov, gc, E, x, state in HBM.  The context's stream is synchronised before the return. */
+int tdt_cnv_bins(tdt_ctx *ctx, const double *cov, const int8_t *gc, int64_t n, const int64_t *table, int nseg, const double *E, int unit,
+                 int32_t *x);
+int tdt_cnv_bins_device(tdt_ctx *ctx, const double *d_cov, const int8_t *d_gc, int64_t n, const int64_t *table, int nseg, const double *d_E,
+                        int unit, int32_t *d_x);
+int tdt_cnv_viterbi(tdt_ctx *ctx, const int32_t *x, int64_t n, const int64_t *table, int nseg, int unit, int64_t cap, int64_t lambda,
+                    int8_t *state);
+int tdt_cnv_viterbi_device(tdt_ctx *ctx, const int32_t *d_x, int64_t n, const int64_t *table, int nseg, int unit, int64_t cap, int64_t lambda,
+                           int8_t *d_state);
+
 /* ---- link counts of SV sites (TIDDIT_GENOTYPE) ------------------------------------------------------- *
  * How many signals of the cluster table join the two regions of a site: for site {bucket, startA, endA, startB, endB} the rows of
  * that (chrA, chrB) bucket with startA <= posA <= endA and startB <= posB <= endB, counted per kind — out[0] the discordant pairs

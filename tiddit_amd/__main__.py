@@ -23,6 +23,10 @@ without ``TIDDIT_VARIANTS=1``.  One process only: on N ranks the switch is refus
 ``TIDDIT_DEPTH_DIST=1``: ``--sv`` also writes ``{o}.depth_dist.tab`` and ``{o}.depth_summary.tab`` — per contig and in total, the bases
 covered at exactly d x and at d x or more, and the mean / min / max depth per base (tiddit_amd/tiddit_depth_dist.py) — from the evidence
 store in one launch behind the candidates table.  One process only, refused on N ranks like ``TIDDIT_GENOTYPE``.
+
+``TIDDIT_CNV=1`` (CNV bins of 500 bp) or ``TIDDIT_CNV=W`` (a multiple of 50, 50 ... 3200): ``--sv`` also writes ``{o}.cnv.bed`` — the
+deletions and duplications that read depth alone shows, from an exact Viterbi segmentation of the job's coverage and GC bins on the
+device behind the ploidy table (tiddit_amd/tiddit_cnv.py).  On N ranks rank 0 holds those bins and runs the stage.
 """
 import argparse
 import os
@@ -204,6 +208,13 @@ def run_sv(args, version):
     except ValueError as e:
         # (before anything is read or made: no {o}_tiddit is left behind)
         print("error, TIDDIT_DEPTH_DIST={}: {}".format(os.environ.get("TIDDIT_DEPTH_DIST"), e))
+        sys.exit(1)
+    try:
+        from . import tiddit_cnv
+        cnv = tiddit_cnv.parse_switch(os.environ.get("TIDDIT_CNV"))
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_CNV={}: {}".format(os.environ.get("TIDDIT_CNV"), e))
         sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
@@ -433,7 +444,7 @@ def run_sv(args, version):
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,
-                    genotype_job, depth_dist)
+                    genotype_job, depth_dist, cnv)
     except BaseException:
         # no helper thread outlives the error: the writer thread of BACKGROUND_WRITES is joined (its own error, if any, is not the one to report)
         try:
@@ -449,8 +460,8 @@ def run_sv(args, version):
 
 
 def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, contigs, contig_length, samples, library, coverage_data, bam_header,
-                max_ins_len, min_mapq, sample_id, version, contig_number, own_group, genotype_job=None, depth_dist=False):
-    """run_sv behind the BAM scan: GC bins, ploidy table, clustering, candidates table, the signal files complete, the depth
+                max_ins_len, min_mapq, sample_id, version, contig_number, own_group, genotype_job=None, depth_dist=False, cnv=None):
+    """run_sv behind the BAM scan: GC bins, ploidy table, copy-number segments (TIDDIT_CNV), clustering, candidates table, the signal files complete, the depth
     distributions (TIDDIT_DEPTH_DIST=1), the variant stage (TIDDIT_VARIANTS=1), the genotypes of known sites (TIDDIT_GENOTYPE)"""
     from . import tiddit_cluster, tiddit_coverage_analysis, tiddit_gc, tiddit_signal
     from .trace import stage
@@ -488,6 +499,14 @@ def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, con
         print("calculated coverage in:")
         print(time.time() - t)
         T["ploidy (masked medians)"] = time.time() - t
+        if cnv is not None:
+            # TIDDIT_CNV: rank 0 holds the (reduced) coverage bins, every contig's GC bins and the ploidy table from here on
+            from . import tiddit_cnv
+            t = time.time()
+            with stage("tiddit: copy-number segments"):
+                tiddit_cnv.main(coverage_data, gc_dictionary, library, contigs, contig_length, args.min_contig, cnv, prefix)
+            T["copy-number segments ({o}.cnv.bed)"] = time.time() - t
+            T.update({"  " + k: v for k, v in tiddit_cnv.STAGE_SECONDS.items()})
     if not args.e:
         args.e = int(library["avg_insert_size"] / 2.0)
     if not args.e:

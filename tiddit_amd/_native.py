@@ -107,6 +107,10 @@ SYMBOLS = {
     "tdt_window_medians_device": (_i, [_P, _P, _P, _i64, _P, _sz, _P, _i, _P, _P, _P]),
     "tdt_gc_class_medians": (_i, [_P, _P, _P, _i64, _P, _i, _P, _P, _P]),
     "tdt_gc_class_medians_device": (_i, [_P, _P, _P, _i64, _P, _i, _P, _P, _P]),
+    "tdt_cnv_bins": (_i, [_P, _P, _P, _i64, _P, _i, _P, _i, _P]),
+    "tdt_cnv_bins_device": (_i, [_P, _P, _P, _i64, _P, _i, _P, _i, _P]),
+    "tdt_cnv_viterbi": (_i, [_P, _P, _i64, _P, _i, _i, _i64, _i64, _P]),
+    "tdt_cnv_viterbi_device": (_i, [_P, _P, _i64, _P, _i, _i, _i64, _i64, _P]),
     "tdt_segment_means": (_i, [_P, _P, _P, _i64, _P, _P, _P, _sz, _P, _P]),
     "tdt_segment_means_device": (_i, [_P, _P, _P, _P, _P, _P, _sz, _P, _P]),
     "tdt_region_counts": (_i, [_P] * 9 + [_sz, _i, _i64, _P, _P, _P, _sz, _i, _i64, _P]),

@@ -32,7 +32,7 @@ struct tdt_buf {
     size_t cap = 0;
 };
 
-enum { TDT_NSCRATCH = 29, TDT_NPINNED = 4 };
+enum { TDT_NSCRATCH = 30, TDT_NPINNED = 4 };
 
 struct tdt_ctx {
     int device = 0;
