@@ -590,6 +590,29 @@ int tdt_copy_to_host(tdt_ctx *ctx, void *dst, const void *d_src, size_t bytes);
 int tdt_calib_stream_read(tdt_ctx *ctx, const void *d_buf, size_t bytes, int reps, int workgroups_per_cu, int blocked, double *best_ms,
                           double *mean_ms);
 
+/* ---- allele counts at known SNV sites (TIDDIT_ALLELES) ------------------------------------------------- *
+ * No counterpart in the reference; the definition is tiddit_amd/tiddit_alleles.py's.  A handle keeps the sites of every contig
+ * (site_pos: 0-based, per contig sorted and unique, contig-major; site_off[n_contigs + 1]) and per site eight zeroed uint32 counters
+ * A C G T N DEL SKIP LOWBQ in HBM.  A push adds one batch of reads: the filters (tid, flag & 0xF04, mapq >= min_q) are tested on the
+ * field columns; a read with a site in [pos, end) has its record (at raw + rec_off: block_size, fixed fields, name, CIGAR, 4-bit
+ * sequence, qualities) bounded against its own block_size and raw_len and then walked.  A record that fails the bounds, holds an op
+ * code above 8 or is asked for a query base at or beyond l_seq counts nothing and adds one to `malformed`; nothing outside
+ * [raw, raw + raw_len) is ever read.  More than 2^32 - 1 reads on one site are outside the contract (the counters wrap).
+ * The push of device arrays takes the pointer table tdt_ingest_arrays filled, is enqueued on the context's stream and waits for nothing; the
+ * push of host arrays uploads them, runs the same kernel and returns when it is done.  Refusals: TDT_E_ARG (null pointers, offsets
+ * that decrease, sites not sorted / unique / >= 0, n >= 2^31), TDT_E_RANGE (min_bq outside 0 ... 93, 2^28 sites or more); a refused
+ * call leaves its outputs untouched.  The read-out calls synchronise the stream; either of their last two pointers may be NULL. */
+typedef struct tdt_alleles tdt_alleles;
+int tdt_alleles_create(tdt_ctx *ctx, const int32_t *site_pos, const int64_t *site_off, int n_contigs, int min_q, int min_bq,
+                       tdt_alleles **out);
+int tdt_alleles_destroy(tdt_alleles *h);
+int tdt_alleles_reset(tdt_alleles *h);
+int tdt_alleles_push_device(tdt_alleles *h, const void *const *d_arrays14, size_t n, size_t raw_len);
+int tdt_alleles_push(tdt_alleles *h, const int32_t *tid, const int32_t *pos, const int32_t *end, const uint8_t *mapq, const uint16_t *flag,
+                     const uint64_t *rec_off, size_t n, const uint8_t *raw, size_t raw_len);
+int tdt_alleles_counts(tdt_alleles *h, uint32_t *out, uint64_t *reads_used, uint64_t *malformed);
+int tdt_alleles_counts_device(tdt_alleles *h, uint32_t *d_out, uint64_t *d_stat2);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

@@ -216,6 +216,13 @@ def run_sv(args, version):
         # (the same)
         print("error, TIDDIT_CNV={}: {}".format(os.environ.get("TIDDIT_CNV"), e))
         sys.exit(1)
+    try:
+        from . import tiddit_alleles
+        alleles = tiddit_alleles.parse_switch(os.environ.get("TIDDIT_ALLELES"), os.environ.get("TIDDIT_ALLELES_MIN_BQ"))
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_ALLELES={}: {}".format(os.environ.get("TIDDIT_ALLELES"), e))
+        sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
     if genotype_depth and sites_path is None:
@@ -251,6 +258,16 @@ def run_sv(args, version):
     contig_number = {c: i for i, c in enumerate(contigs)}
     contig_length = {c["SN"]: c["LN"] for c in bam_header["SQ"]}
     prefix = args.o
+    allele_sites = None
+    if alleles is not None:
+        # TIDDIT_ALLELES: the sites are read now, on every rank — a file that cannot be read ends the job before anything is made
+        t_sites = time.time()
+        try:
+            allele_sites = tiddit_alleles.read_sites(alleles[0], chromosomes, [contig_length[c] for c in chromosomes])
+        except (OSError, EOFError, UnicodeDecodeError) as e:
+            print("error, TIDDIT_ALLELES={}: {}".format(alleles[0], e))
+            sys.exit(1)
+        t_sites = time.time() - t_sites
     # one process per GPU on ONE file (BASELINE configs[4]; `torchrun --nproc-per-node N -m tiddit_amd --sv ...`): rank 0 owns the
     # output files and the host-only stages, the signal scan and the clustering are shared (tiddit_signal.main_sharded,
     # tiddit_cluster.main_sharded)
@@ -296,6 +313,8 @@ def run_sv(args, version):
     T = STAGE_SECONDS
     T.clear()
     STAGE_NOTES.clear()
+    if allele_sites is not None:
+        T["allele sites (host, before the scan)"] = t_sites
     from .trace import stage
     # The GC / N-mask bins depend on the reference FASTA alone (the reference computes them after the signals, __main__.py:166): a
     # second host thread with its own library context (own streams and scratch) reads the FASTA and runs the GC kernel BESIDE the BAM
@@ -413,6 +432,9 @@ def run_sv(args, version):
     if track is not None:
         # TIDDIT_COV_TRACK: the scan fills a second histogram — every contig, the track's bin size and mapq cut — from the same batches
         tiddit_signal.COV_TRACK = (track[0], track[1])
+    if allele_sites is not None:
+        # TIDDIT_ALLELES: ... and counts the reads' bases at the sites, one launch per batch
+        tiddit_signal.ALLELES = (allele_sites.site_pos, allele_sites.site_off, alleles[1])
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -425,6 +447,7 @@ def run_sv(args, version):
             tiddit_signal.KEEP_EVIDENCE = False
             if track is not None:
                 tiddit_signal.COV_TRACK = None
+            tiddit_signal.ALLELES = None
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:
@@ -441,6 +464,12 @@ def run_sv(args, version):
             tiddit_coverage.print_coverage(bins, bam_header, track[0], track[2], "{}.{}".format(prefix, track[2]))
             T["coverage track ({o}.bed / {o}.wig, from the scan's second histogram)"] = time.time() - t
         del bins
+    if allele_sites is not None:
+        counter, tiddit_signal.ALLELE_COUNTER = tiddit_signal.ALLELE_COUNTER, None
+        t = time.time()
+        tiddit_alleles.main(counter, allele_sites, prefix, multi=multi, rank=rank)
+        T["allele counts ({o}.alleles.tab)"] = time.time() - t
+        T.update({"  " + k: v for k, v in tiddit_alleles.STAGE_SECONDS.items()})
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,
