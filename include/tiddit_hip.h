@@ -445,6 +445,38 @@ int tdt_cnv_viterbi(tdt_ctx *ctx, const int32_t *x, int64_t n, const int64_t *ta
 int tdt_cnv_viterbi_device(tdt_ctx *ctx, const int32_t *d_x, int64_t n, const int64_t *table, int nseg, int unit, int64_t cap, int64_t lambda,
                            int8_t *d_state);
 
+/* ---- allele-specific copy number (TIDDIT_ASCN; tiddit_amd/tiddit_ascn.py has the definition) -------------------------- *
+ * tdt_ascn_emissions: counts = uint32[nsites][8], the counter table of tdt_alleles_counts; site_pos = int32[nsites], its positions
+ * (0-based, sorted inside every row's range); cols = uint8[nsites][2], the counter columns (0 .. 7) of the site's REF and ALT; x =
+ * int32[total], the CNV bins of tdt_cnv_bins (x < 0 = masked).  table = int64[nseg][5] rows {site_lo, site_hi, toff, T, W} (a HOST
+ * array in both entries): the contig's sites site_lo .. site_hi - 1, its T bins of W bp (1 .. 3200) from bin toff, contiguous from 0
+ * and summing to total.  Bin t of a row holds its sites with t W <= pos < (t + 1) W, found with two lower bounds.  A site with
+ * n = ref_n + alt_n >= min_n is informative: beta = (min(ref_n, alt_n) * bu) / n in 64 bits, h = min(acap, beta^2), and for state k =
+ * (c, m) of the 16 (c = 0 .. 6, 0 <= m <= c / 2, c ascending, then m) g(k) = h if m == 0, else min(min(acap, (beta - (bu m) / c)^2),
+ * h + hom).  E[t][k] = (x_t < 0 ? 0 : min(cap, (x_t - unit c)^2)) + the sum of g(k) over the bin's informative sites; nsite[t] = their
+ * number, sum_beta[t] = the sum of their beta.  unit in 1 .. 2^20, cap in 0 .. 2^28, bu in 1 .. 2^15, acap in 0 .. 2^16, hom in
+ * 0 .. 2^28, min_n >= 1.  E = int32[total][16], nsite = int32[total], sum_beta = int32[total].  Positions that repeat inside a row are
+ * outside the contract (an emission may pass 2^31); the host entry refuses a column above 7 (TDT_E_RANGE), the device entry reads its
+ * low three bits.
+ * tdt_hmm16_viterbi: e = int32[n][16], the emissions of n bins; table = int64[nseg][3] rows {toff, T, home} (HOST), contiguous from 0
+ * and summing to n, home in 0 .. 15.  state = int8[n]: for every row the minimum-cost path over the 16 states of the chain
+ * V_0(k) = e_0(k) + (k == home ? 0 : lambda), V_t(k) = e_t(k) + min(V_{t-1}(k), min_i V_{t-1}(i) + lambda), end cost V_{T-1}(k) +
+ * (k == home ? 0 : lambda); ties go to staying (V_{t-1}(k) <= m + lambda) and to the lowest state.  int64 costs, chunks of 256 bins
+ * whose (min,+) matrices are stitched: the sequential result exactly (csrc/tdt_ascn.hip).  lambda in 0 .. 2^28; emissions outside
+ * 0 .. 2^28 are outside the contract — the host entry refuses them (TDT_E_RANGE), the device entry does not look.
+ * All four: TDT_E_ARG for a null context, a negative count, a parameter outside its range and — unless the bins or nseg are 0, which
+ * return TDT_OK — a null or misaligned pointer (8 bytes for int64, 4 for int32 / uint32); TDT_E_RANGE for a row outside the arrays or
+ * not following the row before it; all before anything is launched, the outputs untouched.  The _device entries take every array but
+ * table in HBM.  The context's stream is synchronised before the return. */
+int tdt_ascn_emissions(tdt_ctx *ctx, const uint32_t *counts, const int32_t *site_pos, const uint8_t *cols, int64_t nsites, const int32_t *x,
+                       int64_t total, const int64_t *table, int nseg, int unit, int64_t cap, int bu, int acap, int hom, int min_n, int32_t *E,
+                       int32_t *nsite, int32_t *sum_beta);
+int tdt_ascn_emissions_device(tdt_ctx *ctx, const uint32_t *d_counts, const int32_t *d_site_pos, const uint8_t *d_cols, int64_t nsites,
+                              const int32_t *d_x, int64_t total, const int64_t *table, int nseg, int unit, int64_t cap, int bu, int acap, int hom,
+                              int min_n, int32_t *d_E, int32_t *d_nsite, int32_t *d_sum_beta);
+int tdt_hmm16_viterbi(tdt_ctx *ctx, const int32_t *e, int64_t n, const int64_t *table, int nseg, int64_t lambda, int8_t *state);
+int tdt_hmm16_viterbi_device(tdt_ctx *ctx, const int32_t *d_e, int64_t n, const int64_t *table, int nseg, int64_t lambda, int8_t *d_state);
+
 /* ---- link counts of SV sites (TIDDIT_GENOTYPE) ------------------------------------------------------- *
  * How many signals of the cluster table join the two regions of a site: for site {bucket, startA, endA, startB, endB} the rows of
  * that (chrA, chrB) bucket with startA <= posA <= endA and startB <= posB <= endB, counted per kind — out[0] the discordant pairs

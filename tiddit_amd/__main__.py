@@ -27,6 +27,11 @@ store in one launch behind the candidates table.  One process only, refused on N
 ``TIDDIT_CNV=1`` (CNV bins of 500 bp) or ``TIDDIT_CNV=W`` (a multiple of 50, 50 ... 3200): ``--sv`` also writes ``{o}.cnv.bed`` — the
 deletions and duplications that read depth alone shows, from an exact Viterbi segmentation of the job's coverage and GC bins on the
 device behind the ploidy table (tiddit_amd/tiddit_cnv.py).  On N ranks rank 0 holds those bins and runs the stage.
+
+``TIDDIT_ASCN=1``, only together with ``TIDDIT_CNV`` and ``TIDDIT_ALLELES``: ``--sv`` also writes ``{o}.ascn.bed`` — allele-specific copy
+number: deletions, duplications, copy-neutral LOH and allelic imbalance from the CNV bins joined with the allele counters at the known
+sites, by an exact 16-state Viterbi segmentation on the device behind the CNV stage (tiddit_amd/tiddit_ascn.py).  Nothing reads the BAM
+again; on N ranks rank 0 holds the bins and the summed counters and runs the stage.
 """
 import argparse
 import os
@@ -222,6 +227,13 @@ def run_sv(args, version):
     except ValueError as e:
         # (the same)
         print("error, TIDDIT_ALLELES={}: {}".format(os.environ.get("TIDDIT_ALLELES"), e))
+        sys.exit(1)
+    try:
+        from . import tiddit_ascn
+        ascn = tiddit_ascn.parse_switch(os.environ.get("TIDDIT_ASCN"), cnv, alleles)
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_ASCN={}: {}".format(os.environ.get("TIDDIT_ASCN"), e))
         sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
@@ -467,13 +479,13 @@ def run_sv(args, version):
     if allele_sites is not None:
         counter, tiddit_signal.ALLELE_COUNTER = tiddit_signal.ALLELE_COUNTER, None
         t = time.time()
-        tiddit_alleles.main(counter, allele_sites, prefix, multi=multi, rank=rank)
+        allele_table = tiddit_alleles.main(counter, allele_sites, prefix, multi=multi, rank=rank)
         T["allele counts ({o}.alleles.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_alleles.STAGE_SECONDS.items()})
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,
-                    genotype_job, depth_dist, cnv)
+                    genotype_job, depth_dist, cnv, (allele_table, allele_sites) if ascn else None)
     except BaseException:
         # no helper thread outlives the error: the writer thread of BACKGROUND_WRITES is joined (its own error, if any, is not the one to report)
         try:
@@ -489,8 +501,9 @@ def run_sv(args, version):
 
 
 def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, contigs, contig_length, samples, library, coverage_data, bam_header,
-                max_ins_len, min_mapq, sample_id, version, contig_number, own_group, genotype_job=None, depth_dist=False, cnv=None):
-    """run_sv behind the BAM scan: GC bins, ploidy table, copy-number segments (TIDDIT_CNV), clustering, candidates table, the signal files complete, the depth
+                max_ins_len, min_mapq, sample_id, version, contig_number, own_group, genotype_job=None, depth_dist=False, cnv=None, ascn=None):
+    """run_sv behind the BAM scan: GC bins, ploidy table, copy-number segments (TIDDIT_CNV), allele-specific ones (TIDDIT_ASCN; ascn: the
+    counter table and the sites of TIDDIT_ALLELES), clustering, candidates table, the signal files complete, the depth
     distributions (TIDDIT_DEPTH_DIST=1), the variant stage (TIDDIT_VARIANTS=1), the genotypes of known sites (TIDDIT_GENOTYPE)"""
     from . import tiddit_cluster, tiddit_coverage_analysis, tiddit_gc, tiddit_signal
     from .trace import stage
@@ -533,9 +546,23 @@ def _after_scan(args, prefix, rank, multi, T, gc_job, start_gc, chromosomes, con
             from . import tiddit_cnv
             t = time.time()
             with stage("tiddit: copy-number segments"):
-                tiddit_cnv.main(coverage_data, gc_dictionary, library, contigs, contig_length, args.min_contig, cnv, prefix)
+                if ascn is None:
+                    tiddit_cnv.main(coverage_data, gc_dictionary, library, contigs, contig_length, args.min_contig, cnv, prefix)
+                else:
+                    # (the same two halves, the bins kept: x stays on the device for the stage below)
+                    cnv_bins = tiddit_cnv.bins_stage(coverage_data, gc_dictionary, library, contigs, contig_length, args.min_contig, cnv)
+                    tiddit_cnv.segments_stage(cnv_bins, contig_length, prefix)
             T["copy-number segments ({o}.cnv.bed)"] = time.time() - t
             T.update({"  " + k: v for k, v in tiddit_cnv.STAGE_SECONDS.items()})
+            if ascn is not None:
+                # TIDDIT_ASCN: ... and the counter table of TIDDIT_ALLELES (on N ranks the sum of every rank's)
+                from . import tiddit_ascn
+                t = time.time()
+                with stage("tiddit: allele-specific copy number"):
+                    tiddit_ascn.main(cnv_bins, ascn[0], ascn[1], contig_number, contig_length, prefix)
+                del cnv_bins
+                T["allele-specific copy number ({o}.ascn.bed)"] = time.time() - t
+                T.update({"  " + k: v for k, v in tiddit_ascn.STAGE_SECONDS.items()})
     if not args.e:
         args.e = int(library["avg_insert_size"] / 2.0)
     if not args.e:

@@ -111,6 +111,10 @@ SYMBOLS = {
     "tdt_cnv_bins_device": (_i, [_P, _P, _P, _i64, _P, _i, _P, _i, _P]),
     "tdt_cnv_viterbi": (_i, [_P, _P, _i64, _P, _i, _i, _i64, _i64, _P]),
     "tdt_cnv_viterbi_device": (_i, [_P, _P, _i64, _P, _i, _i, _i64, _i64, _P]),
+    "tdt_ascn_emissions": (_i, [_P, _P, _P, _P, _i64, _P, _i64, _P, _i, _i, _i64, _i, _i, _i, _i, _P, _P, _P]),
+    "tdt_ascn_emissions_device": (_i, [_P, _P, _P, _P, _i64, _P, _i64, _P, _i, _i, _i64, _i, _i, _i, _i, _P, _P, _P]),
+    "tdt_hmm16_viterbi": (_i, [_P, _P, _i64, _P, _i, _i64, _P]),
+    "tdt_hmm16_viterbi_device": (_i, [_P, _P, _i64, _P, _i, _i64, _P]),
     "tdt_segment_means": (_i, [_P, _P, _P, _i64, _P, _P, _P, _sz, _P, _P]),
     "tdt_segment_means_device": (_i, [_P, _P, _P, _P, _P, _P, _sz, _P, _P]),
     "tdt_region_counts": (_i, [_P] * 9 + [_sz, _i, _i64, _P, _P, _P, _sz, _i, _i64, _P]),

@@ -149,10 +149,18 @@ def expected_depth(lower, upper, count, C):
     return numpy.ascontiguousarray(numpy.where(numpy.asarray(count) >= MIN_CLASS, M, numpy.asarray(C, dtype=numpy.float64)[:, None]))
 
 
-def main(coverage_data, gc_dictionary, library, contigs, contig_length, min_contig, W, prefix, ctx=None):
-    """the stage behind the ploidy table: ``{prefix}.cnv.bed`` from the job's bins (the module docstring has the definition) -> the
-    segments.  One upload of the processed contigs' bins serves the class medians and the CNV bins; x stays on the device between the
-    two new entries."""
+class Bins:
+    """what the first half of the stage leaves: ``contigs`` as given, the processed ones (``used``), the ``skipped`` ones, the
+    ``ploidy`` of the used, their chain table ``chains`` (int64[nseg][3] {toff, T, P}), ``W``, and the CNV bins ``d_x`` — an int32
+    tensor that stays on the device (None when no contig is processed)"""
+
+    def __init__(self, contigs, used, skipped, ploidy, chains, W, d_x):
+        self.contigs, self.used, self.skipped, self.ploidy, self.chains, self.W, self.d_x = contigs, used, skipped, ploidy, chains, W, d_x
+
+
+def bins_stage(coverage_data, gc_dictionary, library, contigs, contig_length, min_contig, W, ctx=None):
+    """the first half of :func:`main`: which contigs are processed, their ploidies and chain table, and x on the device -> Bins.
+    One upload of the processed contigs' bins serves the class medians and the CNV bins."""
     import time
     import torch
     from . import tiddit_coverage_analysis
@@ -177,52 +185,73 @@ def main(coverage_data, gc_dictionary, library, contigs, contig_length, min_cont
     used = [cand[i] for i in keep]
     covs, gcs, C = [covs[i] for i in keep], [gcs[i] for i in keep], [med[i] for i in keep]
     STAGE_SECONDS["CNV contig medians (device, masked_medians)"] = time.time() - t0
-    if skipped:
-        order = {c: i for i, c in enumerate(contigs)}
-        print("note: TIDDIT_CNV skips {}".format(", ".join(sorted(skipped, key=order.get))))
+    if not used:
+        return Bins(contigs, used, skipped, [], numpy.zeros((0, 3), dtype=numpy.int64), W, None)
+    t0 = time.time()
+    ploidy = [int(library["contig_ploidy_{}".format(c)]) for c in used]
+    rows, o = [], 0
+    for v, P in zip(covs, ploidy):
+        rows.append((o, len(v), K, P))
+        o += len(v)
+    table = bin_table(rows)
+    chains = chain_table([(bins_of(r[1], K), r[3]) for r in rows])
+    total = int(chains[:, 1].sum())
+    seg = numpy.ascontiguousarray(table[:, :2])
+    dev = torch.device("cuda", ctx.device)
+    d_cov = torch.from_numpy(numpy.concatenate(covs)).to(dev)
+    d_gc = torch.from_numpy(numpy.concatenate(gcs)).to(dev)
+    d_cls = torch.empty((2, len(used), CLASSES), dtype=torch.float64, device=dev)        # lower, upper
+    d_cls_n = torch.empty((len(used), CLASSES), dtype=torch.int64, device=dev)
+    d_x = torch.empty(total, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)                   # torch's copies run on its stream, the library on its own
+    STAGE_SECONDS["CNV upload of the bins"] = time.time() - t0
+    t0 = time.time()
+    _native.check(ctx.lib.tdt_gc_class_medians_device(ctx.handle, d_cov.data_ptr(), d_gc.data_ptr(), o, _native.ptr(seg), len(used),
+                                                      d_cls[0].data_ptr(), d_cls[1].data_ptr(), d_cls_n.data_ptr()))
+    cls = d_cls.cpu().numpy()
+    E = expected_depth(cls[0], cls[1], d_cls_n.cpu().numpy(), C)
+    d_E = torch.from_numpy(E).to(dev)
+    torch.cuda.synchronize(dev)
+    STAGE_SECONDS["CNV expected depth (device, tdt_gc_class_medians)"] = time.time() - t0
+    t0 = time.time()
+    _native.check(ctx.lib.tdt_cnv_bins_device(ctx.handle, d_cov.data_ptr(), d_gc.data_ptr(), o, _native.ptr(table), len(used), d_E.data_ptr(),
+                                              UNIT, d_x.data_ptr()))
+    STAGE_SECONDS["CNV bins (device, tdt_cnv_bins)"] = time.time() - t0
+    return Bins(contigs, used, skipped, ploidy, chains, W, d_x)
+
+
+def segments_stage(bins, contig_length, prefix, ctx=None):
+    """the second half of :func:`main`: the note on the skipped contigs, x through the Viterbi segmentation, ``{prefix}.cnv.bed`` ->
+    the segments.  x stays where it is, for a stage behind this one (tiddit_ascn.py)."""
+    import time
+    import torch
+    ctx = ctx or _native.default_context()
+    if bins.skipped:
+        order = {c: i for i, c in enumerate(bins.contigs)}
+        print("note: TIDDIT_CNV skips {}".format(", ".join(sorted(bins.skipped, key=order.get))))
     segments = []
-    if used:
-        t0 = time.time()
-        ploidy = [int(library["contig_ploidy_{}".format(c)]) for c in used]
-        rows, o = [], 0
-        for v, P in zip(covs, ploidy):
-            rows.append((o, len(v), K, P))
-            o += len(v)
-        table = bin_table(rows)
-        chains = chain_table([(bins_of(r[1], K), r[3]) for r in rows])
+    if bins.used:
+        chains, W = bins.chains, bins.W
         total = int(chains[:, 1].sum())
-        seg = numpy.ascontiguousarray(table[:, :2])
-        dev = torch.device("cuda", ctx.device)
-        d_cov = torch.from_numpy(numpy.concatenate(covs)).to(dev)
-        d_gc = torch.from_numpy(numpy.concatenate(gcs)).to(dev)
-        d_cls = torch.empty((2, len(used), CLASSES), dtype=torch.float64, device=dev)        # lower, upper
-        d_cls_n = torch.empty((len(used), CLASSES), dtype=torch.int64, device=dev)
-        d_x = torch.empty(total, dtype=torch.int32, device=dev)
-        d_state = torch.empty(total, dtype=torch.int8, device=dev)
-        torch.cuda.synchronize(dev)                   # torch's copies run on its stream, the library on its own
-        STAGE_SECONDS["CNV upload of the bins"] = time.time() - t0
         t0 = time.time()
-        _native.check(ctx.lib.tdt_gc_class_medians_device(ctx.handle, d_cov.data_ptr(), d_gc.data_ptr(), o, _native.ptr(seg), len(used),
-                                                          d_cls[0].data_ptr(), d_cls[1].data_ptr(), d_cls_n.data_ptr()))
-        cls = d_cls.cpu().numpy()
-        E = expected_depth(cls[0], cls[1], d_cls_n.cpu().numpy(), C)
-        d_E = torch.from_numpy(E).to(dev)
-        torch.cuda.synchronize(dev)
-        STAGE_SECONDS["CNV expected depth (device, tdt_gc_class_medians)"] = time.time() - t0
-        t0 = time.time()
-        _native.check(ctx.lib.tdt_cnv_bins_device(ctx.handle, d_cov.data_ptr(), d_gc.data_ptr(), o, _native.ptr(table), len(used), d_E.data_ptr(),
-                                                  UNIT, d_x.data_ptr()))
-        STAGE_SECONDS["CNV bins (device, tdt_cnv_bins)"] = time.time() - t0
-        t0 = time.time()
-        _native.check(ctx.lib.tdt_cnv_viterbi_device(ctx.handle, d_x.data_ptr(), total, _native.ptr(chains), len(used), UNIT, CAP, LAMBDA,
+        d_state = torch.empty(total, dtype=torch.int8, device=bins.d_x.device)
+        torch.cuda.synchronize(bins.d_x.device)
+        _native.check(ctx.lib.tdt_cnv_viterbi_device(ctx.handle, bins.d_x.data_ptr(), total, _native.ptr(chains), len(bins.used), UNIT, CAP, LAMBDA,
                                                      d_state.data_ptr()))
         STAGE_SECONDS["CNV segmentation (device, tdt_cnv_viterbi: five kernels)"] = time.time() - t0
         t0 = time.time()
-        x, state = d_x.cpu().numpy(), d_state.cpu().numpy()
-        for c, P, (toff, T, _) in zip(used, ploidy, chains):
+        x, state = bins.d_x.cpu().numpy(), d_state.cpu().numpy()
+        for c, P, (toff, T, _) in zip(bins.used, bins.ploidy, chains):
             segments += segments_of(state[toff:toff + T], x[toff:toff + T], P, W, contig_length[c], c)
         STAGE_SECONDS["CNV segments (host)"] = time.time() - t0
     t0 = time.time()
     write_bed(prefix + ".cnv.bed", segments)
     STAGE_SECONDS["CNV text (host)"] = time.time() - t0
     return segments
+
+
+def main(coverage_data, gc_dictionary, library, contigs, contig_length, min_contig, W, prefix, ctx=None):
+    """the stage behind the ploidy table: ``{prefix}.cnv.bed`` from the job's bins (the module docstring has the definition) -> the
+    segments.  x stays on the device between the two halves, :func:`bins_stage` and :func:`segments_stage`."""
+    return segments_stage(bins_stage(coverage_data, gc_dictionary, library, contigs, contig_length, min_contig, W, ctx=ctx), contig_length,
+                          prefix, ctx=ctx)
