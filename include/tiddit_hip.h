@@ -645,6 +645,49 @@ int tdt_alleles_push(tdt_alleles *h, const int32_t *tid, const int32_t *pos, con
 int tdt_alleles_counts(tdt_alleles *h, uint32_t *out, uint64_t *reads_used, uint64_t *malformed);
 int tdt_alleles_counts_device(tdt_alleles *h, uint32_t *d_out, uint64_t *d_stat2);
 
+/* ---- read-level QC tables (TIDDIT_QC) ------------------------------------------------------------------ *
+ * No counterpart in the reference (its users run `samtools flagstat` / `samtools stats`, one more pass over the file); the definition
+ * is tiddit_amd/tiddit_qc.py's.  A handle keeps ONE array of TDT_QC_TOTAL zeroed uint64 counters in HBM, in sections (row-major):
+ *   SN    [TDT_QC_SN_N]   records secondary supplementary | primary qc_fail duplicate unmapped mapped paired read1 read2 proper_pair
+ *                         mate_unmapped both_mapped mate_other_contig mate_other_contig_mapq5 reverse mapq0 | malformed bases
+ *                         reads_no_seq reads_no_qual bases_q20 bases_q30 aligned_bases soft_clipped_bases hard_clipped_bases
+ *                         inserted_bases deleted_bases skipped_bases insertions deletions reads_clipped
+ *   MAPQ  [256]           mapped primary records by mapq
+ *   RL    [512 + 1]       records with flag & 0xB00 == 0 ("S") by min(l_seq, 512)
+ *   IS    [2000 + 1][3]   S, paired, both mapped, mate_tid == tid, tlen > 0, by min(tlen, 2000): inward outward same
+ *   CYC   [512 + 1][7]    per cycle (read orientation; the cycles from 512 share the last row): A C G T other qual_sum qual_n
+ *   QUAL  [256]           every quality byte of the reads with qualities
+ *   GCR   [101]           reads with l_seq > 0 by (100 * gc) / l_seq
+ *   ID    [64][2]         insertion / deletion events of the mapped reads by min(len, 64) - 1
+ * SN up to mapq0, MAPQ, RL and IS come from the field columns alone.  Everything else is read from the bytes of the records of S, each
+ * bounded first as tdt_alleles bounds one (rec_off + 36 <= raw_len, 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <=
+ * block_size, rec_off + 4 + block_size <= raw_len; l_seq is the record's own): a record that fails, or holds a CIGAR op code above 8,
+ * adds one to `malformed` and nothing else from its bytes; nothing outside [raw, raw + raw_len) is ever read.
+ * tdt_qc_push_device takes the pointer table tdt_ingest_arrays filled, enqueues two launches on the context's stream, waits for nothing
+ * and allocates nothing; tdt_qc_push uploads host columns, runs the same kernels and returns when they are done.  Refusals: TDT_E_ARG
+ * (null pointers, record offsets that decrease, n >= 2^31, a misaligned device output); a refused call leaves its outputs untouched.
+ * The read-out calls synchronise the stream.  tdt_qc_size() = TDT_QC_TOTAL. */
+#define TDT_QC_SN_N 33
+#define TDT_QC_OFF_SN 0
+#define TDT_QC_OFF_MAPQ 33
+#define TDT_QC_OFF_RL 289
+#define TDT_QC_OFF_IS 802
+#define TDT_QC_OFF_CYC 6805
+#define TDT_QC_OFF_QUAL 10396
+#define TDT_QC_OFF_GCR 10652
+#define TDT_QC_OFF_ID 10753
+#define TDT_QC_TOTAL 10881
+typedef struct tdt_qc tdt_qc;
+int tdt_qc_create(tdt_ctx *ctx, tdt_qc **out);
+int tdt_qc_destroy(tdt_qc *h);
+int tdt_qc_reset(tdt_qc *h);
+int tdt_qc_push_device(tdt_qc *h, const void *const *d_arrays14, size_t n, size_t raw_len);
+int tdt_qc_push(tdt_qc *h, const uint16_t *flag, const uint8_t *mapq, const int32_t *tid, const int32_t *mate_tid, const int32_t *tlen,
+                const int32_t *l_seq, const uint64_t *rec_off, size_t n, const uint8_t *raw, size_t raw_len);
+int tdt_qc_counts(tdt_qc *h, uint64_t *out);
+int tdt_qc_counts_device(tdt_qc *h, uint64_t *d_out);
+size_t tdt_qc_size(void);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

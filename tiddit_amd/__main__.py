@@ -32,6 +32,11 @@ device behind the ploidy table (tiddit_amd/tiddit_cnv.py).  On N ranks rank 0 ho
 number: deletions, duplications, copy-neutral LOH and allelic imbalance from the CNV bins joined with the allele counters at the known
 sites, by an exact 16-state Viterbi segmentation on the device behind the CNV stage (tiddit_amd/tiddit_ascn.py).  Nothing reads the BAM
 again; on N ranks rank 0 holds the bins and the summed counters and runs the stage.
+
+``TIDDIT_QC=1``: ``--sv`` also writes ``{o}.qc.tab`` — read-level QC tables from the records the scan already holds in HBM: flag counts,
+MAPQ, read lengths, insert sizes, per-cycle base composition and quality, the quality histogram, GC per read, CIGAR sums and indel
+lengths (tiddit_amd/tiddit_qc.py has the definition and the file's format).  Unset or empty is off; any other value ends the job with an
+error before the scan.  On N ranks every rank counts the records of its shard and rank 0 writes the summed tables.
 """
 import argparse
 import os
@@ -234,6 +239,13 @@ def run_sv(args, version):
     except ValueError as e:
         # (the same)
         print("error, TIDDIT_ASCN={}: {}".format(os.environ.get("TIDDIT_ASCN"), e))
+        sys.exit(1)
+    try:
+        from . import tiddit_qc
+        qc = tiddit_qc.parse_switch(os.environ.get("TIDDIT_QC"))
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_QC={}: {}".format(os.environ.get("TIDDIT_QC"), e))
         sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
@@ -447,6 +459,9 @@ def run_sv(args, version):
     if allele_sites is not None:
         # TIDDIT_ALLELES: ... and counts the reads' bases at the sites, one launch per batch
         tiddit_signal.ALLELES = (allele_sites.site_pos, allele_sites.site_off, alleles[1])
+    if qc:
+        # TIDDIT_QC: ... and fills the read-level QC tables, two launches per batch
+        tiddit_signal.QC = True
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -460,6 +475,7 @@ def run_sv(args, version):
             if track is not None:
                 tiddit_signal.COV_TRACK = None
             tiddit_signal.ALLELES = None
+            tiddit_signal.QC = None
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:
@@ -482,6 +498,12 @@ def run_sv(args, version):
         allele_table = tiddit_alleles.main(counter, allele_sites, prefix, multi=multi, rank=rank)
         T["allele counts ({o}.alleles.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_alleles.STAGE_SECONDS.items()})
+    if qc:
+        counter, tiddit_signal.QC_COUNTER = tiddit_signal.QC_COUNTER, None
+        t = time.time()
+        tiddit_qc.main(counter, prefix, multi=multi, rank=rank)
+        T["qc tables ({o}.qc.tab)"] = time.time() - t
+        T.update({"  " + k: v for k, v in tiddit_qc.STAGE_SECONDS.items()})
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,

@@ -139,6 +139,14 @@ SYMBOLS = {
     "tdt_alleles_push": (_i, [_P] * 7 + [_sz, _P, _sz]),
     "tdt_alleles_counts": (_i, [_P, _P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "tdt_alleles_counts_device": (_i, [_P, _P, _P]),
+    "tdt_qc_create": (_i, [_P, _PP]),
+    "tdt_qc_destroy": (_i, [_P]),
+    "tdt_qc_reset": (_i, [_P]),
+    "tdt_qc_push_device": (_i, [_P, _P, _sz, _sz]),
+    "tdt_qc_push": (_i, [_P] * 8 + [_sz, _P, _sz]),
+    "tdt_qc_counts": (_i, [_P, _P]),
+    "tdt_qc_counts_device": (_i, [_P, _P]),
+    "tdt_qc_size": (_sz, []),
     "tdt_format_coverage": (_i, [_P, _sz, ctypes.c_char_p, _i64, _i64, _i, _P, _sz, ctypes.POINTER(_sz)]),
     "tdt_fasta_write_fai": (_i, [ctypes.c_char_p, ctypes.c_char_p]),
     "tdt_host_threads": (_i, [_i]),

@@ -301,9 +301,10 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
 
     ``COV_TRACK = (bin_size, min_q)``: a second histogram over EVERY contig of the header is filled from the same batches (their second
     coverage-record column, written by the ingest kernel in the pass that decodes them) and its bins are left in ``COV_TRACK_BINS``."""
-    global COV_TRACK_BINS, ALLELE_COUNTER
+    global COV_TRACK_BINS, ALLELE_COUNTER, QC_COUNTER
     COV_TRACK_BINS = None
     ALLELE_COUNTER = None
+    QC_COUNTER = None
     track = COV_TRACK
     max_ins = int(max_ins)         # the reference's `int max_ins` argument truncates a float percentile (:147,:230; probed with Cython 3.2)
     from . import bamio
@@ -364,6 +365,12 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         from . import tiddit_alleles
         alleles = tiddit_alleles.AlleleCounter(ALLELES[0], ALLELES[1], min_q, ALLELES[2], ctx=getattr(reader, "ctx", None))
         T["allele counts (push)"] = 0.0
+    qc = None
+    if QC:
+        # TIDDIT_QC: one counter array in HBM; every batch costs two more launches on the columns and bytes it already holds there
+        from . import tiddit_qc
+        qc = tiddit_qc.QcCounter(ctx=getattr(reader, "ctx", None))
+        T["qc tables (push)"] = 0.0
     tables = data = splits = clips = None
     if isinstance(reader, DeviceBamReader):
         from .sigtab import SignalTables
@@ -421,6 +428,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                     t3b = time.time()
                     T["allele counts (push)"] += t3b - t3
                     t3 = t3b
+                if qc is not None:                              # (the same)
+                    qc.push_device_batch(b)
+                    t3b = time.time()
+                    T["qc tables (push)"] += t3b - t3
+                    t3 = t3b
                 # the per-read chain of worker (:171-221) on the device; only the selected reads come back (fields + raw records)
                 # (once the scan's kernels are enqueued nothing will read the batch's raw bytes again: the next span's inflate is started
                 #  behind them — DeviceBamReader.ahead() — and runs while this thread waits for the selected reads and hands them on)
@@ -445,6 +457,10 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 t1b = time.time()
                 alleles.push_host_batch(b)
                 T["allele counts (push)"] += time.time() - t1b
+            if qc is not None:
+                t1b = time.time()
+                qc.push_host_batch(b)
+                T["qc tables (push)"] += time.time() - t1b
             tid = b.tid
             flag = b.flag.astype(numpy.int32)
             placed = tid >= 0
@@ -507,6 +523,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             hist2.close()
         if alleles is not None:
             alleles.close()
+        if qc is not None:
+            qc.close()
         raise
     finally:
         pool.shutdown(wait=True)                              # (also on an error: no row thread outlives the scan)
@@ -521,8 +539,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             READER_SECONDS["pushes"] = len(reader.timings)
     if alleles is not None:
         alleles.ctx.sync()                                      # (its launches read the reader's buffers, which go now)
+    if qc is not None:
+        qc.ctx.sync()                                           # (the same)
     reader.close()
     ALLELE_COUNTER = alleles                                    # (the caller reads the counters and closes it)
+    QC_COUNTER = qc                                             # (the same)
     if store is not None:
         from . import tiddit_variant
         if tiddit_variant.LIVE_STORE is not None:
@@ -572,6 +593,8 @@ COV_TRACK = None            # (bin_size, min_q): the scan also fills a second hi
 COV_TRACK_BINS = None       # {contig: float64 bins} of that histogram after the last scan that had COV_TRACK set (on N ranks: the reduced bins), else None
 ALLELES = None              # (site_pos, site_off, min_bq): the scan also counts the reads' bases at these sites (tiddit_alleles.AlleleCounter), one launch per batch
 ALLELE_COUNTER = None       # that counter after the last scan that had ALLELES set (the caller reads and closes it), else None
+QC = None                   # True: the scan also fills the read-level QC tables (tiddit_qc.QcCounter), two launches per batch
+QC_COUNTER = None           # that counter after the last scan that had QC set (the caller reads and closes it), else None
 KEEP_EVIDENCE = False       # the scan packs every placed record into an evidence store for the variant stage (tiddit_variant.LIVE_STORE)
 AFTER_SCAN = []             # callables main() invokes once the file has been scanned, before the tables are written (host-only work from there on)
 READER_SECONDS = {}         # the reader thread of the last scan: seconds reading, scanning BGZF headers, building tables, waiting — and the consumer's waits
