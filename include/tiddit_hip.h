@@ -688,6 +688,44 @@ int tdt_qc_counts(tdt_qc *h, uint64_t *out);
 int tdt_qc_counts_device(tdt_qc *h, uint64_t *d_out);
 size_t tdt_qc_size(void);
 
+/* ---- duplicate metrics and library size (TIDDIT_DUPS) -------------------------------------------------- *
+ * No counterpart in the reference (its users run Picard MarkDuplicates / samtools markdup, one more pass over the file); the
+ * definition is tiddit_amd/tiddit_dup.py's.  A handle keeps a store of keys in HBM — per keyed read K1 = tid << 34 | E << 1 | rev,
+ * K2 = 0 (a fragment) or 1 << 58 | mate_tid << 34 | ME << 1 | mrev (the carrier of a pair), and the read's 0x400 bit — and ONE array of
+ * TDT_DUP_TOTAL uint64 counters (row-major):
+ *   SN    [TDT_DUP_SN_N]  records eligible malformed fragments pairs pair_mates pairs_no_mc flagged | fragment_sets pair_sets
+ *                         fragment_duplicates pair_duplicates
+ *   HIST  [1024][2]       sets of equal (K1, K2) by min(size, 1024) - 1: pair_sets fragment_sets
+ * A push adds one batch of reads, one launch: eligibility (flag & 0xB04 == 0, tid >= 0) and the carrier rule are tested on the field
+ * columns; a fragment or carrier has its record bounded as tdt_alleles bounds one (rec_off + 36 <= raw_len, 32 + l_read_name +
+ * 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <= block_size, rec_off + 4 + block_size <= raw_len), its CIGAR walked for the clip sums and, a
+ * carrier, its aux fields for the first MC:Z.  A record that fails the bounds, holds an op code above 8, a contig id of 2^24 or more, or
+ * an end outside [0, 2^33) after the bias of 2^28 adds one to `malformed` and gets no key; nothing outside [raw, raw + raw_len) is ever
+ * read.  The store grows by itself (1.5 x) and is in stream order, not file order.  tdt_dup_push_device takes the pointer table
+ * tdt_ingest_arrays filled, enqueues the launch on the context's stream and waits for nothing unless the store must grow; tdt_dup_push
+ * uploads host columns, runs the same kernel and returns when it is done.  tdt_dup_finish sorts the store (two stable radix sorts and a
+ * gather), measures the runs of equal keys and returns the whole counter array; the store is left as it was, so pushes may go on and a
+ * second finish gives the same answer.  tdt_dup_keys reads the store out (*n in: room of the arrays, out: keys stored; all three arrays
+ * NULL: the count alone).  tdt_dup_timing: device milliseconds of the last finish (sort by K2, gather, sort by K1, run lengths).
+ * Refusals: TDT_E_ARG (null pointers, record offsets that decrease, n >= 2^31), TDT_E_RANGE (more than 2^24 contigs, too little room
+ * in tdt_dup_keys, 2^30 keys or more at the finish: the sort's limit); a refused call leaves its outputs untouched.  The read-out calls
+ * synchronise the stream.  tdt_dup_size() = TDT_DUP_TOTAL. */
+#define TDT_DUP_SN_N 12
+#define TDT_DUP_OFF_HIST 12
+#define TDT_DUP_HIST_MAX 1024
+#define TDT_DUP_TOTAL 2060
+typedef struct tdt_dup tdt_dup;
+int tdt_dup_create(tdt_ctx *ctx, int n_contigs, int64_t max_contig_len, size_t capacity, tdt_dup **out);
+int tdt_dup_destroy(tdt_dup *h);
+int tdt_dup_reset(tdt_dup *h);
+int tdt_dup_push_device(tdt_dup *h, const void *const *d_arrays14, size_t n, size_t raw_len);
+int tdt_dup_push(tdt_dup *h, const uint16_t *flag, const int32_t *tid, const int32_t *pos, const int32_t *end, const int32_t *mate_tid,
+                 const int32_t *mate_pos, const uint64_t *rec_off, size_t n, const uint8_t *raw, size_t raw_len);
+int tdt_dup_keys(tdt_dup *h, uint64_t *k1, uint64_t *k2, uint8_t *marked, size_t *n);
+int tdt_dup_finish(tdt_dup *h, uint64_t *out);
+int tdt_dup_timing(tdt_dup *h, double *ms4);
+size_t tdt_dup_size(void);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

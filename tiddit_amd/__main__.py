@@ -37,6 +37,12 @@ again; on N ranks rank 0 holds the bins and the summed counters and runs the sta
 MAPQ, read lengths, insert sizes, per-cycle base composition and quality, the quality histogram, GC per read, CIGAR sums and indel
 lengths (tiddit_amd/tiddit_qc.py has the definition and the file's format).  Unset or empty is off; any other value ends the job with an
 error before the scan.  On N ranks every rank counts the records of its shard and rank 0 writes the summed tables.
+
+``TIDDIT_DUPS=1``: ``--sv`` also writes ``{o}.dup.tab`` — duplicate metrics recomputed from the reads' unclipped 5' ends (whatever the
+file's 0x400 marks say): fragment and pair duplicates, the histogram of set sizes, the duplication rate and the estimated library size
+(tiddit_amd/tiddit_dup.py has the definition and the file's format), from a key store the scan fills in HBM and one sort behind it.
+Unset or empty is off; any other value ends the job with an error before the scan.  One process only, refused on N ranks like
+``TIDDIT_DEPTH_DIST``: a set of duplicates can straddle a shard seam.
 """
 import argparse
 import os
@@ -247,6 +253,13 @@ def run_sv(args, version):
         # (the same)
         print("error, TIDDIT_QC={}: {}".format(os.environ.get("TIDDIT_QC"), e))
         sys.exit(1)
+    try:
+        from . import tiddit_dup
+        dups = tiddit_dup.parse_switch(os.environ.get("TIDDIT_DUPS"))
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_DUPS={}: {}".format(os.environ.get("TIDDIT_DUPS"), e))
+        sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
     if genotype_depth and sites_path is None:
@@ -309,6 +322,11 @@ def run_sv(args, version):
         # (the same: a base near a shard seam is covered by two shards' reads, and per-shard histograms of depth do not add up)
         print("error, TIDDIT_DEPTH_DIST is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
               "reads on another rank")
+        sys.exit(1)
+    if multi and dups:
+        # (the same: a set of duplicates can straddle a shard seam, and per-rank set counts do not add up)
+        print("error, TIDDIT_DUPS is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
+              "keys on another rank")
         sys.exit(1)
     if multi:
         import torch
@@ -462,6 +480,9 @@ def run_sv(args, version):
     if qc:
         # TIDDIT_QC: ... and fills the read-level QC tables, two launches per batch
         tiddit_signal.QC = True
+    if dups:
+        # TIDDIT_DUPS: ... and stores a duplicate key per fragment and pair, one launch per batch
+        tiddit_signal.DUPS = True
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -476,6 +497,7 @@ def run_sv(args, version):
                 tiddit_signal.COV_TRACK = None
             tiddit_signal.ALLELES = None
             tiddit_signal.QC = None
+            tiddit_signal.DUPS = None
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:
@@ -504,6 +526,12 @@ def run_sv(args, version):
         tiddit_qc.main(counter, prefix, multi=multi, rank=rank)
         T["qc tables ({o}.qc.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_qc.STAGE_SECONDS.items()})
+    if dups:
+        counter, tiddit_signal.DUP_COUNTER = tiddit_signal.DUP_COUNTER, None
+        t = time.time()
+        tiddit_dup.main(counter, prefix)
+        T["duplicates ({o}.dup.tab)"] = time.time() - t
+        T.update({"  " + k: v for k, v in tiddit_dup.STAGE_SECONDS.items()})
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,

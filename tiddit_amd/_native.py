@@ -147,6 +147,15 @@ SYMBOLS = {
     "tdt_qc_counts": (_i, [_P, _P]),
     "tdt_qc_counts_device": (_i, [_P, _P]),
     "tdt_qc_size": (_sz, []),
+    "tdt_dup_create": (_i, [_P, _i, _i64, _sz, _PP]),
+    "tdt_dup_destroy": (_i, [_P]),
+    "tdt_dup_reset": (_i, [_P]),
+    "tdt_dup_push_device": (_i, [_P, _P, _sz, _sz]),
+    "tdt_dup_push": (_i, [_P] * 8 + [_sz, _P, _sz]),
+    "tdt_dup_keys": (_i, [_P, _P, _P, _P, ctypes.POINTER(_sz)]),
+    "tdt_dup_finish": (_i, [_P, _P]),
+    "tdt_dup_timing": (_i, [_P, _P]),
+    "tdt_dup_size": (_sz, []),
     "tdt_format_coverage": (_i, [_P, _sz, ctypes.c_char_p, _i64, _i64, _i, _P, _sz, ctypes.POINTER(_sz)]),
     "tdt_fasta_write_fai": (_i, [ctypes.c_char_p, ctypes.c_char_p]),
     "tdt_host_threads": (_i, [_i]),

@@ -301,10 +301,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
 
     ``COV_TRACK = (bin_size, min_q)``: a second histogram over EVERY contig of the header is filled from the same batches (their second
     coverage-record column, written by the ingest kernel in the pass that decodes them) and its bins are left in ``COV_TRACK_BINS``."""
-    global COV_TRACK_BINS, ALLELE_COUNTER, QC_COUNTER
+    global COV_TRACK_BINS, ALLELE_COUNTER, QC_COUNTER, DUP_COUNTER
     COV_TRACK_BINS = None
     ALLELE_COUNTER = None
     QC_COUNTER = None
+    DUP_COUNTER = None
     track = COV_TRACK
     max_ins = int(max_ins)         # the reference's `int max_ins` argument truncates a float percentile (:147,:230; probed with Cython 3.2)
     from . import bamio
@@ -371,6 +372,14 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         from . import tiddit_qc
         qc = tiddit_qc.QcCounter(ctx=getattr(reader, "ctx", None))
         T["qc tables (push)"] = 0.0
+    dups = None
+    if DUPS:
+        # TIDDIT_DUPS: a key store in HBM; every batch costs one more launch on the columns and bytes it already holds there
+        from . import tiddit_dup
+        # (a paired 150-bp file holds a read per ~90 compressed bytes and a key per two reads: 1.4 x that; the store grows 1.5x when a batch does not fit)
+        dups = tiddit_dup.DupCounter(len(names), max(lengths) if len(lengths) else 0, capacity=max(os.path.getsize(bam_file_name) // 128, 1 << 16),
+                                     ctx=getattr(reader, "ctx", None))
+        T["duplicates (push)"] = 0.0
     tables = data = splits = clips = None
     if isinstance(reader, DeviceBamReader):
         from .sigtab import SignalTables
@@ -433,6 +442,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                     t3b = time.time()
                     T["qc tables (push)"] += t3b - t3
                     t3 = t3b
+                if dups is not None:                            # (the same)
+                    dups.push_device_batch(b)
+                    t3b = time.time()
+                    T["duplicates (push)"] += t3b - t3
+                    t3 = t3b
                 # the per-read chain of worker (:171-221) on the device; only the selected reads come back (fields + raw records)
                 # (once the scan's kernels are enqueued nothing will read the batch's raw bytes again: the next span's inflate is started
                 #  behind them — DeviceBamReader.ahead() — and runs while this thread waits for the selected reads and hands them on)
@@ -461,6 +475,10 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 t1b = time.time()
                 qc.push_host_batch(b)
                 T["qc tables (push)"] += time.time() - t1b
+            if dups is not None:
+                t1b = time.time()
+                dups.push_host_batch(b)
+                T["duplicates (push)"] += time.time() - t1b
             tid = b.tid
             flag = b.flag.astype(numpy.int32)
             placed = tid >= 0
@@ -525,6 +543,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             alleles.close()
         if qc is not None:
             qc.close()
+        if dups is not None:
+            dups.close()
         raise
     finally:
         pool.shutdown(wait=True)                              # (also on an error: no row thread outlives the scan)
@@ -541,9 +561,12 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         alleles.ctx.sync()                                      # (its launches read the reader's buffers, which go now)
     if qc is not None:
         qc.ctx.sync()                                           # (the same)
+    if dups is not None:
+        dups.ctx.sync()                                         # (the same)
     reader.close()
     ALLELE_COUNTER = alleles                                    # (the caller reads the counters and closes it)
     QC_COUNTER = qc                                             # (the same)
+    DUP_COUNTER = dups                                          # (the same: the caller runs its finish and closes it)
     if store is not None:
         from . import tiddit_variant
         if tiddit_variant.LIVE_STORE is not None:
@@ -595,6 +618,8 @@ ALLELES = None              # (site_pos, site_off, min_bq): the scan also counts
 ALLELE_COUNTER = None       # that counter after the last scan that had ALLELES set (the caller reads and closes it), else None
 QC = None                   # True: the scan also fills the read-level QC tables (tiddit_qc.QcCounter), two launches per batch
 QC_COUNTER = None           # that counter after the last scan that had QC set (the caller reads and closes it), else None
+DUPS = None                 # True: the scan also stores a duplicate key per fragment and pair (tiddit_dup.DupCounter), one launch per batch
+DUP_COUNTER = None          # that counter after the last scan that had DUPS set (the caller runs its finish and closes it), else None
 KEEP_EVIDENCE = False       # the scan packs every placed record into an evidence store for the variant stage (tiddit_variant.LIVE_STORE)
 AFTER_SCAN = []             # callables main() invokes once the file has been scanned, before the tables are written (host-only work from there on)
 READER_SECONDS = {}         # the reader thread of the last scan: seconds reading, scanning BGZF headers, building tables, waiting — and the consumer's waits
