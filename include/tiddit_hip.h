@@ -235,7 +235,7 @@ int tdt_signal_select_device(tdt_ctx *ctx, const uint16_t *d_flag, const uint8_t
                              int min_q, int64_t max_ins, uint32_t *d_out_idx, uint64_t *d_count);
 
 /* The WHOLE per-read chain of tiddit_signal.worker (tiddit_signal.pyx:171-221) on a decoded batch resident in HBM.  d_arrays14 =
- * the pointer table of tdt_ingest_arrays (tdt_bam_decode's field order, then the raw record bytes); contig_ok is a HOST array.
+ * the pointer table of tdt_ingest_arrays (TDT_COL_*: tdt_bam_decode's field order, then the raw record bytes); contig_ok is a HOST array.
  * Every read gets an action byte — 2: clipped read for local assembly (:190-197), 4: carries an SA tag, SA_analysis is called
  * (:199-202), 8: a discordant-pair row is appended (:204-221) — and the reads with any bit set are compacted in stream order
  * with their fields and raw record bytes, so that the host touches only those.  tdt_signal_scan returns how many (*n_sel) and
@@ -543,9 +543,12 @@ int tdt_bgzf_inflate_hbm(tdt_ctx *ctx, const uint8_t *comp, size_t len, uint8_t 
  * tdt_ingest_carry's host_chases) — the result is the sequential decode either way.  After a push has returned an error
  * the stream position is undefined: further pushes on that object are refused.  tdt_ingest_arrays: device pointers, valid until the next push, in tdt_bam_decode's
  * output order (tid, pos, end, mapq, flag, mate_tid, mate_pos, tlen, l_seq, cigar_first, cigar_last, rec_off, sa_off)
- * followed by the batch's raw record bytes (rec_off / sa_off index into them).  tdt_ingest_edges: record indices
+ * followed by the batch's raw record bytes (rec_off / sa_off index into them) — the TDT_COL_* below, the ONE statement of that
+ * order: every reader of the table indexes it by these names.  tdt_ingest_edges: record indices
  * where the contig id changes (*n = (size_t)-1 when there are more than 8191, i.e. the input is not coordinate
  * sorted).  tdt_ingest_carry: bytes of the pending partial record (0 after a well-formed file). */
+enum { TDT_COL_TID = 0, TDT_COL_POS, TDT_COL_END, TDT_COL_MAPQ, TDT_COL_FLAG, TDT_COL_MATE_TID, TDT_COL_MATE_POS, TDT_COL_TLEN, TDT_COL_L_SEQ,
+       TDT_COL_CIGAR_FIRST, TDT_COL_CIGAR_LAST, TDT_COL_REC_OFF, TDT_COL_SA_OFF, TDT_COL_RAW, TDT_NCOL };
 typedef struct tdt_ingest tdt_ingest;
 int tdt_ingest_create(tdt_ctx *ctx, int n_ref, tdt_ingest **out);
 int tdt_ingest_destroy(tdt_ingest *g);
@@ -630,7 +633,7 @@ int tdt_calib_stream_read(tdt_ctx *ctx, const void *d_buf, size_t bytes, int rep
  * sequence, qualities) bounded against its own block_size and raw_len and then walked.  A record that fails the bounds, holds an op
  * code above 8 or is asked for a query base at or beyond l_seq counts nothing and adds one to `malformed`; nothing outside
  * [raw, raw + raw_len) is ever read.  More than 2^32 - 1 reads on one site are outside the contract (the counters wrap).
- * The push of device arrays takes the pointer table tdt_ingest_arrays filled, is enqueued on the context's stream and waits for nothing; the
+ * The push of device arrays takes the pointer table tdt_ingest_arrays filled (TDT_COL_*), is enqueued on the context's stream and waits for nothing; the
  * push of host arrays uploads them, runs the same kernel and returns when it is done.  Refusals: TDT_E_ARG (null pointers, offsets
  * that decrease, sites not sorted / unique / >= 0, n >= 2^31), TDT_E_RANGE (min_bq outside 0 ... 93, 2^28 sites or more); a refused
  * call leaves its outputs untouched.  The read-out calls synchronise the stream; either of their last two pointers may be NULL. */
@@ -663,7 +666,7 @@ int tdt_alleles_counts_device(tdt_alleles *h, uint32_t *d_out, uint64_t *d_stat2
  * bounded first as tdt_alleles bounds one (rec_off + 36 <= raw_len, 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <=
  * block_size, rec_off + 4 + block_size <= raw_len; l_seq is the record's own): a record that fails, or holds a CIGAR op code above 8,
  * adds one to `malformed` and nothing else from its bytes; nothing outside [raw, raw + raw_len) is ever read.
- * tdt_qc_push_device takes the pointer table tdt_ingest_arrays filled, enqueues two launches on the context's stream, waits for nothing
+ * tdt_qc_push_device takes the pointer table tdt_ingest_arrays filled (TDT_COL_*), enqueues two launches on the context's stream, waits for nothing
  * and allocates nothing; tdt_qc_push uploads host columns, runs the same kernels and returns when they are done.  Refusals: TDT_E_ARG
  * (null pointers, record offsets that decrease, n >= 2^31, a misaligned device output); a refused call leaves its outputs untouched.
  * The read-out calls synchronise the stream.  tdt_qc_size() = TDT_QC_TOTAL. */
@@ -702,7 +705,7 @@ size_t tdt_qc_size(void);
  * carrier, its aux fields for the first MC:Z.  A record that fails the bounds, holds an op code above 8, a contig id of 2^24 or more, or
  * an end outside [0, 2^33) after the bias of 2^28 adds one to `malformed` and gets no key; nothing outside [raw, raw + raw_len) is ever
  * read.  The store grows by itself (1.5 x) and is in stream order, not file order.  tdt_dup_push_device takes the pointer table
- * tdt_ingest_arrays filled, enqueues the launch on the context's stream and waits for nothing unless the store must grow; tdt_dup_push
+ * tdt_ingest_arrays filled (TDT_COL_*), enqueues the launch on the context's stream and waits for nothing unless the store must grow; tdt_dup_push
  * uploads host columns, runs the same kernel and returns when it is done.  tdt_dup_finish sorts the store (two stable radix sorts and a
  * gather), measures the runs of equal keys and returns the whole counter array; the store is left as it was, so pushes may go on and a
  * second finish gives the same answer.  tdt_dup_keys reads the store out (*n in: room of the arrays, out: keys stored; all three arrays

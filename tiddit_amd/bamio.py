@@ -359,7 +359,16 @@ def find_block_start(path, offset):
 # ------------------------------------------------------------------------------------ device reader
 _FIELDS = (("tid", np.int32), ("pos", np.int32), ("end", np.int32), ("mapq", np.uint8), ("flag", np.uint16), ("mate_tid", np.int32),
            ("mate_pos", np.int32), ("tlen", np.int32), ("l_seq", np.int32), ("cigar_first", np.uint32), ("cigar_last", np.uint32),
-           ("rec_off", np.uint64), ("sa_off", np.int64))
+           ("rec_off", np.uint64), ("sa_off", np.int64))      # TDT_COL_* of include/tiddit_hip.h; "raw" closes the pointer table
+
+
+def host_columns(b, names):
+    """-> (contiguous arrays of the columns `names` of a host-decoded batch — or of any object that has them — in the dtypes of
+    ``_FIELDS``, its raw record bytes as uint8): what the ``tdt_*_push`` entries of host columns take"""
+    dt = dict(_FIELDS)
+    cols = [np.ascontiguousarray(getattr(b, k), dtype=dt[k]) for k in names]
+    raw = np.frombuffer(b.raw, dtype=np.uint8) if isinstance(b.raw, (bytes, bytearray)) else np.ascontiguousarray(b.raw, dtype=np.uint8)
+    return cols, raw
 
 
 class DeviceBatch:
@@ -377,9 +386,20 @@ class DeviceBatch:
         self.dev["raw"] = int(ptrs[13] or 0)
         self._host = {}
         self._live = True
+        self._table = None
 
     def __len__(self):
         return self._n
+
+    def pointer_table(self):
+        """the ``(c_void_p * 14)`` table ``tdt_ingest_arrays`` filled — the field arrays in ``_FIELDS`` order, then ``raw`` — for the
+        native entries that take a whole batch (each checks only the columns it reads).  Built once per batch."""
+        if self._table is None:
+            self._table = (ctypes.c_void_p * 14)(*[self.dev[k] or None for k in [k for k, _ in _FIELDS] + ["raw"]])
+        return self._table
+
+    def _gone(self):                    # (the device buffers are no longer this batch's)
+        self._live, self._table = False, None
 
     def __getattr__(self, name):
         if name.startswith("_") or name not in self.dev:
@@ -407,7 +427,7 @@ class DeviceBatch:
         if h:
             self._reader.ctx.lib.tdt_ingest_release(h)
             self._retained = None
-            self._live = False
+            self._gone()
 
 
 class ScanCarry:
@@ -861,7 +881,7 @@ class DeviceBamReader:
                     self.spans_ahead -= 1                           # (not ahead of anything: counted are spans begun before their turn)
                 self.ahead()
             if prev is not None and not getattr(prev, "_retained", None):
-                prev._live = False
+                prev._gone()
             n = ctypes.c_size_t(0)
             skip = (self._skip if self._b_lo == 0 else nothing) if first else 0
             final = self.shard is not None and abs0 + consumed >= self._x_hi

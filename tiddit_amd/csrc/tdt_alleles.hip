@@ -14,7 +14,8 @@
 //   * step k of a wave handles the k-th site of every lane: equal (site, column) keys are merged over the wave and ONE lane issues the
 //     atomic with the number of lanes that share the key (30 neighbouring reads on one site: two or three atomics, not 30).
 // Every counter is an order-independent integer sum: the result equals the per-read definition exactly.
-#include "tdt_common.h"
+#include "tdt_batch.h"
+#include "tdt_bam_record.h"
 
 typedef unsigned long long ull;
 
@@ -31,8 +32,7 @@ struct tdt_alleles {
     long long *d_off;                         // n_contigs + 1
     unsigned *d_cnt;                          // ns * 8
     ull *d_stat;                              // {reads used, malformed}
-    void *d_io;                               // columns + raw bytes of the host entry (grows)
-    size_t io_cap;
+    tdt_batch_io io;                          // columns + raw bytes of the host entry
 };
 
 struct AlIn {
@@ -42,12 +42,6 @@ struct AlIn {
     const uint64_t *rec_off;
     const uint8_t *raw;
 };
-
-__device__ __forceinline__ unsigned al_u32(const uint8_t *p) {
-    unsigned v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
 
 // first index in [lo, hi) whose site is >= v
 __device__ __forceinline__ long long al_lower_bound(const int32_t *__restrict__ s, long long lo, long long hi, int v) {
@@ -68,7 +62,7 @@ struct AlWalk {
 __device__ __forceinline__ int al_site(const uint8_t *__restrict__ cig, unsigned n_cig, const uint8_t *__restrict__ seq,
                                        const uint8_t *__restrict__ qual, int l_seq, int min_bq, AlWalk &w, int s) {
     while (w.j < n_cig) {
-        const unsigned cw = al_u32(cig + 4 * (size_t)w.j), op = cw & 0xf;
+        const unsigned cw = tdt_ld_u32(cig + 4 * (size_t)w.j), op = cw & 0xf;
         const long long len = cw >> 4;
         const bool ref = op == 0 || op == 2 || op == 3 || op == 7 || op == 8;       // M D N = X
         const bool qry = op == 0 || op == 1 || op == 4 || op == 7 || op == 8;       // M I S = X
@@ -87,14 +81,6 @@ __device__ __forceinline__ int al_site(const uint8_t *__restrict__ cig, unsigned
         w.j++;
     }
     return -1;
-}
-
-__device__ __forceinline__ int al_wave_max(int v) {
-    for (int d = 32; d > 0; d >>= 1) {
-        const int o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(AL_BLOCK) void al_count(AlIn I, int n, ull raw_len, const int32_t *__restrict__ site_pos,
@@ -123,15 +109,10 @@ __global__ __launch_bounds__(AL_BLOCK) void al_count(AlIn I, int n, ull raw_len,
     // ---- the reads that hold a site, compacted in read order
     const bool has = hi > lo;
     const ull m = __ballot(has);
-    if (lane == 0) s_wsum[wave] = __popcll(m);
-    __syncthreads();
-    int base = 0, total = 0;
-    for (int w = 0; w < AL_BLOCK / 64; w++) {
-        base += w < wave ? s_wsum[w] : 0;
-        total += s_wsum[w];
-    }
+    const tdt_slots S = tdt_block_slots<AL_BLOCK / 64>(m, s_wsum, lane, wave);
+    const int total = S.total;
     if (has) {
-        const int k = base + __popcll(m & ((1ull << lane) - 1ull));
+        const int k = S.base + tdt_lane_rank(m, lane);
         s_read[k] = (int)i;
         s_lo[k] = lo;
         s_hi[k] = hi;
@@ -151,22 +132,21 @@ __global__ __launch_bounds__(AL_BLOCK) void al_count(AlIn I, int n, ull raw_len,
         pos = I.pos[ri];
         const ull ro = I.rec_off[ri];
         bad = true;
-        if (raw_len >= 36 && ro <= raw_len - 36) {
-            const uint8_t *r = I.raw + ro + 4;
-            const unsigned bs = al_u32(I.raw + ro), l_name = r[8];
-            n_cig = (unsigned)r[12] | ((unsigned)r[13] << 8);
-            l_seq = (int)al_u32(r + 16);
+        if (TDT_REC_HEADER_INSIDE(raw_len, ro)) {
+            const tdt_rec R = TDT_REC_READ(I.raw, ro);
+            n_cig = R.n_cig;
+            l_seq = R.l_seq;
             if (n_cig == 0 || l_seq < 1) {             // not a read that counts (and not a malformed one)
                 live = false;
                 bad = false;
-            } else if (32ull + l_name + 4ull * n_cig + ((ull)l_seq + 1) / 2 + (ull)l_seq <= (ull)bs && (ull)bs <= raw_len - 4 - ro) {
-                cig = r + 32 + l_name;
-                seq = cig + 4 * (size_t)n_cig;
-                qual = seq + ((size_t)l_seq + 1) / 2;
+            } else if (TDT_REC_FITS(R, raw_len)) {
+                cig = I.raw + R.cig();
+                seq = I.raw + R.seq();
+                qual = I.raw + R.qual();
                 bad = false;
                 ull qlen = 0;
                 for (unsigned j = 0; j < n_cig; j++) {
-                    const unsigned cw = al_u32(cig + 4 * (size_t)j), op = cw & 0xf;
+                    const unsigned cw = tdt_ld_u32(cig + 4 * (size_t)j), op = cw & 0xf;
                     if (op > 8) bad = true;
                     if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) qlen += cw >> 4;
                 }
@@ -176,7 +156,7 @@ __global__ __launch_bounds__(AL_BLOCK) void al_count(AlIn I, int n, ull raw_len,
         if (bad) live = false;
     }
     if (__any(suspect)) {                              // the walk without counting
-        const int kmax = al_wave_max(suspect ? ns_mine : 0);
+        const int kmax = tdt_wave_reduce<tdt_max>(suspect ? ns_mine : 0);
         AlWalk w{0u, (long long)pos, 0ll};
         for (int k = 0; k < kmax; k++)
             if (suspect && !bad && k < ns_mine && al_site(cig, n_cig, seq, qual, l_seq, min_bq, w, site_pos[lo + k]) == -2) bad = true;
@@ -187,7 +167,7 @@ __global__ __launch_bounds__(AL_BLOCK) void al_count(AlIn I, int n, ull raw_len,
         if (m_used) atomicAdd(&stat[0], (ull)__popcll(m_used));
         if (m_bad) atomicAdd(&stat[1], (ull)__popcll(m_bad));
     }
-    const int kmax = al_wave_max(live ? ns_mine : 0);
+    const int kmax = tdt_wave_reduce<tdt_max>(live ? ns_mine : 0);
     AlWalk w{0u, (long long)pos, 0ll};
     for (int k = 0; k < kmax; k++) {
         int col = -1;
@@ -209,7 +189,7 @@ static void al_free(tdt_alleles *h) {
     if (h->d_off) (void)hipFree(h->d_off);
     if (h->d_cnt) (void)hipFree(h->d_cnt);
     if (h->d_stat) (void)hipFree(h->d_stat);
-    if (h->d_io) (void)hipFree(h->d_io);
+    if (h->io.d) (void)hipFree(h->io.d);
     delete h;
 }
 
@@ -248,7 +228,7 @@ extern "C" int tdt_alleles_create(tdt_ctx *ctx, const int32_t *site_pos, const i
         }
     }
     TDT_HIP(hipSetDevice(ctx->device));
-    tdt_alleles *h = new tdt_alleles{ctx, n_contigs, min_q, min_bq, ns, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    tdt_alleles *h = new tdt_alleles{ctx, n_contigs, min_q, min_bq, ns, nullptr, nullptr, nullptr, nullptr, {nullptr, 0}};
     const size_t N = ns ? ns : 1;
     if (tdt_dev_malloc((void **)&h->d_pos, N * 4) != hipSuccess || tdt_dev_malloc((void **)&h->d_off, (size_t)(n_contigs + 1) * 8) != hipSuccess ||
         tdt_dev_malloc((void **)&h->d_cnt, N * AL_COLS * 4) != hipSuccess || tdt_dev_malloc((void **)&h->d_stat, 256) != hipSuccess) {
@@ -300,67 +280,35 @@ static int al_launch(tdt_alleles *h, const AlIn &I, size_t n, size_t raw_len) {
     return TDT_OK;
 }
 
-// One batch of the device ingest: d_arrays14 = the pointer table tdt_ingest_arrays filled (a host array of 14 device pointers).  The
-// launch is enqueued on the context's stream; nothing is waited for.
+#define AL_NEED (TDT_NEED(TID) | TDT_NEED(POS) | TDT_NEED(END) | TDT_NEED(MAPQ) | TDT_NEED(FLAG) | TDT_NEED(REC_OFF) | TDT_NEED(RAW))
+
+// One batch of the device ingest: d_arrays14 = the pointer table tdt_ingest_arrays filled (TDT_COL_*: a host array of TDT_NCOL device
+// pointers).  The launch is enqueued on the context's stream; nothing is waited for.
 extern "C" int tdt_alleles_push_device(tdt_alleles *h, const void *const *d_arrays14, size_t n, size_t raw_len) {
-    if (!h || n >= 0x7fffffffull || (n && !d_arrays14)) {
-        tdt_set_error("tdt_alleles_push_device: bad argument");
-        return TDT_E_ARG;
-    }
+    tdt_batch B;                                       // (a handle without sites reads no column: none is asked for)
+    const int rc = tdt_batch_view("tdt_alleles_push_device", h, d_arrays14, n, raw_len, h && h->ns ? AL_NEED : 0u, &B);
+    if (rc) return rc;
     if (n == 0 || h->ns == 0) return TDT_OK;
-    const void *const *p = d_arrays14;
-    if (!p[0] || !p[1] || !p[2] || !p[3] || !p[4] || !p[11] || (raw_len && !p[13])) {
-        tdt_set_error("tdt_alleles_push_device: a column of the batch is NULL");
-        return TDT_E_ARG;
-    }
     TDT_HIP(hipSetDevice(h->ctx->device));
-    const AlIn I{(const int32_t *)p[0], (const int32_t *)p[1], (const int32_t *)p[2], (const uint8_t *)p[3], (const uint16_t *)p[4],
-                 (const uint64_t *)p[11], (const uint8_t *)p[13]};
-    return al_launch(h, I, n, raw_len);
+    return al_launch(h, AlIn{B.tid, B.pos, B.end, B.mapq, B.flag, B.rec_off, B.raw}, n, raw_len);
 }
 
 // The same kernel on host columns and host record bytes (uploaded into the handle's own block).  The stream is synchronised before the
 // return: the caller's arrays are free again.
 extern "C" int tdt_alleles_push(tdt_alleles *h, const int32_t *tid, const int32_t *pos, const int32_t *end, const uint8_t *mapq,
                                 const uint16_t *flag, const uint64_t *rec_off, size_t n, const uint8_t *raw, size_t raw_len) {
-    if (!h || n >= 0x7fffffffull || (n && (!tid || !pos || !end || !mapq || !flag || !rec_off)) || (raw_len && !raw)) {
-        tdt_set_error("tdt_alleles_push: bad argument");
-        return TDT_E_ARG;
-    }
-    if (n == 0 || h->ns == 0) return TDT_OK;
-    tdt_ctx *ctx = h->ctx;
-    TDT_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    tdt_carver sz(nullptr);
-    sz.take<int32_t>(3 * n), sz.take<uint64_t>(n), sz.take<uint16_t>(n), sz.take<uint8_t>(n), sz.take<uint8_t>(raw_len + 1);
-    if (sz.size > h->io_cap) {
-        TDT_HIP(hipStreamSynchronize(st));
-        if (h->d_io) TDT_HIP(hipFree(h->d_io));
-        h->d_io = nullptr;
-        h->io_cap = 0;
-        if (tdt_dev_malloc(&h->d_io, sz.size) != hipSuccess) {
-            tdt_set_error("tdt_alleles_push: out of device memory (%zu reads, %zu bytes)", n, raw_len);
-            return TDT_E_NOMEM;
-        }
-        h->io_cap = sz.size;
-    }
-    tdt_carver cv(h->d_io);
-    int32_t *d3 = cv.take<int32_t>(3 * n);
-    uint64_t *doff = cv.take<uint64_t>(n);
-    uint16_t *dflag = cv.take<uint16_t>(n);
-    uint8_t *dmapq = cv.take<uint8_t>(n);
-    uint8_t *draw = cv.take<uint8_t>(raw_len + 1);
-    TDT_HIP(hipMemcpyAsync(d3, tid, n * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(d3 + n, pos, n * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(d3 + 2 * n, end, n * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(doff, rec_off, n * 8, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(dflag, flag, n * 2, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(dmapq, mapq, n, hipMemcpyHostToDevice, st));
-    if (raw_len) TDT_HIP(hipMemcpyAsync(draw, raw, raw_len, hipMemcpyHostToDevice, st));
-    const AlIn I{d3, d3 + n, d3 + 2 * n, dmapq, dflag, doff, draw};
-    const int rc = al_launch(h, I, n, raw_len);
+    tdt_batch H{}, B;
+    H.tid = tid, H.pos = pos, H.end = end, H.mapq = mapq, H.flag = flag, H.rec_off = rec_off, H.raw = raw;
+    int rc = tdt_batch_host("tdt_alleles_push", h, H, n, raw_len, AL_NEED);
     if (rc) return rc;
-    TDT_HIP(hipStreamSynchronize(st));
+    // (no tdt_batch_offsets_ascend here, unlike tdt_qc_push / tdt_dup_push: this entry has never refused offsets that decrease, and
+    // al_count bounds every record by itself)
+    if (n == 0 || h->ns == 0) return TDT_OK;
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    rc = tdt_batch_upload("tdt_alleles_push", h->ctx, &h->io, H, AL_NEED, n, raw_len, &B);
+    if (rc == TDT_OK) rc = al_launch(h, AlIn{B.tid, B.pos, B.end, B.mapq, B.flag, B.rec_off, B.raw}, n, raw_len);
+    if (rc) return rc;
+    TDT_HIP(hipStreamSynchronize(h->ctx->stream));
     return TDT_OK;
 }
 

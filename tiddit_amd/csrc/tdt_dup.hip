@@ -25,7 +25,8 @@
 //     tiles, dup_runs measures every run at its END (position - last head + 1) and adds it to an LDS histogram whose non-zero words
 //     leave by 64-bit atomics.  No workgroup of these kernels waits for another, and no loop is as long as a run: one run of n equal
 //     keys costs what n distinct keys cost.
-#include "tdt_common.h"
+#include "tdt_batch.h"
+#include "tdt_bam_record.h"
 
 #include <vector>
 
@@ -60,8 +61,7 @@ struct tdt_dup {
     uint8_t *marked;
     size_t cap, upper;                        // upper: no more than this many keys are stored (the device knows how many)
     ull *d_state;                             // ST_WORDS
-    void *d_io;                               // columns + raw bytes of the host entry (grows)
-    size_t io_cap;
+    tdt_batch_io io;                          // columns + raw bytes of the host entry
     void *d_work;                             // the finish's buffers (grows)
     size_t work_cap;
     hipEvent_t ev[5];
@@ -74,17 +74,6 @@ struct DupIn {
     const uint64_t *rec_off;
     const uint8_t *raw;
 };
-
-__device__ __forceinline__ unsigned dup_u32(const uint8_t *p) {
-    unsigned v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-
-__device__ __forceinline__ ull dup_wave_or(ull v) {
-    for (int d = 32; d > 0; d >>= 1) v |= __shfl_xor(v, d);
-    return v;
-}
 
 __device__ __forceinline__ bool dup_is_pair(unsigned f, int mtid) { return (f & 0x1u) && !(f & 0x8u) && mtid >= 0; }
 
@@ -140,7 +129,7 @@ __device__ __forceinline__ bool dup_mate_cigar(const uint8_t *__restrict__ raw, 
             const unsigned sub = raw[p];
             const unsigned bsz = (sub == 'c' || sub == 'C') ? 1u : (sub == 's' || sub == 'S') ? 2u : (sub == 'i' || sub == 'I' || sub == 'f') ? 4u : 0u;
             if (!bsz) return false;
-            const ull bytes = 5ull + (ull)dup_u32(raw + p + 1) * bsz;
+            const ull bytes = 5ull + (ull)tdt_ld_u32(raw + p + 1) * bsz;
             if (p + bytes > e) return false;
             p += bytes;
         } else {
@@ -159,7 +148,6 @@ __global__ __launch_bounds__(DUP_BLOCK) void dup_keys(DupIn I, int n, ull raw_le
     __shared__ ull s_cnt[DUP_BLOCK / 64][SN_PUSH_N + 4];          // per wave: the push counters, then the OR / NAND words
     __shared__ ull s_base;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const ull below = (1ull << lane) - 1ull;
     const long long lo = (long long)blockIdx.x * DUP_K_TILE, hi = lo + DUP_K_TILE < n ? lo + DUP_K_TILE : n;
     ull cnt[SN_PUSH_N] = {0, 0, 0, 0, 0, 0, 0, 0};                // (wave-uniform: sums of ballots)
     ull or1 = 0, nand1 = 0, or2 = 0, nand2 = 0;                   // (this lane's keys; merged over the wave at the end)
@@ -184,17 +172,11 @@ __global__ __launch_bounds__(DUP_BLOCK) void dup_keys(DupIn I, int n, ull raw_le
         cnt[SN_RECORDS] += (ull)__popcll(m_rec);
         cnt[SN_ELIGIBLE] += (ull)__popcll(m_el);
         cnt[SN_PAIR_MATES] += (ull)__popcll(m_el & ~m_need);
-        if (lane == 0) s_wsum[wave] = __popcll(m_need);
-        __syncthreads();
-        int base = 0, total = 0;
-        for (int w = 0; w < DUP_BLOCK / 64; w++) {
-            base += w < wave ? s_wsum[w] : 0;
-            total += s_wsum[w];
-        }
-        if (need) s_read[base + __popcll(m_need & below)] = (int)i;
+        const tdt_slots S = tdt_block_slots<DUP_BLOCK / 64>(m_need, s_wsum, lane, wave);
+        if (need) s_read[S.base + tdt_lane_rank(m_need, lane)] = (int)i;
         __syncthreads();
         // ---- lane = compacted read: bound the record, walk its CIGAR once and (a carrier) its aux fields once
-        const bool live = t < total;
+        const bool live = t < S.total;
         bool ok = false, pair = false, no_mc = false;
         unsigned f = 0;
         ull k1 = 0, k2 = 0;
@@ -204,18 +186,17 @@ __global__ __launch_bounds__(DUP_BLOCK) void dup_keys(DupIn I, int n, ull raw_le
             const int tid = I.tid[ri], mtid = I.mate_tid[ri];
             pair = dup_is_pair(f, mtid);
             const ull ro = I.rec_off[ri];
-            if (tid < DUP_MAX_CONTIGS && !(pair && mtid >= DUP_MAX_CONTIGS) && raw_len >= 36 && ro <= raw_len - 36) {
+            if (tid < DUP_MAX_CONTIGS && !(pair && mtid >= DUP_MAX_CONTIGS) && TDT_REC_HEADER_INSIDE(raw_len, ro)) {
                 const uint8_t *__restrict__ raw = I.raw;
-                const uint8_t *r = raw + ro + 4;
-                const unsigned bs = dup_u32(raw + ro), l_name = r[8], n_cig = (unsigned)r[12] | ((unsigned)r[13] << 8);
-                const int l_seq = (int)dup_u32(r + 16);
-                const ull body = 32ull + l_name + 4ull * n_cig + ((ull)(l_seq < 0 ? 0 : l_seq) + 1) / 2 + (ull)(l_seq < 0 ? 0 : l_seq);
-                if (l_seq >= 0 && body <= (ull)bs && (ull)bs <= raw_len - 4 - ro) {
-                    const uint8_t *cig = r + 32 + l_name;
+                tdt_rec R = TDT_REC_READ(raw, ro);
+                const int l_seq = R.l_seq;
+                R.l_seq = l_seq < 0 ? 0 : l_seq;                   // (clamped: the body's sum never sees a negative length)
+                if (l_seq >= 0 && TDT_REC_FITS(R, raw_len)) {
+                    const uint8_t *cig = raw + R.cig();
                     bool bad = false, seen = false;
                     ull lead = 0, trail = 0;
-                    for (unsigned j = 0; j < n_cig; j++) {
-                        const unsigned cw = dup_u32(cig + 4ull * j), op = cw & 0xf, len = cw >> 4;
+                    for (unsigned j = 0; j < R.n_cig; j++) {
+                        const unsigned cw = tdt_ld_u32(cig + 4ull * j), op = cw & 0xf, len = cw >> 4;
                         bad |= op > 8;
                         if (op == 4 || op == 5) {
                             if (seen) trail += len;
@@ -235,7 +216,7 @@ __global__ __launch_bounds__(DUP_BLOCK) void dup_keys(DupIn I, int n, ull raw_le
                             const unsigned mrev = (f >> 5) & 1u;
                             ull mlead = 0, mtrail = 0, mref = 0;
                             long long mend5 = mpos;
-                            if (dup_mate_cigar(raw, ro + 4 + body, ro + 4 + bs, mlead, mtrail, mref))
+                            if (dup_mate_cigar(raw, R.aux(), R.end(), mlead, mtrail, mref))
                                 mend5 = mrev ? mpos + (long long)(mref ? mref : 1) - 1 + (long long)mtrail : mpos - (long long)mlead;
                             else
                                 no_mc = true;
@@ -255,24 +236,18 @@ __global__ __launch_bounds__(DUP_BLOCK) void dup_keys(DupIn I, int n, ull raw_le
         cnt[SN_PAIRS_NO_MC] += (ull)__popcll(__ballot(ok && pair && no_mc));
         cnt[SN_FLAGGED] += (ull)__popcll(__ballot(ok && (f & 0x400u)));
         if (ok) or1 |= k1, nand1 |= ~k1, or2 |= k2, nand2 |= ~k2;
-        if (lane == 0) s_wkeys[wave] = __popcll(m_ok);
-        __syncthreads();
         // ---- the round's keys behind the tile's earlier ones, in LDS
-        int kbase = 0, ktotal = 0;
-        for (int w = 0; w < DUP_BLOCK / 64; w++) {
-            kbase += w < wave ? s_wkeys[w] : 0;
-            ktotal += s_wkeys[w];
-        }
+        const tdt_slots K = tdt_block_slots<DUP_BLOCK / 64>(m_ok, s_wkeys, lane, wave);
         if (ok) {
-            const int slot = nk + kbase + __popcll(m_ok & below);  // (< DUP_K_TILE: at most one key per read of the tile)
+            const int slot = nk + K.base + tdt_lane_rank(m_ok, lane);      // (< DUP_K_TILE: at most one key per read of the tile)
             s_k1[slot] = k1;
             s_k2[slot] = k2;
             s_m[slot] = (f & 0x400u) ? 1 : 0;
         }
-        nk += ktotal;
+        nk += K.total;
     }
     // ---- the tile's counters: merged per wave, then over the workgroup, ONE atomic per non-zero counter
-    or1 = dup_wave_or(or1), nand1 = dup_wave_or(nand1), or2 = dup_wave_or(or2), nand2 = dup_wave_or(nand2);
+    or1 = tdt_wave_reduce<tdt_or>(or1), nand1 = tdt_wave_reduce<tdt_or>(nand1), or2 = tdt_wave_reduce<tdt_or>(or2), nand2 = tdt_wave_reduce<tdt_or>(nand2);
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < SN_PUSH_N; k++) s_cnt[wave][k] = cnt[k];
@@ -426,7 +401,7 @@ static void dup_free(tdt_dup *h) {
     if (h->k2) (void)hipFree(h->k2);
     if (h->marked) (void)hipFree(h->marked);
     if (h->d_state) (void)hipFree(h->d_state);
-    if (h->d_io) (void)hipFree(h->d_io);
+    if (h->io.d) (void)hipFree(h->io.d);
     if (h->d_work) (void)hipFree(h->d_work);
     for (int k = 0; k < 5; k++)
         if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
@@ -557,70 +532,34 @@ static int dup_launch(tdt_dup *h, const DupIn &I, size_t n, size_t raw_len) {
     return TDT_OK;
 }
 
-// One batch of the device ingest: d_arrays14 = the pointer table tdt_ingest_arrays filled (a host array of 14 device pointers).  The
-// launch is enqueued on the context's stream and nothing is waited for — unless the store must grow.
+#define DUP_NEED (TDT_NEED(FLAG) | TDT_NEED(TID) | TDT_NEED(POS) | TDT_NEED(END) | TDT_NEED(MATE_TID) | TDT_NEED(MATE_POS) | TDT_NEED(REC_OFF) | TDT_NEED(RAW))
+
+// One batch of the device ingest: d_arrays14 = the pointer table tdt_ingest_arrays filled (TDT_COL_*: a host array of TDT_NCOL device
+// pointers).  The launch is enqueued on the context's stream and nothing is waited for — unless the store must grow.
 extern "C" int tdt_dup_push_device(tdt_dup *h, const void *const *d_arrays14, size_t n, size_t raw_len) {
-    if (!h || n >= 0x7fffffffull || (n && !d_arrays14)) {
-        tdt_set_error("tdt_dup_push_device: bad argument");
-        return TDT_E_ARG;
-    }
+    tdt_batch B;
+    const int rc = tdt_batch_view("tdt_dup_push_device", h, d_arrays14, n, raw_len, DUP_NEED, &B);
+    if (rc) return rc;
     if (n == 0) return TDT_OK;
-    const void *const *p = d_arrays14;
-    if (!p[0] || !p[1] || !p[2] || !p[4] || !p[5] || !p[6] || !p[11] || (raw_len && !p[13])) {
-        tdt_set_error("tdt_dup_push_device: a column of the batch is NULL");
-        return TDT_E_ARG;
-    }
     TDT_HIP(hipSetDevice(h->ctx->device));
-    const DupIn I{(const uint16_t *)p[4], (const int32_t *)p[0], (const int32_t *)p[1], (const int32_t *)p[2], (const int32_t *)p[5],
-                  (const int32_t *)p[6], (const uint64_t *)p[11], (const uint8_t *)p[13]};
-    return dup_launch(h, I, n, raw_len);
+    return dup_launch(h, DupIn{B.flag, B.tid, B.pos, B.end, B.mate_tid, B.mate_pos, B.rec_off, B.raw}, n, raw_len);
 }
 
 // The same kernel on host columns and host record bytes (uploaded into the handle's own block).  The stream is synchronised before the
 // return: the caller's arrays are free again.
 extern "C" int tdt_dup_push(tdt_dup *h, const uint16_t *flag, const int32_t *tid, const int32_t *pos, const int32_t *end, const int32_t *mate_tid,
                             const int32_t *mate_pos, const uint64_t *rec_off, size_t n, const uint8_t *raw, size_t raw_len) {
-    if (!h || n >= 0x7fffffffull || (n && (!flag || !tid || !pos || !end || !mate_tid || !mate_pos || !rec_off)) || (raw_len && !raw)) {
-        tdt_set_error("tdt_dup_push: bad argument");
-        return TDT_E_ARG;
-    }
-    for (size_t i = 1; i < n; i++) {
-        if (rec_off[i] < rec_off[i - 1]) {
-            tdt_set_error("tdt_dup_push: record offsets must not decrease (record %zu)", i);
-            return TDT_E_ARG;
-        }
-    }
-    if (n == 0) return TDT_OK;
-    tdt_ctx *ctx = h->ctx;
-    TDT_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    tdt_carver sz(nullptr);
-    sz.take<int32_t>(5 * n), sz.take<uint64_t>(n), sz.take<uint16_t>(n), sz.take<uint8_t>(raw_len + 1);
-    if (sz.size > h->io_cap) {
-        TDT_HIP(hipStreamSynchronize(st));
-        if (h->d_io) TDT_HIP(hipFree(h->d_io));
-        h->d_io = nullptr;
-        h->io_cap = 0;
-        if (tdt_dev_malloc(&h->d_io, sz.size) != hipSuccess) {
-            tdt_set_error("tdt_dup_push: out of device memory (%zu reads, %zu bytes)", n, raw_len);
-            return TDT_E_NOMEM;
-        }
-        h->io_cap = sz.size;
-    }
-    tdt_carver cv(h->d_io);
-    int32_t *d5 = cv.take<int32_t>(5 * n);
-    uint64_t *doff = cv.take<uint64_t>(n);
-    uint16_t *dflag = cv.take<uint16_t>(n);
-    uint8_t *draw = cv.take<uint8_t>(raw_len + 1);
-    const int32_t *cols[5] = {tid, pos, end, mate_tid, mate_pos};
-    for (int k = 0; k < 5; k++) TDT_HIP(hipMemcpyAsync(d5 + k * n, cols[k], n * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(doff, rec_off, n * 8, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(dflag, flag, n * 2, hipMemcpyHostToDevice, st));
-    if (raw_len) TDT_HIP(hipMemcpyAsync(draw, raw, raw_len, hipMemcpyHostToDevice, st));
-    const DupIn I{dflag, d5, d5 + n, d5 + 2 * n, d5 + 3 * n, d5 + 4 * n, doff, draw};
-    const int rc = dup_launch(h, I, n, raw_len);
+    tdt_batch H{}, B;
+    H.flag = flag, H.tid = tid, H.pos = pos, H.end = end, H.mate_tid = mate_tid, H.mate_pos = mate_pos, H.rec_off = rec_off, H.raw = raw;
+    int rc = tdt_batch_host("tdt_dup_push", h, H, n, raw_len, DUP_NEED);
+    if (rc == TDT_OK) rc = tdt_batch_offsets_ascend("tdt_dup_push", rec_off, n);
     if (rc) return rc;
-    TDT_HIP(hipStreamSynchronize(st));
+    if (n == 0) return TDT_OK;
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    rc = tdt_batch_upload("tdt_dup_push", h->ctx, &h->io, H, DUP_NEED, n, raw_len, &B);
+    if (rc == TDT_OK) rc = dup_launch(h, DupIn{B.flag, B.tid, B.pos, B.end, B.mate_tid, B.mate_pos, B.rec_off, B.raw}, n, raw_len);
+    if (rc) return rc;
+    TDT_HIP(hipStreamSynchronize(h->ctx->stream));
     return TDT_OK;
 }
 

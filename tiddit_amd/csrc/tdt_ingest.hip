@@ -1199,9 +1199,13 @@ extern "C" int tdt_ingest_arrays(tdt_ingest *g, const void **out14, size_t *raw_
         return TDT_E_ARG;
     }
     const IngestOut &O = g->O;
-    const void *p[14] = {O.tid, O.pos, O.end, O.mapq, O.flag, O.mate_tid, O.mate_pos, O.tlen, O.l_seq, O.cigar_first, O.cigar_last, O.rec_off,
-                         O.sa_off, g->cur >= 0 && g->slot[g->cur].out.p ? (const char *)g->slot[g->cur].out.p + g->lead : nullptr};
-    for (int i = 0; i < 14; i++) out14[i] = g->n_records || i == 13 ? p[i] : nullptr;
+    static_assert(TDT_NCOL == 14, "out14 has fourteen entries");
+    const void *p[TDT_NCOL];
+    p[TDT_COL_TID] = O.tid, p[TDT_COL_POS] = O.pos, p[TDT_COL_END] = O.end, p[TDT_COL_MAPQ] = O.mapq, p[TDT_COL_FLAG] = O.flag;
+    p[TDT_COL_MATE_TID] = O.mate_tid, p[TDT_COL_MATE_POS] = O.mate_pos, p[TDT_COL_TLEN] = O.tlen, p[TDT_COL_L_SEQ] = O.l_seq;
+    p[TDT_COL_CIGAR_FIRST] = O.cigar_first, p[TDT_COL_CIGAR_LAST] = O.cigar_last, p[TDT_COL_REC_OFF] = O.rec_off, p[TDT_COL_SA_OFF] = O.sa_off;
+    p[TDT_COL_RAW] = g->cur >= 0 && g->slot[g->cur].out.p ? (const char *)g->slot[g->cur].out.p + g->lead : nullptr;
+    for (int i = 0; i < TDT_NCOL; i++) out14[i] = g->n_records || i == TDT_COL_RAW ? p[i] : nullptr;
     if (raw_len) *raw_len = g->out_len;
     return TDT_OK;
 }

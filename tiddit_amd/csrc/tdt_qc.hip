@@ -25,7 +25,8 @@
 //     QC_CYCLES takes one base of a read (+1, qual_sum +255 at the most), a GCR cell one read, an ID cell up to 65535 operations of a
 //     read: at most 65535 * QC_B_TILE < 2^32 between the zeroing and the flush of a workgroup.  QC_B_TILE is that bound.
 //   * either kernel ends with its workgroup adding the non-zero words of its image to the global array by 64-bit atomics.
-#include "tdt_common.h"
+#include "tdt_batch.h"
+#include "tdt_bam_record.h"
 
 typedef unsigned long long ull;
 
@@ -53,8 +54,7 @@ static_assert(SN_N == TDT_QC_SN_N, "SN rows");
 struct tdt_qc {
     tdt_ctx *ctx;
     ull *d_cnt;                               // TDT_QC_TOTAL
-    void *d_io;                               // columns + raw bytes of the host entry (grows)
-    size_t io_cap;
+    tdt_batch_io io;                          // columns + raw bytes of the host entry
 };
 
 struct QcIn {
@@ -64,12 +64,6 @@ struct QcIn {
     const uint64_t *rec_off;
     const uint8_t *raw;
 };
-
-__device__ __forceinline__ unsigned qc_u32(const uint8_t *p) {
-    unsigned v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
 
 // The value lane k holds, in a scalar register: what the wave branches and loops on must be uniform FOR THE COMPILER too (see qc_bases
 // above).  A value that comes out of __shfl is a vector register to it.
@@ -149,11 +143,6 @@ __global__ __launch_bounds__(QC_BLOCK) void qc_fields(QcIn I, int n, ull *__rest
     }
 }
 
-__device__ __forceinline__ ull qc_wave_sum(ull v) {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 __global__ __launch_bounds__(QC_BLOCK) void qc_bases(QcIn I, int n, ull raw_len, ull *__restrict__ g) {
     __shared__ unsigned s_cyc[QC_CYCLES * 7], s_gcr[101], s_id[QC_ID_MAX * 2];
     __shared__ ull s_sn[SN_N], s_qual[256], s_last[7];
@@ -181,15 +170,14 @@ __global__ __launch_bounds__(QC_BLOCK) void qc_bases(QcIn I, int n, ull raw_len,
                 inS = true;
                 bad = true;
                 const ull ro = I.rec_off[i];
-                if (raw_len >= 36 && ro <= raw_len - 36) {
-                    const uint8_t *r = raw + ro + 4;
-                    const unsigned bs = qc_u32(raw + ro), l_name = r[8];
-                    n_cig = (unsigned)r[12] | ((unsigned)r[13] << 8);
-                    l_seq = (int)qc_u32(r + 16);
-                    if (l_seq >= 0 && 32ull + l_name + 4ull * n_cig + ((ull)l_seq + 1) / 2 + (ull)l_seq <= (ull)bs && (ull)bs <= raw_len - 4 - ro) {
+                if (TDT_REC_HEADER_INSIDE(raw_len, ro)) {
+                    const tdt_rec R = TDT_REC_READ(raw, ro);
+                    n_cig = R.n_cig;
+                    l_seq = R.l_seq;
+                    if (l_seq >= 0 && TDT_REC_FITS(R, raw_len)) {
                         bad = false;
-                        cig_off = ro + 36 + l_name;
-                        if (l_seq > 0) hasq = raw[cig_off + 4ull * n_cig + ((ull)l_seq + 1) / 2] != 0xff;
+                        cig_off = R.cig();
+                        if (l_seq > 0) hasq = raw[R.qual()] != 0xff;    // (the first quality byte says whether the read has any)
                     }
                 }
             }
@@ -208,7 +196,7 @@ __global__ __launch_bounds__(QC_BLOCK) void qc_bases(QcIn I, int n, ull raw_len,
             bool badop = false;
             for (unsigned j0 = 0; j0 < r_ncig; j0 += 64) {
                 const unsigned j = j0 + lane;
-                if (j < r_ncig) badop |= (qc_u32(cig + 4ull * j) & 0xf) > 8;
+                if (j < r_ncig) badop |= (tdt_ld_u32(cig + 4ull * j) & 0xf) > 8;
             }
             if (__any(badop)) {
                 a_bad++;
@@ -223,7 +211,7 @@ __global__ __launch_bounds__(QC_BLOCK) void qc_bases(QcIn I, int n, ull raw_len,
                 for (unsigned j0 = 0; j0 < r_ncig; j0 += 64) {
                     const unsigned j = j0 + lane;
                     if (j < r_ncig) {
-                        const unsigned cw = qc_u32(cig + 4ull * j), op = cw & 0xf, len = cw >> 4;
+                        const unsigned cw = tdt_ld_u32(cig + 4ull * j), op = cw & 0xf, len = cw >> 4;
                         const int sn = (op == 0 || op == 7 || op == 8) ? SN_ALIGNED : op == 1 ? SN_INSERTED : op == 2 ? SN_DELETED : op == 3 ? SN_SKIPPED
                                      : op == 4 ? SN_SOFT : op == 5 ? SN_HARD : -1;
                         if (sn >= 0 && len) atomicAdd(&s_sn[sn], (ull)len);
@@ -276,7 +264,7 @@ __global__ __launch_bounds__(QC_BLOCK) void qc_bases(QcIn I, int n, ull raw_len,
                 }
             }
             if (L > QC_CYCLES) {
-                last_q = qc_wave_sum(last_q);
+                last_q = tdt_wave_reduce<tdt_sum>(last_q);
                 if (lane == 0) {
 #pragma unroll
                     for (int c = 0; c < 5; c++)
@@ -313,7 +301,7 @@ __global__ __launch_bounds__(QC_BLOCK) void qc_bases(QcIn I, int n, ull raw_len,
 
 static void qc_free(tdt_qc *h) {
     if (h->d_cnt) (void)hipFree(h->d_cnt);
-    if (h->d_io) (void)hipFree(h->d_io);
+    if (h->io.d) (void)hipFree(h->io.d);
     delete h;
 }
 
@@ -325,7 +313,7 @@ extern "C" int tdt_qc_create(tdt_ctx *ctx, tdt_qc **out) {
         return TDT_E_ARG;
     }
     TDT_HIP(hipSetDevice(ctx->device));
-    tdt_qc *h = new tdt_qc{ctx, nullptr, nullptr, 0};
+    tdt_qc *h = new tdt_qc{ctx, nullptr, {nullptr, 0}};
     if (tdt_dev_malloc((void **)&h->d_cnt, (size_t)TDT_QC_TOTAL * 8) != hipSuccess) {
         qc_free(h);
         tdt_set_error("tdt_qc_create: out of device memory");
@@ -367,74 +355,34 @@ static int qc_launch(tdt_qc *h, const QcIn &I, size_t n, size_t raw_len) {
     return TDT_OK;
 }
 
-// One batch of the device ingest: d_arrays14 = the pointer table tdt_ingest_arrays filled (a host array of 14 device pointers).  The two
-// launches are enqueued on the context's stream; nothing is waited for and nothing is allocated.
+#define QC_NEED (TDT_NEED(FLAG) | TDT_NEED(MAPQ) | TDT_NEED(TID) | TDT_NEED(MATE_TID) | TDT_NEED(TLEN) | TDT_NEED(L_SEQ) | TDT_NEED(REC_OFF) | TDT_NEED(RAW))
+
+// One batch of the device ingest: d_arrays14 = the pointer table tdt_ingest_arrays filled (TDT_COL_*: a host array of TDT_NCOL device
+// pointers).  The two launches are enqueued on the context's stream; nothing is waited for and nothing is allocated.
 extern "C" int tdt_qc_push_device(tdt_qc *h, const void *const *d_arrays14, size_t n, size_t raw_len) {
-    if (!h || n >= 0x7fffffffull || (n && !d_arrays14)) {
-        tdt_set_error("tdt_qc_push_device: bad argument");
-        return TDT_E_ARG;
-    }
+    tdt_batch B;
+    const int rc = tdt_batch_view("tdt_qc_push_device", h, d_arrays14, n, raw_len, QC_NEED, &B);
+    if (rc) return rc;
     if (n == 0) return TDT_OK;
-    const void *const *p = d_arrays14;
-    if (!p[0] || !p[3] || !p[4] || !p[5] || !p[7] || !p[8] || !p[11] || (raw_len && !p[13])) {
-        tdt_set_error("tdt_qc_push_device: a column of the batch is NULL");
-        return TDT_E_ARG;
-    }
     TDT_HIP(hipSetDevice(h->ctx->device));
-    const QcIn I{(const uint16_t *)p[4], (const uint8_t *)p[3], (const int32_t *)p[0], (const int32_t *)p[5], (const int32_t *)p[7],
-                 (const int32_t *)p[8], (const uint64_t *)p[11], (const uint8_t *)p[13]};
-    return qc_launch(h, I, n, raw_len);
+    return qc_launch(h, QcIn{B.flag, B.mapq, B.tid, B.mate_tid, B.tlen, B.l_seq, B.rec_off, B.raw}, n, raw_len);
 }
 
 // The same kernels on host columns and host record bytes (uploaded into the handle's own block).  The stream is synchronised before the
 // return: the caller's arrays are free again.
 extern "C" int tdt_qc_push(tdt_qc *h, const uint16_t *flag, const uint8_t *mapq, const int32_t *tid, const int32_t *mate_tid, const int32_t *tlen,
                            const int32_t *l_seq, const uint64_t *rec_off, size_t n, const uint8_t *raw, size_t raw_len) {
-    if (!h || n >= 0x7fffffffull || (n && (!flag || !mapq || !tid || !mate_tid || !tlen || !l_seq || !rec_off)) || (raw_len && !raw)) {
-        tdt_set_error("tdt_qc_push: bad argument");
-        return TDT_E_ARG;
-    }
-    for (size_t i = 1; i < n; i++) {
-        if (rec_off[i] < rec_off[i - 1]) {
-            tdt_set_error("tdt_qc_push: record offsets must not decrease (record %zu)", i);
-            return TDT_E_ARG;
-        }
-    }
-    if (n == 0) return TDT_OK;
-    tdt_ctx *ctx = h->ctx;
-    TDT_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    tdt_carver sz(nullptr);
-    sz.take<int32_t>(4 * n), sz.take<uint64_t>(n), sz.take<uint16_t>(n), sz.take<uint8_t>(n), sz.take<uint8_t>(raw_len + 1);
-    if (sz.size > h->io_cap) {
-        TDT_HIP(hipStreamSynchronize(st));
-        if (h->d_io) TDT_HIP(hipFree(h->d_io));
-        h->d_io = nullptr;
-        h->io_cap = 0;
-        if (tdt_dev_malloc(&h->d_io, sz.size) != hipSuccess) {
-            tdt_set_error("tdt_qc_push: out of device memory (%zu reads, %zu bytes)", n, raw_len);
-            return TDT_E_NOMEM;
-        }
-        h->io_cap = sz.size;
-    }
-    tdt_carver cv(h->d_io);
-    int32_t *d4 = cv.take<int32_t>(4 * n);
-    uint64_t *doff = cv.take<uint64_t>(n);
-    uint16_t *dflag = cv.take<uint16_t>(n);
-    uint8_t *dmapq = cv.take<uint8_t>(n);
-    uint8_t *draw = cv.take<uint8_t>(raw_len + 1);
-    TDT_HIP(hipMemcpyAsync(d4, tid, n * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(d4 + n, mate_tid, n * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(d4 + 2 * n, tlen, n * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(d4 + 3 * n, l_seq, n * 4, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(doff, rec_off, n * 8, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(dflag, flag, n * 2, hipMemcpyHostToDevice, st));
-    TDT_HIP(hipMemcpyAsync(dmapq, mapq, n, hipMemcpyHostToDevice, st));
-    if (raw_len) TDT_HIP(hipMemcpyAsync(draw, raw, raw_len, hipMemcpyHostToDevice, st));
-    const QcIn I{dflag, dmapq, d4, d4 + n, d4 + 2 * n, d4 + 3 * n, doff, draw};
-    const int rc = qc_launch(h, I, n, raw_len);
+    tdt_batch H{}, B;
+    H.flag = flag, H.mapq = mapq, H.tid = tid, H.mate_tid = mate_tid, H.tlen = tlen, H.l_seq = l_seq, H.rec_off = rec_off, H.raw = raw;
+    int rc = tdt_batch_host("tdt_qc_push", h, H, n, raw_len, QC_NEED);
+    if (rc == TDT_OK) rc = tdt_batch_offsets_ascend("tdt_qc_push", rec_off, n);
     if (rc) return rc;
-    TDT_HIP(hipStreamSynchronize(st));
+    if (n == 0) return TDT_OK;
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    rc = tdt_batch_upload("tdt_qc_push", h->ctx, &h->io, H, QC_NEED, n, raw_len, &B);
+    if (rc == TDT_OK) rc = qc_launch(h, QcIn{B.flag, B.mapq, B.tid, B.mate_tid, B.tlen, B.l_seq, B.rec_off, B.raw}, n, raw_len);
+    if (rc) return rc;
+    TDT_HIP(hipStreamSynchronize(h->ctx->stream));
     return TDT_OK;
 }
 

@@ -4,7 +4,7 @@
 //   sig_masks    lane = read: predicate -> 64-bit ballot word, tile count (4096 reads per workgroup)
 //   sig_compact  tile prefix = sum of the earlier tiles' counts (reduced in the workgroup), then wavefront
 //                compaction: a read's slot = prefix + set bits below its lane (mbcnt) — order preserving.
-#include "tdt_common.h"
+#include "tdt_batch.h"
 
 #define SG_THREADS 256
 #define SG_WORDS 64
@@ -298,17 +298,12 @@ extern "C" int tdt_signal_scan(tdt_ctx *ctx, const void *const *d_arrays14, size
     unsigned long long *d_total = (unsigned long long *)p;
     if (n_contigs) TDT_HIP(hipMemcpyAsync(d_ok, contig_ok, (size_t)n_contigs, hipMemcpyHostToDevice, st));
     ScanParams P;
-    P.tid = (const int32_t *)d_arrays14[0];
-    const int32_t *d_pos = (const int32_t *)d_arrays14[1], *d_end = (const int32_t *)d_arrays14[2];
-    P.mapq = (const uint8_t *)d_arrays14[3];
-    P.flag = (const uint16_t *)d_arrays14[4];
-    P.mate_tid = (const int32_t *)d_arrays14[5];
-    P.tlen = (const int32_t *)d_arrays14[7];
-    P.cig_first = (const uint32_t *)d_arrays14[9];
-    P.cig_last = (const uint32_t *)d_arrays14[10];
-    const unsigned long long *d_rec_off = (const unsigned long long *)d_arrays14[11];
-    P.sa_off = (const long long *)d_arrays14[12];
-    const uint8_t *d_raw = (const uint8_t *)d_arrays14[13];
+    const tdt_batch B = tdt_batch_of(d_arrays14);
+    P.tid = B.tid, P.mapq = B.mapq, P.flag = B.flag, P.mate_tid = B.mate_tid, P.tlen = B.tlen;
+    P.cig_first = B.cigar_first, P.cig_last = B.cigar_last, P.sa_off = (const long long *)B.sa_off;
+    const int32_t *d_pos = B.pos, *d_end = B.end;
+    const unsigned long long *d_rec_off = (const unsigned long long *)B.rec_off;
+    const uint8_t *d_raw = B.raw;
     P.contig_ok = d_ok;
     P.n_contigs = n_contigs;
     P.n = n;

@@ -52,7 +52,7 @@ import time
 
 import numpy
 
-from . import _native
+from . import _native, bamio
 
 COLUMNS = ("A", "C", "G", "T", "N", "DEL", "SKIP", "LOWBQ")
 A, C, G, T, N, DEL, SKIP, LOWBQ = range(8)
@@ -222,19 +222,12 @@ class AlleleCounter:
 
     def push_device_batch(self, b):
         """one DeviceBatch: enqueued on the reader's stream, nothing waited for (call before the batch's buffers are handed on)"""
-        d = b.dev
-        ptrs = (ctypes.c_void_p * 14)()
-        for i, k in ((0, "tid"), (1, "pos"), (2, "end"), (3, "mapq"), (4, "flag"), (11, "rec_off"), (13, "raw")):
-            ptrs[i] = d[k] or None
-        _native.check(self.ctx.lib.tdt_alleles_push_device(self.handle, ptrs, len(b), b._raw_len))
+        _native.check(self.ctx.lib.tdt_alleles_push_device(self.handle, b.pointer_table(), len(b), b._raw_len))
 
     def push_host_batch(self, b):
         """one host-decoded batch (or any object with its columns): uploaded, then the same kernel"""
-        n = len(b.tid)
-        cols = [numpy.ascontiguousarray(getattr(b, k), dtype=dt) for k, dt in (("tid", numpy.int32), ("pos", numpy.int32), ("end", numpy.int32),
-                                                                                ("mapq", numpy.uint8), ("flag", numpy.uint16), ("rec_off", numpy.uint64))]
-        raw = numpy.frombuffer(b.raw, dtype=numpy.uint8) if isinstance(b.raw, (bytes, bytearray)) else numpy.ascontiguousarray(b.raw, dtype=numpy.uint8)
-        _native.check(self.ctx.lib.tdt_alleles_push(self.handle, *[_native.ptr(c) for c in cols], n, _native.ptr(raw), len(raw)))
+        cols, raw = bamio.host_columns(b, ("tid", "pos", "end", "mapq", "flag", "rec_off"))      # (the arguments of tdt_alleles_push, in order)
+        _native.check(self.ctx.lib.tdt_alleles_push(self.handle, *[_native.ptr(c) for c in cols], len(cols[0]), _native.ptr(raw), len(raw)))
 
     def counts(self):
         """-> (uint32[sites][8], reads_used, malformed), behind everything pushed so far"""

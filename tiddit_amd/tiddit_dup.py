@@ -60,7 +60,7 @@ import time
 
 import numpy
 
-from . import _native
+from . import _native, bamio
 
 DUP_BIAS = 1 << 28
 DUP_HIST_MAX = 1024
@@ -383,10 +383,6 @@ def summarise_columns(k1, k2, sn):
 
 
 # ------------------------------------------------------------------------------------------- the device handle
-_COLUMNS = (("flag", numpy.uint16), ("tid", numpy.int32), ("pos", numpy.int32), ("end", numpy.int32), ("mate_tid", numpy.int32),
-            ("mate_pos", numpy.int32), ("rec_off", numpy.uint64))
-
-
 class DupCounter:
     """``tdt_dup_*``: the key store and the counters in HBM; one push per batch of the scan, one finish per job."""
 
@@ -399,16 +395,11 @@ class DupCounter:
 
     def push_device_batch(self, b):
         """one DeviceBatch: enqueued on the reader's stream, nothing waited for (call before the batch's buffers are handed on)"""
-        d = b.dev
-        ptrs = (ctypes.c_void_p * 14)()
-        for i, k in ((0, "tid"), (1, "pos"), (2, "end"), (4, "flag"), (5, "mate_tid"), (6, "mate_pos"), (11, "rec_off"), (13, "raw")):
-            ptrs[i] = d[k] or None
-        _native.check(self.ctx.lib.tdt_dup_push_device(self.handle, ptrs, len(b), b._raw_len))
+        _native.check(self.ctx.lib.tdt_dup_push_device(self.handle, b.pointer_table(), len(b), b._raw_len))
 
     def push_host_batch(self, b):
         """one host-decoded batch (or any object with its columns): uploaded, then the same kernel"""
-        cols = [numpy.ascontiguousarray(getattr(b, k), dtype=dt) for k, dt in _COLUMNS]
-        raw = numpy.frombuffer(b.raw, dtype=numpy.uint8) if isinstance(b.raw, (bytes, bytearray)) else numpy.ascontiguousarray(b.raw, dtype=numpy.uint8)
+        cols, raw = bamio.host_columns(b, ("flag", "tid", "pos", "end", "mate_tid", "mate_pos", "rec_off"))      # (the arguments of tdt_dup_push, in order)
         _native.check(self.ctx.lib.tdt_dup_push(self.handle, *[_native.ptr(c) for c in cols], len(cols[0]), _native.ptr(raw), len(raw)))
 
     def keys(self):

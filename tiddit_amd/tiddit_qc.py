@@ -51,7 +51,7 @@ import time
 
 import numpy
 
-from . import _native
+from . import _native, bamio
 
 QC_CYCLES, QC_IS_MAX, QC_ID_MAX = 512, 2000, 64
 SN = ("records", "secondary", "supplementary", "primary", "qc_fail", "duplicate", "unmapped", "mapped", "paired", "read1", "read2", "proper_pair",
@@ -293,10 +293,6 @@ def count_batch_columns(c, b, chunk_bases=1 << 22):
 
 
 # ------------------------------------------------------------------------------------------- the device handle
-_COLUMNS = (("flag", numpy.uint16), ("mapq", numpy.uint8), ("tid", numpy.int32), ("mate_tid", numpy.int32), ("tlen", numpy.int32),
-            ("l_seq", numpy.int32), ("rec_off", numpy.uint64))
-
-
 class QcCounter:
     """``tdt_qc_*``: the counter array in HBM; one push per batch of the scan."""
 
@@ -309,16 +305,11 @@ class QcCounter:
 
     def push_device_batch(self, b):
         """one DeviceBatch: enqueued on the reader's stream, nothing waited for (call before the batch's buffers are handed on)"""
-        d = b.dev
-        ptrs = (ctypes.c_void_p * 14)()
-        for i, k in ((0, "tid"), (3, "mapq"), (4, "flag"), (5, "mate_tid"), (7, "tlen"), (8, "l_seq"), (11, "rec_off"), (13, "raw")):
-            ptrs[i] = d[k] or None
-        _native.check(self.ctx.lib.tdt_qc_push_device(self.handle, ptrs, len(b), b._raw_len))
+        _native.check(self.ctx.lib.tdt_qc_push_device(self.handle, b.pointer_table(), len(b), b._raw_len))
 
     def push_host_batch(self, b):
         """one host-decoded batch (or any object with its columns): uploaded, then the same kernels"""
-        cols = [numpy.ascontiguousarray(getattr(b, k), dtype=dt) for k, dt in _COLUMNS]
-        raw = numpy.frombuffer(b.raw, dtype=numpy.uint8) if isinstance(b.raw, (bytes, bytearray)) else numpy.ascontiguousarray(b.raw, dtype=numpy.uint8)
+        cols, raw = bamio.host_columns(b, ("flag", "mapq", "tid", "mate_tid", "tlen", "l_seq", "rec_off"))      # (the arguments of tdt_qc_push, in order)
         _native.check(self.ctx.lib.tdt_qc_push(self.handle, *[_native.ptr(c) for c in cols], len(cols[0]), _native.ptr(raw), len(raw)))
 
     def counts(self):

@@ -136,7 +136,6 @@ _META = numpy.dtype([("idx", "<u4"), ("tid", "<i4"), ("pos", "<i4"), ("end", "<i
                      ("flag", "<u2"), ("action", "u1"), ("pad", "u1")])
 _SPLIT = numpy.dtype([("status", "<i4"), ("read_start", "<i4"), ("read_end", "<i4"), ("split_pos", "<i4"), ("sa_split", "<i4"), ("seg_start", "<i4"),
                       ("seg_end", "<i4"), ("chr_off", "<u4"), ("chr_len", "<u4"), ("is_reverse", "u1"), ("sa_minus", "u1"), ("pad", "<u2")])
-_FIELD_ORDER = ("tid", "pos", "end", "mapq", "flag", "mate_tid", "mate_pos", "tlen", "l_seq", "cigar_first", "cigar_last", "rec_off", "sa_off", "raw")
 
 
 class SelectedReads:
@@ -240,9 +239,8 @@ def _device_scan(batch, contig_ok, min_q, max_ins, min_anchor_len, min_clip_len,
     global _SEL_POOL
     ctx = ctx or _native.default_context()
     ok = numpy.ascontiguousarray(contig_ok, dtype=numpy.uint8)
-    table = (ctypes.c_void_p * 14)(*[batch.dev[k] or None for k in _FIELD_ORDER])
     n_sel, raw_bytes = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    _native.check(ctx.lib.tdt_signal_scan(ctx.handle, table, len(batch), _native.ptr(ok), len(ok), int(min_q), int(max_ins), int(min_anchor_len),
+    _native.check(ctx.lib.tdt_signal_scan(ctx.handle, batch.pointer_table(), len(batch), _native.ptr(ok), len(ok), int(min_q), int(max_ins), int(min_anchor_len),
                                           int(min_clip_len), ctypes.byref(n_sel), ctypes.byref(raw_bytes)))
     if launched is not None:
         launched()
