@@ -729,6 +729,50 @@ int tdt_dup_finish(tdt_dup *h, uint64_t *out);
 int tdt_dup_timing(tdt_dup *h, double *ms4);
 size_t tdt_dup_size(void);
 
+/* ---- small-indel candidates (TIDDIT_INDELS) ------------------------------------------------------------ *
+ * No counterpart in the reference (its signals start at discordant pairs and split reads); the definition is
+ * tiddit_amd/tiddit_indels.py's.  A handle keeps a store of keys in HBM — per keyed event (a flanked I or D operation of an eligible
+ * read's CIGAR, 1 <= len < TDT_INDEL_MAX_LEN) K1 = tid << 32 | P and K2 = type << 63 | len << 47 | kind << 45 | payload << 1 | rev —
+ * and TDT_INDEL_SN_N uint64 counters:
+ *   SN    records eligible malformed unanchored too_long noisy_reads reads_with_events insertions deletions | distinct_events
+ *         reported_events
+ * A push adds one batch of reads, one launch: eligibility (flag & 0xF04 == 0, tid >= 0, mapq >= min_mapq) is tested on the field
+ * columns; an eligible read has its record bounded as tdt_dup bounds one and its CIGAR walked once.  A record that fails the bounds,
+ * holds an op code above 8, has a tid of 2^24 or more, a negative pos, or a keyed event with P outside [1, 2^31) adds one to `malformed`
+ * and gives nothing else; a read with more than TDT_INDEL_MAX_PER_READ keyed events adds one to `noisy_reads` and gives no key; nothing
+ * outside [raw, raw + raw_len) is ever read.  The store grows by itself (1.5 x) and is in stream order, not file order: before each
+ * launch room for TDT_INDEL_MAX_PER_READ keys per read is reserved, and a reserve that does not fit first asks the device how many keys
+ * there really are.  tdt_indel_push_device takes the pointer table tdt_ingest_arrays filled (TDT_COL_*), enqueues the launch on the
+ * context's stream and waits for nothing unless the reserve must ask or grow; tdt_indel_push uploads host columns, runs the same kernel
+ * and returns when it is done.  tdt_indel_finish sorts the store (two stable radix sorts and a gather), measures the runs of equal
+ * (K1, K2 >> 1) — SUPPORT their size, REV the members with bit 0 set — fills sn_out[TDT_INDEL_SN_N] and keeps the runs with SUPPORT >=
+ * min_support as rows, ascending by key; the store is left as it was, so pushes may go on and another finish, with any min_support,
+ * gives the definition's answer.  tdt_indel_rows reads those rows out (K1, K2 with bit 0 clear, SUPPORT, REV; *n in: room of the arrays,
+ * out: rows; all four arrays NULL: the count alone); tdt_indel_keys the store (the same convention).  tdt_indel_timing: device
+ * milliseconds of the last finish (sort by K2, gather, sort by K1, run lengths and rows).  tdt_indel_reserve_stats: out3 = how often
+ * the reserve asked the device, how often the store grew, its capacity now.
+ * Refusals: TDT_E_ARG (null pointers, record offsets that decrease, n >= 2^31, tdt_indel_rows without a finish since the last push or
+ * reset), TDT_E_RANGE (more than 2^24 contigs, min_mapq outside 0 ... 255, min_support outside 1 ... TDT_INDEL_MAX_SUPPORT, too little
+ * room in tdt_indel_keys / tdt_indel_rows, 2^30 keys or more at the finish: the sort's limit); a refused call leaves its outputs
+ * untouched.  The read-out calls synchronise the stream.  tdt_indel_sn_size() = TDT_INDEL_SN_N. */
+#define TDT_INDEL_SN_N 11
+#define TDT_INDEL_MAX_PER_READ 4
+#define TDT_INDEL_MAX_LEN 65536
+#define TDT_INDEL_MAX_SUPPORT 1000000
+typedef struct tdt_indel tdt_indel;
+int tdt_indel_create(tdt_ctx *ctx, int n_contigs, int min_mapq, size_t capacity, tdt_indel **out);
+int tdt_indel_destroy(tdt_indel *h);
+int tdt_indel_reset(tdt_indel *h);
+int tdt_indel_push_device(tdt_indel *h, const void *const *d_arrays14, size_t n, size_t raw_len);
+int tdt_indel_push(tdt_indel *h, const uint16_t *flag, const int32_t *tid, const int32_t *pos, const uint8_t *mapq, const uint64_t *rec_off,
+                   size_t n, const uint8_t *raw, size_t raw_len);
+int tdt_indel_keys(tdt_indel *h, uint64_t *k1, uint64_t *k2, size_t *n);
+int tdt_indel_finish(tdt_indel *h, uint64_t min_support, uint64_t *sn_out, size_t *n_rows);
+int tdt_indel_rows(tdt_indel *h, uint64_t *k1, uint64_t *k2, uint32_t *support, uint32_t *rev, size_t *n);
+int tdt_indel_timing(tdt_indel *h, double *ms4);
+int tdt_indel_reserve_stats(tdt_indel *h, uint64_t *out3);
+size_t tdt_indel_sn_size(void);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

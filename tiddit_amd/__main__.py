@@ -43,6 +43,13 @@ file's 0x400 marks say): fragment and pair duplicates, the histogram of set size
 (tiddit_amd/tiddit_dup.py has the definition and the file's format), from a key store the scan fills in HBM and one sort behind it.
 Unset or empty is off; any other value ends the job with an error before the scan.  One process only, refused on N ranks like
 ``TIDDIT_DEPTH_DIST``: a set of duplicates can straddle a shard seam.
+
+``TIDDIT_INDELS=1`` (minimum support 2, minimum MAPQ 20), ``TIDDIT_INDELS=S`` or ``TIDDIT_INDELS=S:Q``: ``--sv`` also writes
+``{o}.indels.tab`` — every distinct insertion or deletion of 1 ... 65535 bases that at least ``S`` eligible reads (MAPQ >= ``Q``) carry in
+their CIGAR, with its support by strand and the job's own 50-bp coverage bin (tiddit_amd/tiddit_indels.py has the definition and the
+file's format), from a key store the scan fills in HBM and one sort behind it.  Unset or empty is off; a value that is none of the three
+forms ends the job with an error before the scan.  One process only, refused on N ranks like ``TIDDIT_DUPS``: merging per-rank rows
+needs an exchange of keys.
 """
 import argparse
 import os
@@ -260,6 +267,13 @@ def run_sv(args, version):
         # (the same)
         print("error, TIDDIT_DUPS={}: {}".format(os.environ.get("TIDDIT_DUPS"), e))
         sys.exit(1)
+    try:
+        from . import tiddit_indels
+        indels = tiddit_indels.parse_switch(os.environ.get("TIDDIT_INDELS"))
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_INDELS={}: {}".format(os.environ.get("TIDDIT_INDELS"), e))
+        sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
     if genotype_depth and sites_path is None:
@@ -326,6 +340,11 @@ def run_sv(args, version):
     if multi and dups:
         # (the same: a set of duplicates can straddle a shard seam, and per-rank set counts do not add up)
         print("error, TIDDIT_DUPS is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
+              "keys on another rank")
+        sys.exit(1)
+    if multi and indels is not None:
+        # (the same: an event's support is spread over the shards, and merging per-rank rows needs an exchange of keys)
+        print("error, TIDDIT_INDELS is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
               "keys on another rank")
         sys.exit(1)
     if multi:
@@ -483,6 +502,9 @@ def run_sv(args, version):
     if dups:
         # TIDDIT_DUPS: ... and stores a duplicate key per fragment and pair, one launch per batch
         tiddit_signal.DUPS = True
+    if indels is not None:
+        # TIDDIT_INDELS: ... and a key per small indel of the reads' CIGARs, one launch per batch
+        tiddit_signal.INDELS = indels
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -498,6 +520,7 @@ def run_sv(args, version):
             tiddit_signal.ALLELES = None
             tiddit_signal.QC = None
             tiddit_signal.DUPS = None
+            tiddit_signal.INDELS = None
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:
@@ -532,6 +555,14 @@ def run_sv(args, version):
         tiddit_dup.main(counter, prefix)
         T["duplicates ({o}.dup.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_dup.STAGE_SECONDS.items()})
+    if indels is not None:
+        # (behind the scan: coverage_data is final, no later stage writes into it)
+        counter, tiddit_signal.INDEL_COUNTER = tiddit_signal.INDEL_COUNTER, None
+        t = time.time()
+        tiddit_indels.main(counter, prefix, coverage_data, chromosomes, indels[0])
+        T["small indels ({o}.indels.tab)"] = time.time() - t
+        T.update({"  " + k: v for k, v in tiddit_indels.STAGE_SECONDS.items()})
+        STAGE_NOTES.update(tiddit_indels.STAGE_NOTES)
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,

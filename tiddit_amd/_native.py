@@ -156,6 +156,17 @@ SYMBOLS = {
     "tdt_dup_finish": (_i, [_P, _P]),
     "tdt_dup_timing": (_i, [_P, _P]),
     "tdt_dup_size": (_sz, []),
+    "tdt_indel_create": (_i, [_P, _i, _i, _sz, _PP]),
+    "tdt_indel_destroy": (_i, [_P]),
+    "tdt_indel_reset": (_i, [_P]),
+    "tdt_indel_push_device": (_i, [_P, _P, _sz, _sz]),
+    "tdt_indel_push": (_i, [_P] * 6 + [_sz, _P, _sz]),
+    "tdt_indel_keys": (_i, [_P, _P, _P, ctypes.POINTER(_sz)]),
+    "tdt_indel_finish": (_i, [_P, ctypes.c_uint64, _P, ctypes.POINTER(_sz)]),
+    "tdt_indel_rows": (_i, [_P, _P, _P, _P, _P, ctypes.POINTER(_sz)]),
+    "tdt_indel_timing": (_i, [_P, _P]),
+    "tdt_indel_reserve_stats": (_i, [_P, _P]),
+    "tdt_indel_sn_size": (_sz, []),
     "tdt_format_coverage": (_i, [_P, _sz, ctypes.c_char_p, _i64, _i64, _i, _P, _sz, ctypes.POINTER(_sz)]),
     "tdt_fasta_write_fai": (_i, [ctypes.c_char_p, ctypes.c_char_p]),
     "tdt_host_threads": (_i, [_i]),

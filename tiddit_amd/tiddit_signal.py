@@ -299,11 +299,12 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
 
     ``COV_TRACK = (bin_size, min_q)``: a second histogram over EVERY contig of the header is filled from the same batches (their second
     coverage-record column, written by the ingest kernel in the pass that decodes them) and its bins are left in ``COV_TRACK_BINS``."""
-    global COV_TRACK_BINS, ALLELE_COUNTER, QC_COUNTER, DUP_COUNTER
+    global COV_TRACK_BINS, ALLELE_COUNTER, QC_COUNTER, DUP_COUNTER, INDEL_COUNTER
     COV_TRACK_BINS = None
     ALLELE_COUNTER = None
     QC_COUNTER = None
     DUP_COUNTER = None
+    INDEL_COUNTER = None
     track = COV_TRACK
     max_ins = int(max_ins)         # the reference's `int max_ins` argument truncates a float percentile (:147,:230; probed with Cython 3.2)
     from . import bamio
@@ -378,6 +379,15 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         dups = tiddit_dup.DupCounter(len(names), max(lengths) if len(lengths) else 0, capacity=max(os.path.getsize(bam_file_name) // 128, 1 << 16),
                                      ctx=getattr(reader, "ctx", None))
         T["duplicates (push)"] = 0.0
+    indels = None
+    if INDELS is not None:
+        # TIDDIT_INDELS: a key store in HBM; every batch costs one more launch on the columns and bytes it already holds there
+        from . import tiddit_indels
+        # (room for 4 keys per read is reserved before each launch: a read per ~90 compressed bytes makes file size / 16 about 1.4 x the whole
+        #  file's bound; capped at 2^26 keys = 1 GB, behind which a reserve asks the device for the real count every few batches)
+        indels = tiddit_indels.IndelCounter(len(names), INDELS[1], capacity=min(max(os.path.getsize(bam_file_name) // 16, 1 << 16), 1 << 26),
+                                            ctx=getattr(reader, "ctx", None))
+        T["indel keys (push)"] = 0.0
     tables = data = splits = clips = None
     if isinstance(reader, DeviceBamReader):
         from .sigtab import SignalTables
@@ -445,6 +455,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                     t3b = time.time()
                     T["duplicates (push)"] += t3b - t3
                     t3 = t3b
+                if indels is not None:                          # (the same)
+                    indels.push_device_batch(b)
+                    t3b = time.time()
+                    T["indel keys (push)"] += t3b - t3
+                    t3 = t3b
                 # the per-read chain of worker (:171-221) on the device; only the selected reads come back (fields + raw records)
                 # (once the scan's kernels are enqueued nothing will read the batch's raw bytes again: the next span's inflate is started
                 #  behind them — DeviceBamReader.ahead() — and runs while this thread waits for the selected reads and hands them on)
@@ -477,6 +492,10 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 t1b = time.time()
                 dups.push_host_batch(b)
                 T["duplicates (push)"] += time.time() - t1b
+            if indels is not None:
+                t1b = time.time()
+                indels.push_host_batch(b)
+                T["indel keys (push)"] += time.time() - t1b
             tid = b.tid
             flag = b.flag.astype(numpy.int32)
             placed = tid >= 0
@@ -543,6 +562,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             qc.close()
         if dups is not None:
             dups.close()
+        if indels is not None:
+            indels.close()
         raise
     finally:
         pool.shutdown(wait=True)                              # (also on an error: no row thread outlives the scan)
@@ -561,10 +582,13 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         qc.ctx.sync()                                           # (the same)
     if dups is not None:
         dups.ctx.sync()                                         # (the same)
+    if indels is not None:
+        indels.ctx.sync()                                       # (the same)
     reader.close()
     ALLELE_COUNTER = alleles                                    # (the caller reads the counters and closes it)
     QC_COUNTER = qc                                             # (the same)
     DUP_COUNTER = dups                                          # (the same: the caller runs its finish and closes it)
+    INDEL_COUNTER = indels                                      # (the same)
     if store is not None:
         from . import tiddit_variant
         if tiddit_variant.LIVE_STORE is not None:
@@ -618,6 +642,8 @@ QC = None                   # True: the scan also fills the read-level QC tables
 QC_COUNTER = None           # that counter after the last scan that had QC set (the caller reads and closes it), else None
 DUPS = None                 # True: the scan also stores a duplicate key per fragment and pair (tiddit_dup.DupCounter), one launch per batch
 DUP_COUNTER = None          # that counter after the last scan that had DUPS set (the caller runs its finish and closes it), else None
+INDELS = None               # (min_support, min_mapq): the scan also stores a key per small indel of the reads' CIGARs (tiddit_indels.IndelCounter), one launch per batch
+INDEL_COUNTER = None        # that counter after the last scan that had INDELS set (the caller runs its finish and closes it), else None
 KEEP_EVIDENCE = False       # the scan packs every placed record into an evidence store for the variant stage (tiddit_variant.LIVE_STORE)
 AFTER_SCAN = []             # callables main() invokes once the file has been scanned, before the tables are written (host-only work from there on)
 READER_SECONDS = {}         # the reader thread of the last scan: seconds reading, scanning BGZF headers, building tables, waiting — and the consumer's waits
