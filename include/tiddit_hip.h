@@ -773,6 +773,46 @@ int tdt_indel_timing(tdt_indel *h, double *ms4);
 int tdt_indel_reserve_stats(tdt_indel *h, uint64_t *out3);
 size_t tdt_indel_sn_size(void);
 
+/* ---- the resident reference sequence ------------------------------------------------------------------ *
+ * The reference in HBM for the kernels of the --sv scan that need it (csrc/tdt_refseq.hip).  A handle owns ONE buffer of 4-bit base
+ * codes, BAM's own ("=ACMGRSVTWYHKDBN"), two bases per byte with the even base in the high nibble — a record's sequence layout, so a
+ * read's nibble and a reference nibble compare directly — and a table of every contig's byte offset and length.  Every contig starts on
+ * an 8-byte boundary and has at least 8 zero bytes in front of it and behind it: code 0 is no base, a comparison that runs off a contig
+ * stops there, and whole 64-bit words can be loaded at either end without a bounds branch.  The lengths are fixed by tdt_refseq_create
+ * (each 0 ... 2^31 - 1, at most 2^24 contigs); the store is allocated and zeroed there.
+ * tdt_refseq_load_fasta packs ONE contig from host bytes exactly as they are in the FASTA file (line ends included, LF or CRLF:
+ * `linebases` bases and `linewidth` bytes per full line, the .fai columns; the layouts tdt_gc_bins_fasta_device takes, TDT_E_UNSUPPORTED
+ * for the others): uploaded, packed by one launch (a lane = 16 bases = one 64-bit store), the staging buffer freed.
+ * tdt_refseq_load_fasta_device does the same on caller-owned device bytes.  Letters map to their code in either case, every other byte
+ * to 15 (N).  Both return when the contig is packed.  tdt_refseq_fetch: n codes from base `start` on, one per output byte.
+ * tdt_refseq_layout: out3 = the store's bytes, the guard bytes between contigs, the bases one workgroup of the pack kernel takes;
+ * offsets (or NULL): every contig's byte offset; store_out (or NULL): the whole store, room for out3[0] bytes.
+ * Refusals, TDT_E_ARG: null pointers, a tid outside the table, a length that differs from the one given at create, a contig loaded
+ * twice, too few bytes for the length, a fetch outside the contig or of a contig that is not loaded, a contig of 2^31 bases or more.
+ * A refused call leaves its outputs and the store untouched. */
+typedef struct tdt_refseq tdt_refseq;
+int tdt_refseq_create(tdt_ctx *ctx, int n_contigs, const int64_t *lengths, tdt_refseq **out);
+int tdt_refseq_destroy(tdt_refseq *h);
+int tdt_refseq_load_fasta(tdt_refseq *h, int tid, const uint8_t *raw, int64_t nbytes, int64_t length, int linebases, int linewidth);
+int tdt_refseq_load_fasta_device(tdt_refseq *h, int tid, const uint8_t *d_raw, int64_t nbytes, int64_t length, int linebases, int linewidth);
+int tdt_refseq_fetch(tdt_refseq *h, int tid, int64_t start, int64_t n, uint8_t *codes_out);
+int tdt_refseq_layout(tdt_refseq *h, uint64_t *out3, uint64_t *offsets, uint8_t *store_out);
+/* tests only: the store words of a contig that is not loaded yet (never a guard byte) filled with `byte` — a load behind it must
+ * overwrite every nibble of them.  TDT_E_ARG: a tid outside the table, a contig that is loaded. */
+int tdt_debug_refseq_fill(tdt_refseq *h, int tid, int byte);
+
+/* ---- small-indel candidates, left-normalised (TIDDIT_INDELS_NORM) -------------------------------------- *
+ * tdt_indel_set_reference attaches a resident reference to a tdt_indel handle (NULL detaches it; the reference is not owned, must lie
+ * on the handle's device and outlive the attachment).  With one attached, a push moves every keyed event of an OK read as far left as
+ * the reference allows before its keys are made — tiddit_amd/tiddit_indels.py: left_normalise; at most TDT_INDEL_NORM_MAX_SHIFT bases,
+ * never to a P below 1, only across A C G T — and an insertion's payload is that of the rotated allele.  Without one the push is the
+ * kernel it always was.  tdt_indel_norm_stats: out3 = events shifted, shifts that stopped at the cap, events off the reference (contig
+ * not loaded, or the event reaches beyond the contig's end: key unchanged), since the last reset; it synchronises the stream.  The
+ * eleven SN counters, the store, the finish and the rows are unchanged.  TDT_E_ARG: null pointers, a reference of another device. */
+#define TDT_INDEL_NORM_MAX_SHIFT 1024
+int tdt_indel_set_reference(tdt_indel *h, tdt_refseq *ref);
+int tdt_indel_norm_stats(tdt_indel *h, uint64_t *out3);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

@@ -50,6 +50,12 @@ their CIGAR, with its support by strand and the job's own 50-bp coverage bin (ti
 file's format), from a key store the scan fills in HBM and one sort behind it.  Unset or empty is off; a value that is none of the three
 forms ends the job with an error before the scan.  One process only, refused on N ranks like ``TIDDIT_DUPS``: merging per-rank rows
 needs an exchange of keys.
+
+``TIDDIT_INDELS_NORM=1`` (valid only together with ``TIDDIT_INDELS``): the reference FASTA is packed into HBM before the scan
+(tiddit_amd/refseq.py) and every event is left-normalised against it before its keys are made, so one indel of a repeat that reads
+place differently is one row (tiddit_indels.left_normalise has the definition).  Unset or empty is off; any other value, the switch
+without ``TIDDIT_INDELS``, or a contig of the BAM header that the FASTA lacks or holds at another length ends the job with an error
+before the scan.
 """
 import argparse
 import os
@@ -274,6 +280,12 @@ def run_sv(args, version):
         # (the same)
         print("error, TIDDIT_INDELS={}: {}".format(os.environ.get("TIDDIT_INDELS"), e))
         sys.exit(1)
+    try:
+        indels_norm = tiddit_indels.parse_norm_switch(os.environ.get("TIDDIT_INDELS_NORM"), indels)
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_INDELS_NORM={}: {}".format(os.environ.get("TIDDIT_INDELS_NORM"), e))
+        sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
     if genotype_depth and sites_path is None:
@@ -309,6 +321,16 @@ def run_sv(args, version):
     contig_number = {c: i for i, c in enumerate(contigs)}
     contig_length = {c["SN"]: c["LN"] for c in bam_header["SQ"]}
     prefix = args.o
+    if indels_norm:
+        # TIDDIT_INDELS_NORM: the contigs of the BAM header are matched to the FASTA's by name now — one that is missing or has another
+        # length ends the job before anything is made
+        from . import refseq
+        norm_fasta = FastaFile(args.ref)
+        try:
+            refseq.check_against_bam(norm_fasta, chromosomes, [contig_length[c] for c in chromosomes])
+        except ValueError as e:
+            print("error, TIDDIT_INDELS_NORM=1: {}".format(e))
+            sys.exit(1)
     allele_sites = None
     if alleles is not None:
         # TIDDIT_ALLELES: the sites are read now, on every rank — a file that cannot be read ends the job before anything is made
@@ -505,6 +527,15 @@ def run_sv(args, version):
     if indels is not None:
         # TIDDIT_INDELS: ... and a key per small indel of the reads' CIGARs, one launch per batch
         tiddit_signal.INDELS = indels
+    if indels_norm:
+        # TIDDIT_INDELS_NORM: the reference goes into HBM before the scan (every contig of the BAM header: read, uploaded, packed to
+        # 4-bit codes) and the scan's key kernel moves every event as far left as it allows
+        t_ref = time.time()
+        reference, t_read, t_load = refseq.load_for_bam(norm_fasta, chromosomes, [contig_length[c] for c in chromosomes])
+        T["reference into HBM (TIDDIT_INDELS_NORM)"] = time.time() - t_ref
+        T["  reference: file read (host)"] = t_read
+        T["  reference: upload + ref_pack (returns when packed)"] = t_load
+        tiddit_signal.INDEL_REFERENCE = reference
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -521,6 +552,7 @@ def run_sv(args, version):
             tiddit_signal.QC = None
             tiddit_signal.DUPS = None
             tiddit_signal.INDELS = None
+            tiddit_signal.INDEL_REFERENCE = None      # (the counter holds it from here on)
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:

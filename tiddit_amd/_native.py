@@ -167,6 +167,15 @@ SYMBOLS = {
     "tdt_indel_timing": (_i, [_P, _P]),
     "tdt_indel_reserve_stats": (_i, [_P, _P]),
     "tdt_indel_sn_size": (_sz, []),
+    "tdt_indel_set_reference": (_i, [_P, _P]),
+    "tdt_indel_norm_stats": (_i, [_P, _P]),
+    "tdt_refseq_create": (_i, [_P, _i, _P, _PP]),
+    "tdt_refseq_destroy": (_i, [_P]),
+    "tdt_refseq_load_fasta": (_i, [_P, _i, _P, _i64, _i64, _i, _i]),
+    "tdt_refseq_load_fasta_device": (_i, [_P, _i, _P, _i64, _i64, _i, _i]),
+    "tdt_refseq_fetch": (_i, [_P, _i, _i64, _i64, _P]),
+    "tdt_refseq_layout": (_i, [_P, _P, _P, _P]),
+    "tdt_debug_refseq_fill": (_i, [_P, _i, _i]),
     "tdt_format_coverage": (_i, [_P, _sz, ctypes.c_char_p, _i64, _i64, _i, _P, _sz, ctypes.POINTER(_sz)]),
     "tdt_fasta_write_fai": (_i, [ctypes.c_char_p, ctypes.c_char_p]),
     "tdt_host_threads": (_i, [_i]),

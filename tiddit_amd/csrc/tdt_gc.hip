@@ -10,6 +10,7 @@
 //            for 50-bp bins), then rounds in integers and stores one int8.
 // Bins wider than GC_SMALL_MAX use one workgroup per bin with a wavefront/LDS reduction.
 #include "tdt_common.h"
+#include "tdt_fasta_map.h"
 
 #define GC_THREADS 256
 #define GC_SMALL_MAX 2048
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(GC_THREADS) void gc_small_bins(const uint8_t *__res
 // reference reads the file through pysam.FastaFile one 50-bp slice at a time (tiddit_gc.pyx:14-19); this removes the
 // host-side newline stripping (two full copies of a 3 GB genome) from the path.
 __global__ __launch_bounds__(GC_THREADS) void gc_fasta_bins(const uint8_t *__restrict__ raw, long long nbytes, long long len, int bin_size,
-                                                            unsigned linebases, unsigned linewidth, unsigned magic, int shift, int tile_bins,
+                                                            tdt_fasta_map map, int tile_bins,
                                                             int max_chunks, long long nbins, unsigned n_min, signed char *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned gc_smem[];
     const int words = (max_chunks + 1) >> 1;
@@ -163,10 +164,7 @@ __global__ __launch_bounds__(GC_THREADS) void gc_fasta_bins(const uint8_t *__res
     unsigned short *g16 = reinterpret_cast<unsigned short *>(gbits);
     unsigned short *n16 = reinterpret_cast<unsigned short *>(nbits);
     const int tid = threadIdx.x;
-    auto fb = [&](unsigned b) -> long long {          // byte offset of base b (b < 2^31)
-        const unsigned line = shift < 0 ? b : (unsigned)(__umulhi(b, magic) >> shift);
-        return (long long)line * linewidth + (b - line * linebases);
-    };
+    auto fb = [&](unsigned b) -> long long { return map.byte_of(b); };          // byte offset of base b (b < 2^31)
     for (long long tile = blockIdx.x; tile * tile_bins < nbins; tile += gridDim.x) {
         const long long B0 = tile * (long long)tile_bins * bin_size;
         long long B1 = B0 + (long long)tile_bins * bin_size;
@@ -338,33 +336,21 @@ extern "C" int tdt_gc_bins_fasta_device(tdt_ctx *ctx, const uint8_t *d_raw, int6
         return TDT_E_ARG;
     }
     if (len == 0) return TDT_OK;
-    if (linebases <= 0 || linewidth < linebases || linewidth > linebases + 2 || bin_size > GC_SMALL_MAX || len >= (1ll << 31) ||
-        ((uintptr_t)d_raw & 15) != 0) {
+    if (!tdt_fasta_layout_ok(len, linebases, linewidth) || bin_size > GC_SMALL_MAX || ((uintptr_t)d_raw & 15) != 0) {
         tdt_set_error("tdt_gc_bins_fasta_device: unsupported layout (linebases %d, linewidth %d, bin %d, len %lld): strip the line ends "
                       "on the host and use tdt_gc_bins", linebases, linewidth, bin_size, (long long)len);
         return TDT_E_UNSUPPORTED;
     }
-    const long long nfull = len / linebases, tail = len - nfull * linebases;
-    const long long need = nfull * linewidth + tail - (tail == 0 ? (linewidth - linebases) : 0);
-    if (nbytes < need) {
+    if (nbytes < tdt_fasta_bytes(len, linebases, linewidth)) {
         tdt_set_error("tdt_gc_bins_fasta_device: %lld bytes cannot hold %lld bases at %d/%d per line", (long long)nbytes, (long long)len,
                       linebases, linewidth);
         return TDT_E_ARG;
     }
     TDT_HIP(hipSetDevice(ctx->device));
-    // floor(b / linebases) = mulhi(b, magic) >> shift for 0 <= b < 2^31 (round-up method, as for the coverage bins)
-    unsigned magic = 0;
-    int shift = -1;
-    if (linebases > 1) {
-        int l = 0;
-        while ((1ll << l) < linebases) l++;
-        const unsigned long long m = ((1ull << (31 + l)) + (unsigned long long)linebases - 1) / (unsigned long long)linebases;
-        if (m > 0xffffffffull) {
-            tdt_set_error("tdt_gc_bins_fasta_device: line length %d has no 32-bit reciprocal", linebases);
-            return TDT_E_UNSUPPORTED;
-        }
-        magic = (unsigned)m;
-        shift = l - 1;   // mulhi already drops 32 bits: (b * m) >> (31 + l) == mulhi(b, m) >> (l - 1)
+    tdt_fasta_map map;
+    if (!tdt_fasta_map_make(linebases, linewidth, &map)) {
+        tdt_set_error("tdt_gc_bins_fasta_device: line length %d has no 32-bit reciprocal", linebases);
+        return TDT_E_UNSUPPORTED;
     }
     const long long nbins = (len + bin_size - 1) / bin_size;
     const unsigned long long n_min = gc_n_min(bin_size, n_cutoff);
@@ -379,7 +365,7 @@ extern "C" int tdt_gc_bins_fasta_device(tdt_ctx *ctx, const uint8_t *d_raw, int6
     const long long cap = (long long)ctx->num_cu * 256;
     if (grid > cap) grid = cap;
     hipLaunchKernelGGL(gc_fasta_bins, dim3((unsigned)grid), dim3(GC_THREADS), lds, ctx->stream, d_raw, (long long)nbytes, (long long)len, bin_size,
-                       (unsigned)linebases, (unsigned)linewidth, magic, shift, tile_bins, max_chunks, nbins,
+                       map, tile_bins, max_chunks, nbins,
                        n_min > 0xffffffffull ? 0xffffffffu : (unsigned)n_min, (signed char *)d_out);
     TDT_CHECK_LAUNCH();
     return TDT_OK;

@@ -24,6 +24,7 @@
 //     per tile, indel_carry_sum turns those counts into offsets, indel_runs<true> writes the kept runs as rows in key order.
 #include "tdt_batch.h"
 #include "tdt_bam_record.h"
+#include "tdt_refseq.h"
 
 #include <vector>
 
@@ -34,6 +35,7 @@ typedef unsigned long long ull;
 #define INDEL_TILE 4096                       // keys of a run-length workgroup: INDEL_BLOCK lanes, INDEL_TILE / INDEL_BLOCK rounds
 #define INDEL_MAX_CONTIGS (1 << 24)
 #define INDEL_P_LIMIT (1ll << 31)
+#define INDEL_NORM_MAX_SHIFT TDT_INDEL_NORM_MAX_SHIFT   // CAP: no event is shifted further left than this (64 word steps)
 #define INDEL_PACK_MAX 22                     // the longest insertion whose bases fit the 44-bit payload, two bits each
 
 static_assert(INDEL_TILE % INDEL_BLOCK == 0 && INDEL_K_TILE % INDEL_BLOCK == 0, "whole rounds");
@@ -44,12 +46,16 @@ enum { SN_RECORDS = 0, SN_ELIGIBLE, SN_MALFORMED, SN_UNANCHORED, SN_TOO_LONG, SN
        SN_DISTINCT, SN_REPORTED, SN_N, SN_PUSH_N = SN_DISTINCT };
 static_assert(SN_N == TDT_INDEL_SN_N, "SN rows");
 // the state words behind the push counters: the OR of the keys and of their complements; the number of keys stored, in a cache line of its own
-enum { ST_OR1 = SN_PUSH_N, ST_NAND1, ST_OR2, ST_NAND2, ST_N = 16, ST_OVERFLOW, ST_WORDS = 32 };
-static_assert(ST_NAND2 < ST_N && ST_N * 8 % 128 == 0, "state layout");
+// (and, words of their own in the counters' line, what the left-normalisation counted: events shifted, shifts that stopped at CAP, events
+// off the reference — the line of ST_N stays the store-slot atomic's alone)
+enum { ST_OR1 = SN_PUSH_N, ST_NAND1, ST_OR2, ST_NAND2, ST_SHIFTED, ST_CAPPED, ST_OFFREF, ST_N = 16, ST_OVERFLOW, ST_WORDS = 32 };
+static_assert(ST_OFFREF < ST_N && ST_N * 8 % 128 == 0, "state layout");
+static_assert(INDEL_NORM_MAX_SHIFT % 16 == 0, "CAP is whole word steps");
 
 struct tdt_indel {
     tdt_ctx *ctx;
     int n_contigs, min_mapq;
+    tdt_refseq *ref;                          // attached by tdt_indel_set_reference (not owned); NULL: keys as the aligner placed them
     ull *k1, *k2;                             // the store: cap entries each
     size_t cap, upper;                        // upper: no more than this many keys are stored (the device knows how many)
     ull *d_state;                             // ST_WORDS
@@ -93,13 +99,75 @@ __device__ __forceinline__ ull indel_ins_key(const uint8_t *__restrict__ raw, ul
     return head | (1ull << 45) | (((h ^ (h >> 44)) & ((1ull << 44) - 1ull)) << 1);
 }
 
+// ---- the left-normalisation (NORM): tiddit_indels.left_normalise on the resident reference
+// How far the event at P = p (n bases; an insertion's bases at query offset q of the sequence at raw[seq ...], its span inside the
+// sequence) moves left: the largest k <= min(CAP, p - 1) with, for every j < k, a_j == b_j and a_j one of A C G T, where
+// a_j = ref[p - j - 1] and b_j = ref[p - j - 1 + n] — but S[n - 1 - j] for an insertion while j < n.  16 bases per step: the window of
+// the 16 bases ending at p - k - 1 against the window n bases to its right (or the read's own nibbles going left), XOR, OR the
+// mask of the non-ACGT nibbles, one count of trailing zeros.  Every window lies inside the contig or its zero guard, and a zero nibble
+// stops the run.
+__device__ __forceinline__ unsigned indel_shift(const uint8_t *__restrict__ store, ull off, unsigned p, unsigned n, bool ins,
+                                                const uint8_t *__restrict__ raw, ull seq, unsigned q) {
+    const unsigned kmax = p - 1u < INDEL_NORM_MAX_SHIFT ? p - 1u : INDEL_NORM_MAX_SHIFT;       // (p >= 1)
+    const ull g0 = off * 2ull + (ull)p;                            // the store nibble of base p
+    unsigned k = 0;
+    if (ins) {
+        const unsigned lim = n < kmax ? n : kmax;
+        while (k < lim) {
+            const unsigned m = lim - k < 16u ? lim - k : 16u;
+            const ull x = tdt_ref_left16(store, g0 - k - 1ull);
+            ull y = 0;
+            for (unsigned t = 0; t < m; t++) {
+                const unsigned at = q + n - 1u - k - t;
+                y |= (ull)((raw[seq + (at >> 1)] >> ((at & 1u) ? 0 : 4)) & 0xfu) << (4u * t);
+            }
+            ull stop = (x ^ y) | tdt_ref_not_acgt(x);
+            if (m < 16u) stop |= ~0ull << (4u * m);
+            const unsigned run = stop ? (unsigned)__builtin_ctzll(stop) >> 2 : 16u;
+            k += run;
+            if (run < m) return k;
+        }
+        if (k < n) return k;                                       // (k == kmax: the bound, not a mismatch, ended it)
+    }
+    while (k < kmax) {
+        const ull x = tdt_ref_left16(store, g0 - k - 1ull), y = tdt_ref_left16(store, g0 - k - 1ull + n);
+        const ull stop = (x ^ y) | tdt_ref_not_acgt(x);
+        const unsigned run = stop ? (unsigned)__builtin_ctzll(stop) >> 2 : 16u;
+        k += run;
+        if (run < 16u) break;
+    }
+    return k < kmax ? k : kmax;
+}
+
+// K2 of that insertion after k > 0 shifts: code i of the rotated allele is ref[p - k + i] for i < k and S[i - k] behind it
+__device__ __forceinline__ ull indel_ins_key_rotated(const uint8_t *__restrict__ raw, ull seq, unsigned q, unsigned len, const uint8_t *__restrict__ store,
+                                                     ull off, unsigned p, unsigned k) {
+    const ull head = (1ull << 63) | ((ull)len << 47);
+    ull h = 0xcbf29ce484222325ull, pack = 0;
+    bool acgt = len <= INDEL_PACK_MAX;
+    for (unsigned i = 0; i < len; i++) {
+        const unsigned at = q + i - k;                             // (used where i >= k)
+        const unsigned b = i < k ? tdt_ref_code(store, off, (long long)p - k + i) : (raw[seq + (at >> 1)] >> ((at & 1u) ? 0 : 4)) & 0xfu;
+        h = (h ^ (ull)b) * 0x100000001b3ull;
+        const unsigned code = b == 1 ? 0u : b == 2 ? 1u : b == 4 ? 2u : 3u;
+        acgt = acgt && (b == 1 || b == 2 || b == 4 || b == 8);
+        if (i < INDEL_PACK_MAX) pack |= (ull)code << (2 * i);
+    }
+    if (acgt) return head | (pack << 1);
+    return head | (1ull << 45) | (((h ^ (h >> 44)) & ((1ull << 44) - 1ull)) << 1);
+}
+
+// NORM false is the kernel of TIDDIT_INDELS alone; NORM true shifts a read's events between the walk and the keying (Rf: the reference)
+template <bool NORM>
 __global__ __launch_bounds__(INDEL_BLOCK) void indel_keys(IndelIn I, int n, ull raw_len, unsigned min_mapq, ull *__restrict__ k1s, ull *__restrict__ k2s,
-                                                          ull cap, ull *__restrict__ st) {
+                                                          ull cap, ull *__restrict__ st, tdt_refview Rf) {
     __shared__ ull s_k1[INDEL_K_TILE * TDT_INDEL_MAX_PER_READ], s_k2[INDEL_K_TILE * TDT_INDEL_MAX_PER_READ];   // the tile's keys, in the order they were made
     __shared__ int s_read[INDEL_BLOCK];
     __shared__ int s_wsum[INDEL_BLOCK / 64], s_wkeys[INDEL_BLOCK / 64];
     __shared__ ull s_cnt[INDEL_BLOCK / 64][SN_PUSH_N + 4];        // per wave: the push counters, then the OR / NAND words
     __shared__ ull s_base;
+    __shared__ ull s_norm[NORM ? INDEL_BLOCK / 64 : 1][3];         // per wave: shifted, capped, off the reference
+    ull nshift = 0, ncap = 0, noff = 0;                            // (this lane's)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const long long lo = (long long)blockIdx.x * INDEL_K_TILE, hi = lo + INDEL_K_TILE < n ? lo + INDEL_K_TILE : n;
     ull cnt[SN_PUSH_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0};             // (records .. noisy, reads_with_events: wave-uniform sums of ballots; the others: this lane's)
@@ -175,6 +243,32 @@ __global__ __launch_bounds__(INDEL_BLOCK) void indel_keys(IndelIn I, int n, ull 
         cnt[SN_NOISY] += (ull)__popcll(__ballot(noisy));
         cnt[SN_READS_WITH_EVENTS] += (ull)__popcll(__ballot(ok && ne > 0));
         if (walked) cnt[SN_UNANCHORED] += un, cnt[SN_TOO_LONG] += tl;
+        // ---- NORM: every event of an ok read moves as far left as the reference lets it (lanes shift by different amounts: each runs
+        // its own short loop; a lane without events does nothing)
+        unsigned eK[TDT_INDEL_MAX_PER_READ] = {0, 0, 0, 0};
+        ull roff = 0;
+        if constexpr (NORM) {
+            if (ok && ne > 0) {
+                const int rlen = tid < Rf.n ? Rf.len[tid] : -1;    // (< 0: the contig is not loaded)
+                if (rlen >= 0) roff = Rf.off[tid];
+#pragma unroll
+                for (int k = 0; k < TDT_INDEL_MAX_PER_READ; k++) {
+                    if ((unsigned)k < ne) {
+                        const unsigned len = eL[k] >> 1;
+                        const bool ins = eL[k] & 1u;
+                        if (ins && (ull)eQ[k] + len > (ull)l_seq) continue;                      // (SEQ *: never shifted, not counted)
+                        if (rlen < 0 || (ull)eP[k] + (ins ? 0ull : (ull)len) > (ull)rlen) {
+                            noff++;
+                            continue;
+                        }
+                        const unsigned ks = indel_shift(Rf.store, roff, eP[k], len, ins, raw, seq, eQ[k]);
+                        eK[k] = ks;
+                        nshift += ks > 0;
+                        ncap += ks == INDEL_NORM_MAX_SHIFT;
+                    }
+                }
+            }
+        }
         // ---- the round's keys behind the tile's earlier ones, in LDS: slots by a prefix sum of the reads' event counts
         const int mine = ok ? (int)ne : 0;
         int incl = mine;
@@ -196,10 +290,11 @@ __global__ __launch_bounds__(INDEL_BLOCK) void indel_keys(IndelIn I, int n, ull 
         for (int k = 0; k < TDT_INDEL_MAX_PER_READ; k++) {
             if (k < mine) {
                 const unsigned len = eL[k] >> 1;
-                const ull k1 = ((ull)(unsigned)tid << 32) | (ull)eP[k];
+                const ull k1 = ((ull)(unsigned)tid << 32) | (ull)(NORM ? eP[k] - eK[k] : eP[k]);
                 ull k2;
                 if (eL[k] & 1u) {
-                    k2 = indel_ins_key(raw, seq, eQ[k], len, l_seq) | rev;
+                    if (NORM && eK[k]) k2 = indel_ins_key_rotated(raw, seq, eQ[k], len, Rf.store, roff, eP[k], eK[k]) | rev;
+                    else k2 = indel_ins_key(raw, seq, eQ[k], len, l_seq) | rev;
                     cnt[SN_INSERTIONS]++;
                 } else {
                     k2 = ((ull)len << 47) | rev;
@@ -221,7 +316,18 @@ __global__ __launch_bounds__(INDEL_BLOCK) void indel_keys(IndelIn I, int n, ull 
         for (int k = 0; k < SN_PUSH_N; k++) s_cnt[wave][k] = cnt[k];
         s_cnt[wave][SN_PUSH_N] = or1, s_cnt[wave][SN_PUSH_N + 1] = nand1, s_cnt[wave][SN_PUSH_N + 2] = or2, s_cnt[wave][SN_PUSH_N + 3] = nand2;
     }
+    if constexpr (NORM) {
+        nshift = tdt_wave_reduce<tdt_sum>(nshift), ncap = tdt_wave_reduce<tdt_sum>(ncap), noff = tdt_wave_reduce<tdt_sum>(noff);
+        if (lane == 0) s_norm[wave][0] = nshift, s_norm[wave][1] = ncap, s_norm[wave][2] = noff;
+    }
     __syncthreads();
+    if constexpr (NORM) {
+        if (t >= 64 && t < 64 + 3) {                               // (a wave the push counters' atomics leave idle)
+            ull v = 0;
+            for (int w = 0; w < INDEL_BLOCK / 64; w++) v += s_norm[w][t - 64];
+            if (v) atomicAdd(&st[ST_SHIFTED + (t - 64)], v);
+        }
+    }
     if (t == 0) s_base = nk ? atomicAdd(&st[ST_N], (ull)nk) : 0ull;        // the workgroup's slots of the store behind ONE atomic
     if (t < SN_PUSH_N + 4) {
         ull v = 0;
@@ -522,8 +628,13 @@ static int indel_launch(tdt_indel *h, const IndelIn &I, size_t n, size_t raw_len
     const size_t room = n * TDT_INDEL_MAX_PER_READ;                // the bound a read's cap gives
     int rc = indel_reserve(h, room);
     if (rc) return rc;
-    hipLaunchKernelGGL(indel_keys, dim3((unsigned)((n + INDEL_K_TILE - 1) / INDEL_K_TILE)), dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n,
-                       (ull)raw_len, (unsigned)h->min_mapq, h->k1, h->k2, (ull)h->cap, h->d_state);
+    const dim3 grid((unsigned)((n + INDEL_K_TILE - 1) / INDEL_K_TILE));
+    if (h->ref)
+        hipLaunchKernelGGL(indel_keys<true>, grid, dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, h->k1, h->k2,
+                           (ull)h->cap, h->d_state, tdt_refview{h->ref->d_store, h->ref->d_off, h->ref->d_len, h->ref->n_contigs});
+    else
+        hipLaunchKernelGGL(indel_keys<false>, grid, dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, h->k1, h->k2,
+                           (ull)h->cap, h->d_state, tdt_refview{nullptr, nullptr, nullptr, 0});
     TDT_CHECK_LAUNCH();
     h->upper += room;
     h->rows_valid = false;
@@ -761,5 +872,31 @@ extern "C" int tdt_indel_reserve_stats(tdt_indel *h, uint64_t *out3) {
         return TDT_E_ARG;
     }
     out3[0] = h->asks, out3[1] = h->grows, out3[2] = h->cap;
+    return TDT_OK;
+}
+
+// The reference the pushes from here on normalise against (tdt_refseq.hip; it must outlive the handle or be detached first, and lie on
+// the handle's device); NULL detaches it: the keys are again what they are without one.  The store and the counters stay as they are.
+extern "C" int tdt_indel_set_reference(tdt_indel *h, tdt_refseq *ref) {
+    if (!h || (ref && ref->ctx->device != h->ctx->device)) {
+        tdt_set_error("tdt_indel_set_reference: bad argument");
+        return TDT_E_ARG;
+    }
+    h->ref = ref;
+    return TDT_OK;
+}
+
+// out3: what the pushes with a reference attached counted since the last reset — events shifted (k > 0), shifts that stopped at
+// INDEL_NORM_MAX_SHIFT, events off the reference (contig not loaded, or the event reaches beyond its end).  The stream is synchronised.
+extern "C" int tdt_indel_norm_stats(tdt_indel *h, uint64_t *out3) {
+    if (!h || !out3) {
+        tdt_set_error("tdt_indel_norm_stats: bad argument");
+        return TDT_E_ARG;
+    }
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    ull state[ST_WORDS];
+    const int rc = indel_stored(h, state);
+    if (rc) return rc;
+    out3[0] = state[ST_SHIFTED], out3[1] = state[ST_CAPPED], out3[2] = state[ST_OFFREF];
     return TDT_OK;
 }

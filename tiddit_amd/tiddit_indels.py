@@ -43,7 +43,22 @@ tab-separated.  ``POS = P``; ``TYPE`` is ``INS`` or ``DEL``; ``SEQ`` the bases (
 the payload (kind 1), ``*`` (kind 2), ``.`` (deletion); ``COV`` is ``"%.2f"`` of the job's own 50-bp coverage bin
 ``coverage_data[chrom][(P - 1) // 50]``, ``.`` when the job holds no bins for that contig (or none that far).
 
-Events are NOT left-normalised against the reference: two reads that place the same indel of a repeat differently give two rows.
+Events are NOT left-normalised against the reference, unless ``TIDDIT_INDELS_NORM=1``: two reads that place the same indel of a repeat
+differently give two rows.
+
+``TIDDIT_INDELS_NORM=1`` (valid only with ``TIDDIT_INDELS``): the reference is loaded into HBM before the scan (refseq.py) and, behind
+step 4 and in front of step 5, every keyed event of an OK read is moved as far LEFT as the reference allows (:func:`left_normalise`).
+With ``p = P``, ``n`` the length and ``CAP = INDEL_NORM_MAX_SHIFT = 1024``:
+  * the contig is not loaded, ``p + n >`` its length (deletion) or ``p >`` its length (insertion): the event keeps its key,
+        ``SN off_reference`` += 1.  An insertion of kind 2 is never shifted and counts nowhere.
+  * ``k = 0``; while ``k < CAP`` and ``p - k >= 2``: ``a = ref[p - k - 1]``; a deletion's ``b = ref[p - k - 1 + n]``; an insertion's ``b`` is the
+        last code of its allele after k shifts, ``S[n - 1 - k]`` for ``k < n`` (``S`` the read's inserted codes) and ``ref[p - k + n - 1]``
+        behind that; ``a == b`` and ``a`` one of A C G T: ``k += 1``, otherwise stop.
+  * ``P' = P - k >= 1``; the insertion's allele becomes ``S_k`` = the first ``n`` codes of ``ref[p - k .. p) ++ S`` and step 5's payload (packed
+        or hashed) is computed from ``S_k``.  ``SN shifted_events`` += 1 when ``k > 0``; ``SN shift_capped`` += 1 when the loop stopped
+        because ``k == CAP`` — the event is keyed at the capped position, so two placements more than ``CAP`` apart can still differ.
+Everything else — eligibility, the bound, malformed / noisy, the cap of four, the eleven counters — is unchanged.  The file's first
+line gains `` left_normalised=1024`` and three ``SN`` rows follow the eleven: ``shifted_events``, ``shift_capped``, ``off_reference``.
 Long-read libraries are out of scope (the cap of 4).  N ranks: refused (``__main__.run_sv``) — merging per-rank rows needs an exchange
 of keys.
 """
@@ -65,6 +80,9 @@ DEFAULT_SUPPORT, DEFAULT_MAPQ = 2, 20
 SN = ("records", "eligible", "malformed", "unanchored", "too_long", "noisy_reads", "reads_with_events", "insertions", "deletions",
       "distinct_events", "reported_events")
 SN_INDEX = {k: i for i, k in enumerate(SN)}
+INDEL_NORM_MAX_SHIFT = 1024          # CAP of left_normalise
+NORM_SN = ("shifted_events", "shift_capped", "off_reference")          # the three counters of TIDDIT_INDELS_NORM, behind the eleven
+NORM_OK, NORM_CAPPED, NORM_OFF = "ok", "capped", "off_reference"
 SIZE = len(SN)
 COLUMNS = "#CHROM\tPOS\tTYPE\tLEN\tSEQ\tSUPPORT\tFWD\tREV\tCOV\n"
 STAGE_SECONDS = {}
@@ -92,6 +110,18 @@ def parse_switch(value):
     return s, q
 
 
+def parse_norm_switch(value, indels):
+    """``TIDDIT_INDELS_NORM`` -> False (unset or empty) or True; ``indels``: what :func:`parse_switch` made of ``TIDDIT_INDELS``.
+    ValueError (its text is the error line) for any other value, and for the switch without its partner"""
+    if value is None or value == "":
+        return False
+    if value != "1":
+        raise ValueError("the switch is 1")
+    if indels is None:
+        raise ValueError("the switch left-normalises the events of TIDDIT_INDELS: TIDDIT_INDELS not set")
+    return True
+
+
 # ------------------------------------------------------------------------------------------- the definition
 def insertion_payload(raw, seq, q, length, l_seq):
     """(kind, payload) of an insertion of ``length`` bases at query offset ``q``; ``seq``: where the record's 4-bit sequence starts in raw"""
@@ -106,13 +136,58 @@ def insertion_payload(raw, seq, q, length, l_seq):
     return 1, (h ^ (h >> 44)) & _M44
 
 
-def events_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq=DEFAULT_MAPQ):
+def payload_of_codes(codes):
+    """(kind, payload) of an insertion whose bases are the 4-bit ``codes`` (step 5's kinds 0 and 1)"""
+    if len(codes) <= PACK_MAX and all(b in _CODE for b in codes):
+        return 0, sum(_CODE[b] << (2 * i) for i, b in enumerate(codes))
+    h = _FNV
+    for b in codes:
+        h = ((h ^ b) * _PRIME) & _M64
+    return 1, (h ^ (h >> 44)) & _M44
+
+
+def left_normalise(ref, tid, P, length, is_ins, ins_codes):
+    """THE DEFINITION of ``TIDDIT_INDELS_NORM``, one keyed event -> (P', ins_codes', k, status).  ``ref``: an object with ``length(tid)``
+    (negative: the contig is not loaded) and ``code(tid, i)`` (the 4-bit code of base i); ``P``, ``length``: the event's; ``ins_codes``:
+    an insertion's bases as 4-bit codes, None for a deletion and for an insertion of kind 2 (which is never shifted).  ``k`` is the
+    shift distance, ``P' = P - k``, ``ins_codes'`` the rotated allele; ``status`` is NORM_OFF (the event keeps its key), NORM_CAPPED
+    (the loop stopped because ``k == INDEL_NORM_MAX_SHIFT``) or NORM_OK."""
+    p, n = P, length
+    if is_ins and ins_codes is None:
+        return P, None, 0, NORM_OK
+    L = ref.length(tid)
+    if L < 0 or (p > L if is_ins else p + n > L):
+        return P, ins_codes, 0, NORM_OFF
+    k = 0
+    while k < INDEL_NORM_MAX_SHIFT and p - k >= 2:
+        a = ref.code(tid, p - k - 1)
+        if is_ins:
+            b = ins_codes[n - 1 - k] if k < n else ref.code(tid, p - k + n - 1)
+        else:
+            b = ref.code(tid, p - k - 1 + n)
+        if a == b and a in _CODE:
+            k += 1
+        else:
+            break
+    if is_ins and k:
+        ins_codes = ([ref.code(tid, i) for i in range(p - k, p)] + list(ins_codes))[:n]
+    return P - k, ins_codes, k, NORM_CAPPED if k == INDEL_NORM_MAX_SHIFT else NORM_OK
+
+
+def events_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq=DEFAULT_MAPQ, ref=None):
     """THE DEFINITION, one read -> (kind, keys, unanchored, too_long): ``keys`` the read's [(K1, K2)] when kind is OK, else [];
     the two counts are what the read adds to ``SN unanchored`` / ``SN too_long`` (0 for a malformed record).  ``raw``: the batch's record
-    bytes (bytes-like), the other arguments the read's entries of the batch's columns."""
+    bytes (bytes-like), the other arguments the read's entries of the batch's columns.  With ``ref`` (see :func:`left_normalise`) every
+    event of an OK read is left-normalised before its keys are made, and a fifth value follows: what the read adds to
+    (``shifted_events``, ``shift_capped``, ``off_reference``)."""
+    r = _events_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq, ref)
+    return r if ref is not None else r[:4]
+
+
+def _events_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq, ref):
     if flag & 0xF04 or tid < 0 or mapq < min_mapq:
-        return NOT_ELIGIBLE, [], 0, 0
-    bad = (MALFORMED, [], 0, 0)
+        return NOT_ELIGIBLE, [], 0, 0, (0, 0, 0)
+    bad = (MALFORMED, [], 0, 0, (0, 0, 0))
     raw_len = len(raw)
     if tid >= INDEL_MAX_CONTIGS or pos < 0 or rec_off + 36 > raw_len:
         return bad
@@ -146,20 +221,30 @@ def events_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq=DEFAULT_MAPQ):
         if op in (0, 1, 4, 7, 8):
             q += ln
     if len(events) > INDEL_MAX_PER_READ:
-        return NOISY, [], un, tl
+        return NOISY, [], un, tl, (0, 0, 0)
     rev = (flag >> 4) & 1
     keys = []
+    norm = [0, 0, 0]
+    seq = cig + 4 * n_cig
     for P, ln, ins, q in events:
-        kind, payload = insertion_payload(raw, cig + 4 * n_cig, q, ln, L) if ins else (0, 0)
+        if ref is None:
+            kind, payload = insertion_payload(raw, seq, q, ln, L) if ins else (0, 0)
+        else:
+            codes = [(raw[seq + (k >> 1)] >> (0 if k & 1 else 4)) & 0xf for k in range(q, q + ln)] if ins and q + ln <= L else None
+            P, codes, k, status = left_normalise(ref, tid, P, ln, ins, codes)
+            norm[0] += k > 0
+            norm[1] += status == NORM_CAPPED
+            norm[2] += status == NORM_OFF
+            kind, payload = (0, 0) if not ins else (2, 0) if codes is None else payload_of_codes(codes)
         keys.append((tid << 32 | P, int(ins) << 63 | ln << 47 | kind << 45 | payload << 1 | rev))
-    return OK, keys, un, tl
+    return OK, keys, un, tl, tuple(norm)
 
 
 def _raw_of(b):
     return b.raw if isinstance(b.raw, (bytes, bytearray)) else memoryview(numpy.ascontiguousarray(b.raw, dtype=numpy.uint8))
 
 
-def _count(sn, kind, keys, un, tl):
+def _count(sn, kind, keys, un, tl, norm=None):
     add = lambda k, n: sn.__setitem__(k, sn.get(k, 0) + n) if n else None
     add("records", 1)
     if kind == NOT_ELIGIBLE:
@@ -172,14 +257,17 @@ def _count(sn, kind, keys, un, tl):
     add("reads_with_events", int(bool(keys)))
     add("insertions", sum(1 for _, k2 in keys if k2 >> 63))
     add("deletions", sum(1 for _, k2 in keys if not k2 >> 63))
+    for name, v in zip(NORM_SN, norm or ()):
+        add(name, v)
 
 
-def keys_of_batch_by_read(b, keys, sn, min_mapq=DEFAULT_MAPQ):
-    """the definition over one batch, read by read: appends (K1, K2) to ``keys`` and adds to the push counters ``sn`` (a dict)"""
+def keys_of_batch_by_read(b, keys, sn, min_mapq=DEFAULT_MAPQ, ref=None):
+    """the definition over one batch, read by read: appends (K1, K2) to ``keys`` and adds to the push counters ``sn`` (a dict; with
+    ``ref`` also to the three of ``NORM_SN``)"""
     raw = _raw_of(b)
     for i in range(len(b.tid)):
-        kind, ks, un, tl = events_of_read(int(b.flag[i]), int(b.tid[i]), int(b.pos[i]), int(b.mapq[i]), int(b.rec_off[i]), raw, min_mapq)
-        _count(sn, kind, ks, un, tl)
+        kind, ks, un, tl, *norm = events_of_read(int(b.flag[i]), int(b.tid[i]), int(b.pos[i]), int(b.mapq[i]), int(b.rec_off[i]), raw, min_mapq, ref)
+        _count(sn, kind, ks, un, tl, *norm)
         keys.extend(ks)
 
 
@@ -188,7 +276,8 @@ def summarise(keys, sn=None, min_support=DEFAULT_SUPPORT):
     (uint64[SIZE], rows): rows = [(K1, K2 with bit 0 clear, SUPPORT, REV)] of the sets with SUPPORT >= min_support, ascending"""
     c = numpy.zeros(SIZE, dtype=numpy.uint64)
     for k, v in (sn or {}).items():
-        c[SN_INDEX[k]] = v
+        if k not in NORM_SN:                                    # (those three are not among the eleven: norm_counts)
+            c[SN_INDEX[k]] = v
     sets = {}
     for k1, k2 in keys:
         s = sets.setdefault((k1, k2 >> 1), [0, 0])
@@ -201,10 +290,11 @@ def summarise(keys, sn=None, min_support=DEFAULT_SUPPORT):
 
 
 # ------------------------------------------------------------------------------------------- the same rules on whole columns
-def keys_of_batch(b, sn, min_mapq=DEFAULT_MAPQ):
+def keys_of_batch(b, sn, min_mapq=DEFAULT_MAPQ, ref=None):
     """The definition over one batch for files too large for :func:`events_of_read`'s loop, to which tests/test_indel_refs_cpu.py pins it
     on every aimed case: the filters, the record bound and a search for ``I`` / ``D`` / bad op codes run on whole columns (numpy); only
-    the reads that HAVE such an operation go through :func:`events_of_read`.  Adds to the push counters ``sn`` -> [(K1, K2)]."""
+    the reads that HAVE such an operation go through :func:`events_of_read` (with ``ref``: left-normalised, and ``sn`` also gets the three
+    counters of ``NORM_SN``).  Adds to the push counters ``sn`` -> [(K1, K2)]."""
     f, tid, pos, mq = (numpy.asarray(getattr(b, k)).astype(numpy.int64) for k in ("flag", "tid", "pos", "mapq"))
     ro = numpy.asarray(b.rec_off).astype(numpy.int64)
     raw = numpy.frombuffer(b.raw, dtype=numpy.uint8) if isinstance(b.raw, (bytes, bytearray)) else numpy.ascontiguousarray(b.raw, dtype=numpy.uint8)
@@ -230,10 +320,10 @@ def keys_of_batch(b, sn, min_mapq=DEFAULT_MAPQ):
     keys = []
     mem = _raw_of(b)
     for k in need[ok & look].tolist():
-        kind, ks, un, tl = events_of_read(int(f[k]), int(tid[k]), int(pos[k]), int(mq[k]), int(ro[k]), mem, min_mapq)
+        kind, ks, un, tl, *norm = events_of_read(int(f[k]), int(tid[k]), int(pos[k]), int(mq[k]), int(ro[k]), mem, min_mapq, ref)
         c = {}
-        _count(c, kind, ks, un, tl)
-        for name in SN[2:9]:
+        _count(c, kind, ks, un, tl, *norm)
+        for name in SN[2:9] + NORM_SN:
             add(name, c.get(name, 0))
         keys.extend(ks)
     return keys
@@ -251,6 +341,19 @@ class IndelCounter:
         self.handle = h
         self.min_mapq = int(min_mapq)
         self._n_rows = 0
+        self.reference = None
+
+    def set_reference(self, ref):
+        """attach a resident reference (refseq.RefSeq; kept alive by this object) — the pushes from here on left-normalise every event
+        against it (``TIDDIT_INDELS_NORM``) — or detach it with None"""
+        _native.check(self.ctx.lib.tdt_indel_set_reference(self.handle, ref.handle if ref is not None else None))
+        self.reference = ref
+
+    def norm_stats(self):
+        """-> uint64[3]: ``NORM_SN`` — events shifted, shifts that stopped at the cap, events off the reference — since the last reset"""
+        out = numpy.zeros(3, dtype=numpy.uint64)
+        _native.check(self.ctx.lib.tdt_indel_norm_stats(self.handle, _native.ptr(out)))
+        return out
 
     def push_device_batch(self, b):
         """one DeviceBatch: enqueued on the reader's stream; nothing is waited for unless the reserve must ask or grow (call before the
@@ -308,6 +411,7 @@ class IndelCounter:
         if getattr(self, "handle", None):
             self.ctx.lib.tdt_indel_destroy(self.handle)
             self.handle = None
+            self.reference = None                               # (only now: the handle's last kernel is done)
 
     def __del__(self):
         try:
@@ -327,13 +431,16 @@ def seq_text(k2):
     return "#%011x" % payload if kind == 1 else "*"
 
 
-def write_file(path, counts, rows, names, coverage_data, min_support, min_mapq):
-    """``{o}.indels.tab`` (see the module docstring); rows: (K1[], K2[], SUPPORT[], REV[]) or a list of such tuples"""
+def write_file(path, counts, rows, names, coverage_data, min_support, min_mapq, norm=None):
+    """``{o}.indels.tab`` (see the module docstring); rows: (K1[], K2[], SUPPORT[], REV[]) or a list of such tuples; ``norm``: the three
+    counters of ``NORM_SN`` when the events were left-normalised, else None"""
     if isinstance(rows, tuple):
         rows = list(zip(*(numpy.asarray(r).tolist() for r in rows)))
     c = [int(v) for v in numpy.asarray(counts).tolist()]
-    out = ["# tiddit_amd indels v1 min_support=%d min_mapq=%d\n" % (min_support, min_mapq)]
+    out = ["# tiddit_amd indels v1 min_support=%d min_mapq=%d%s\n" % (min_support, min_mapq, " left_normalised=%d" % INDEL_NORM_MAX_SHIFT if norm is not None else "")]
     out += ["SN\t%s\t%d\n" % (k, c[i]) for i, k in enumerate(SN)]
+    if norm is not None:
+        out += ["SN\t%s\t%d\n" % (k, int(v)) for k, v in zip(NORM_SN, norm)]
     out.append(COLUMNS)
     for k1, k2, sup, rev in rows:
         tid, P = k1 >> 32, k1 & 0xffffffff
@@ -359,6 +466,7 @@ def main(counter, prefix, coverage_data, names, S):
     t = time.time()
     counts = counter.finish(S)
     rows = counter.rows()
+    norm = counter.norm_stats() if counter.reference is not None else None
     ms = counter.timing()
     asks, grows, cap = counter.reserve_stats()
     min_mapq = counter.min_mapq
@@ -368,7 +476,10 @@ def main(counter, prefix, coverage_data, names, S):
         STAGE_SECONDS["  " + k + " (device time)"] = v * 1e-3
     STAGE_NOTES.update({"indel store: reserves that asked the device": asks, "indel store: growths": grows, "indel store: capacity (keys)": cap})
     t = time.time()
-    write_file(prefix + ".indels.tab", counts, rows, names, coverage_data, S, min_mapq)
+    write_file(prefix + ".indels.tab", counts, rows, names, coverage_data, S, min_mapq, norm)
     STAGE_SECONDS["indel table text (host)"] = time.time() - t
     print(summary_line(counts))
+    if norm is not None:
+        print("indels, left-normalised: {} events shifted, {} stopped at the cap of {} bases, {} off the reference".format(
+            int(norm[0]), int(norm[1]), INDEL_NORM_MAX_SHIFT, int(norm[2])))
     return counts

@@ -387,6 +387,9 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         #  file's bound; capped at 2^26 keys = 1 GB, behind which a reserve asks the device for the real count every few batches)
         indels = tiddit_indels.IndelCounter(len(names), INDELS[1], capacity=min(max(os.path.getsize(bam_file_name) // 16, 1 << 16), 1 << 26),
                                             ctx=getattr(reader, "ctx", None))
+        if INDEL_REFERENCE is not None:
+            # TIDDIT_INDELS_NORM: the same launch, its events left-normalised against the resident reference
+            indels.set_reference(INDEL_REFERENCE)
         T["indel keys (push)"] = 0.0
     tables = data = splits = clips = None
     if isinstance(reader, DeviceBamReader):
@@ -643,6 +646,7 @@ QC_COUNTER = None           # that counter after the last scan that had QC set (
 DUPS = None                 # True: the scan also stores a duplicate key per fragment and pair (tiddit_dup.DupCounter), one launch per batch
 DUP_COUNTER = None          # that counter after the last scan that had DUPS set (the caller runs its finish and closes it), else None
 INDELS = None               # (min_support, min_mapq): the scan also stores a key per small indel of the reads' CIGARs (tiddit_indels.IndelCounter), one launch per batch
+INDEL_REFERENCE = None      # a refseq.RefSeq: the indel counter of the scan left-normalises its events against it (TIDDIT_INDELS_NORM)
 INDEL_COUNTER = None        # that counter after the last scan that had INDELS set (the caller runs its finish and closes it), else None
 KEEP_EVIDENCE = False       # the scan packs every placed record into an evidence store for the variant stage (tiddit_variant.LIVE_STORE)
 AFTER_SCAN = []             # callables main() invokes once the file has been scanned, before the tables are written (host-only work from there on)
