@@ -1,0 +1,517 @@
+"""One small file with something in it for EVERY consumer of the ``--sv`` scan, and every consumer's result on it from the definitions.
+
+The scan decodes each batch once into HBM and up to eight consumers launch on the same columns and record bytes — the 50-bp histogram,
+the coverage track, the evidence store, the allele counters, the QC tables, the duplicate key store, the indel key store (with or without
+left-normalisation), the signal predicates and gather.  Every one of them has an aimed case module of its own; this module is what they
+are run on TOGETHER: :func:`generate` writes a coordinate-sorted BAM, its reference FASTA and an allele sites VCF into a directory,
+everything derived from ``SEED`` (no golden file), and :func:`expected` gives every consumer's result from its definition over the host
+reader's batches — never from a device result.
+
+The bulk of the pairs is ``synth_bam.write_wgs_sv_bam`` (6x, 100-bp reads, 20 events per Mb: discordant pairs, split reads, clips, a tail
+of unplaced reads) cut from a reference made here.  That bulk holds no insertion, deletions of support 1 only and no ``MC`` tag, so the
+generator plants, on a grid of ``GRID`` bases over every contig of ``MIN_CONTIG`` or more (and on the last, small contig):
+
+  * indel events carried by 3-4 reads on both strands: plain deletions and insertions, insertions longer than 22 bases (the hashed
+    payload), a deletion or an insertion of one unit of a homopolymer / dinucleotide repeat of the reference that every read places at
+    another unit (one row with the reference attached, one per placement without), reads with five events (noisy) and leading
+    insertions (unanchored);
+  * duplicate sets of 2 ... 6 members, fragments and pairs in turn, forward and reverse, their members clipped differently (one
+    unclipped 5' end from several ``pos``); the pairs carry ``MC``; and a few reverse fragment sets with a member that reaches its end
+    over a 50 000-base ``N`` skip, thousands of records — several spans — before the others;
+  * three sites per grid point, every third of them heterozygous: about half of the bulk reads over it get the alternative base;
+  * a clipped read, a split read (``SA``) or a pair with its mate on another contig.
+
+Every bulk pair that is a proper pair of two ``100M`` reads also gets ``MC:Z:100M``."""
+import os
+import struct
+
+import numpy as np
+
+SEED = 20261
+READ_LEN, DEPTH, SV_PER_MB, TOTAL_MB = 100, 6, 20, 1.0
+GRID, GRID_FIRST = 2000, 1000
+MIN_Q, MAX_INS, MIN_CONTIG, MIN_ANCHOR, MIN_CLIP = 5, 700, 10000, 60, 25          # the scan's parameters (tiddit --sv's defaults; max_ins: the bulk's insert + 7.5 sd)
+INDEL_Q, INDEL_SUPPORTS = 20, (1, 2, 3)
+MIN_BQ = 13
+TRACK = (100, 20)                  # the coverage track's bin size and MAPQ cut
+OTHER_TRACK_BIN = 250              # a carry made for this bin size is of no use to a scan that writes TRACK
+FAR_SKIP = 50000                   # the N skip of the far member of a reverse fragment set
+NAMES = ("all.bam", "all.fa", "sites.vcf")
+_M, _I, _D, _N, _S = 0, 1, 2, 3, 4
+
+
+def contigs():
+    from tiddit_amd import synth_bam
+    return synth_bam.wgs_contigs(TOTAL_MB)
+
+
+def paths(directory):
+    return tuple(os.path.join(directory, n) for n in NAMES)
+
+
+# ------------------------------------------------------------------------------------------- the reference
+def grid_points(table=None):
+    """[(k, tid, g)]: the planted groups, numbered over the whole file"""
+    out = []
+    for tid, (_, L) in enumerate(table or contigs()):
+        if L < MIN_CONTIG:
+            continue
+        for g in range(GRID_FIRST, L - 700, GRID):
+            out.append((len(out), tid, g))
+    return out
+
+
+def repeat_of(k):
+    """the repeat planted at g + 200 of group k: (unit, copies)"""
+    return (("A", "C", "G", "T")[k // 2 % 4], 16) if k % 2 == 0 else (("CA", "GT", "AG", "TC")[k // 2 % 4], 8)
+
+
+def site_positions(g):
+    return (g + 300, g + 900, g + 1500)
+
+
+def reference():
+    """-> ({name: uint8 ASCII}, sites [(tid, pos0, ref, alt, heterozygous)]).  ``synth.gen_sequence`` per contig (N runs, lower case, IUPAC
+    codes); around every grid point 500 clean upper-case bases with the group's repeat in them; every site's base one of ACGT."""
+    from tiddit_amd import synth
+    table = contigs()
+    rng = np.random.default_rng([SEED, 1])
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    seqs = {name: synth.gen_sequence(L, seed=SEED + 100 + i).copy() for i, (name, L) in enumerate(table)}
+    sites = []
+    for k, tid, g in grid_points(table):
+        s = seqs[table[tid][0]]
+        s[g - 50:g + 450] = acgt[rng.integers(0, 4, 500)]
+        unit, copies = repeat_of(k)
+        rep = np.frombuffer((unit * copies).encode(), dtype=np.uint8)
+        s[g + 200:g + 200 + len(rep)] = rep
+        for j, p in enumerate(site_positions(g)):
+            if p >= len(s):
+                continue
+            ref = int(rng.integers(0, 4))
+            s[p] = acgt[ref]
+            het = (3 * k + j) % 3 == 0
+            sites.append((tid, p, "ACGT"[ref], "ACGT"[(ref + 1 + int(rng.integers(0, 3))) % 4], het))
+    small = len(table) - 1                                           # the last contig, below MIN_CONTIG: a few planted reads, two sites
+    s = seqs[table[small][0]]
+    s[300:900] = acgt[rng.integers(0, 4, 600)]
+    for p in (450, 650):
+        ref = int(rng.integers(0, 4))
+        s[p] = acgt[ref]
+        sites.append((small, p, "ACGT"[ref], "ACGT"[(ref + 1) % 4], False))
+    return seqs, sites
+
+
+def host_reference(seqs=None):
+    """the reference as the left-normalisation's definition reads it (refseq.HostReference)"""
+    from tiddit_amd import refseq
+    seqs = seqs if seqs is not None else reference()[0]
+    return refseq.HostReference({t: refseq.codes_of_bases(seqs[name]) for t, (name, _) in enumerate(contigs())})
+
+
+def _write_fasta(path, table, seqs, width=60):
+    with open(path, "wb") as f:
+        for name, L in table:
+            s = seqs[name]
+            f.write((">%s\n" % name).encode())
+            for o in range(0, L, width):
+                f.write(s[o:o + width].tobytes() + b"\n")
+
+
+def _write_sites(path, table, sites):
+    with open(path, "w") as f:
+        f.write("##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
+        for tid, p, ref, alt, _ in sites:
+            f.write("%s\t%d\t.\t%s\t%s\t.\t.\t.\n" % (table[tid][0], p + 1, ref, alt))
+
+
+# ------------------------------------------------------------------------------------------- the planted records
+class _Planter:
+    def __init__(self, table, seqs):
+        self.table, self.seqs = table, seqs
+        self.rng = np.random.default_rng([SEED, 2])
+        self.recs = []                                  # (tid, pos, record bytes)
+        self.n = 0
+        self.info = {"repeat_events": 0, "both_strand_events": 0, "long_insertions": 0, "noisy_reads": 0, "unanchored": 0, "dup_sets": 0, "far_sets": 0,
+                     "clip_reads": 0, "split_reads": 0, "discordant_pairs": 0}
+
+    def bases(self, tid, p, n):
+        return self.seqs[self.table[tid][0]][p:p + n].tobytes().decode().upper()
+
+    def name(self, what):
+        self.n += 1
+        return "%s%d" % (what, self.n)
+
+    def put(self, qname, flag, tid, pos, cigar, seq, mate_tid=-1, mate_pos=-1, tlen=0, tags=(), mapq=60):
+        from tiddit_amd import bamio
+        qual = bytes(self.rng.integers(2, 41, len(seq), dtype=np.uint8).tolist())      # (on both sides of MIN_BQ)
+        self.recs.append((tid, pos, bamio.encode_record(qname, flag, tid, pos, mapq, cigar, mate_tid, mate_pos, tlen, seq, tags, qual)))
+
+    def read(self, tid, pos, cigar, rev, ins="", what="i"):
+        """an unpaired read of the reference at pos with this CIGAR (an insertion's bases: ``ins``, one string per I in order)"""
+        ins = [ins] if isinstance(ins, str) else list(ins)
+        seq, r = [], pos
+        for op, ln in cigar:
+            if op == _M:
+                seq.append(self.bases(tid, r, ln))
+                r += ln
+            elif op in (_D, _N):
+                r += ln
+            elif op == _I:
+                seq.append(ins.pop(0))
+            elif op == _S:
+                seq.append("ACGT"[ln % 4] * ln)
+        self.put(self.name(what), 0x10 if rev else 0, tid, pos, cigar, "".join(seq))
+
+    def pair(self, what, tid, pos, cigar, mate_pos, tid2=None, tags=(), mate_cigar=None, proper=True):
+        """read 1 forward at pos, read 2 reverse at mate_pos (on tid2 when given); both carry MC"""
+        rl = READ_LEN
+        mate_cigar = mate_cigar or [(_M, rl)]
+        cs = lambda cig: "".join("%d%s" % (ln, "MIDNSHP=X"[op]) for op, ln in cig)
+        same = tid2 is None or tid2 == tid
+        tid2 = tid if tid2 is None else tid2
+        tl = mate_pos + rl - pos if same else 0
+        ext = 0x2 if proper and same else 0
+        q = self.name(what)
+        sq = lambda t, p, cig: "".join(self.bases(t, p, ln) if op == _M else "ACGT"[ln % 4] * ln for op, ln in cig)      # (M and S only)
+        self.put(q, 0x1 | 0x40 | 0x20 | ext, tid, pos, cigar, sq(tid, pos, cigar), tid2, mate_pos, tl, tuple(tags) + (("MC", "Z", cs(mate_cigar)),))
+        self.put(q, 0x1 | 0x80 | 0x10 | ext, tid2, mate_pos, mate_cigar, sq(tid2, mate_pos, mate_cigar), tid, pos, -tl, (("MC", "Z", cs(cigar)),))
+
+    # ---- one group
+    def indels(self, k, tid, g):
+        rl, info = READ_LEN, self.info
+        kind = k % 5
+        unit, copies = repeat_of(k)
+        u = len(unit)
+        if kind == 0:                                   # a plain deletion, four reads, two on each strand
+            n = 1 + k % 30
+            for j in range(4):
+                a = 30 + 10 * j
+                self.read(tid, g + 120 - a, [(_M, a), (_D, n), (_M, rl - a)], j % 2)
+            info["both_strand_events"] += 1
+        elif kind in (1, 4):                            # an insertion: up to 22 bases packed, longer ones hashed
+            n = 1 + k % 22 if kind == 1 else 23 + k % 20
+            ins = "".join("ACGT"[int(x)] for x in self.rng.integers(0, 4, n))
+            for j in range(3):
+                a = 25 + 9 * j
+                self.read(tid, g + 120 - a, [(_M, a), (_I, n), (_M, rl - n - a)], j % 2, ins)
+            info["both_strand_events"] += 1
+            info["long_insertions"] += kind == 4
+        else:                                           # one unit of the repeat at g + 200 deleted (2) or inserted (3): every read places it elsewhere
+            for j in range(3 + k % 2):
+                at = g + 200 + 2 * u * j                # (0, 2, 4, 6 units in: inside 16 bases of A, 8 units of CA)
+                a = 40 + 7 * j + 2 * u * j
+                if kind == 2:
+                    self.read(tid, at - a, [(_M, a), (_D, u), (_M, rl - a)], j % 2)
+                else:
+                    self.read(tid, at - a, [(_M, a), (_I, u), (_M, rl - u - a)], j % 2, unit)
+            info["repeat_events"] += 1
+            info["both_strand_events"] += 1
+        if k % 25 == 7:                                 # five events in one read
+            self.read(tid, g + 60, [(_M, 10), (_D, 1)] * 5 + [(_M, 50)], 0, what="n")
+            info["noisy_reads"] += 1
+        if k % 25 == 9:                                 # an insertion in front of the first match, one beside a deletion
+            self.read(tid, g + 60, [(_I, 3), (_M, 97)], 1, "ACG", what="u")
+            self.read(tid, g + 70, [(_M, 40), (_I, 2), (_D, 2), (_M, 58)], 0, "TT", what="u")
+            info["unanchored"] += 2
+
+    def dups(self, k, tid, g):
+        rl = READ_LEN
+        size = 2 + k % 5
+        p = g + 350
+        for j in range(size):
+            c = 3 * (j % 3)
+            if k % 2:                                   # a set of pairs: one unclipped 5' end of read 1, one mate end
+                self.pair("dp", tid, p + c, [(_S, c), (_M, rl - c)] if c else [(_M, rl)], p + 250)
+            elif k % 4 == 0:                            # forward fragments: pos moves with the clip
+                self.read(tid, p + c, [(_S, c), (_M, rl - c)] if c else [(_M, rl)], 0, what="df")
+            else:                                       # reverse fragments: the end moves with the clip
+                self.read(tid, p, [(_M, rl - c), (_S, c)] if c else [(_M, rl)], 1, what="dr")
+        self.info["dup_sets"] += 1
+        if k % 8 == 6 and g + 350 - FAR_SKIP >= 500:
+            # two more members of the reverse set above, from far away: 50 bases, a skip, 50 bases ending where the set's reads end
+            for extra in (0, 10):
+                self.read(tid, p - FAR_SKIP - extra, [(_M, 50), (_N, FAR_SKIP + extra), (_M, 50)], 1, what="dx")
+            self.info["far_sets"] += 1
+
+    def signals(self, k, tid, g, big):
+        rl = READ_LEN
+        if k % 4 == 0:
+            self.pair("sc", tid, g + 380, [(_S, 30), (_M, rl - 30)], g + 680)
+            self.info["clip_reads"] += 1
+        elif k % 4 == 1:
+            t2 = big[(big.index(tid) + 3) % len(big)]
+            sa = "%s,%d,+,60S40M,60,0;" % (self.table[t2][0], 1500 + 13 * k % 4000)
+            self.pair("ss", tid, g + 420, [(_M, 60), (_S, 40)], g + 700, tags=(("SA", "Z", sa), ("NM", "i", 0)))
+            self.info["split_reads"] += 1
+        elif k % 4 == 2:
+            t2 = big[(big.index(tid) + 5) % len(big)]
+            self.pair("sd", tid, g + 400, [(_M, rl)], 1200 + 37 * k % 5000, tid2=t2)
+            self.info["discordant_pairs"] += 1
+
+
+def _plant(table, seqs):
+    P = _Planter(table, seqs)
+    big = [t for t, (_, L) in enumerate(table) if L >= MIN_CONTIG]
+    for k, tid, g in grid_points(table):
+        P.indels(k, tid, g)
+        P.dups(k, tid, g)
+        P.signals(k, tid, g, big)
+    small = len(table) - 1
+    for j in range(3):                                  # the last placed records of the file: an event, a fragment set, reads over two sites
+        P.read(small, 400 + 5 * j, [(_M, 45 - 5 * j), (_D, 4), (_M, 55 + 5 * j)], j % 2)
+    for j in range(2):
+        P.read(small, 600, [(_M, READ_LEN)], 0, what="df")
+    return P.recs, P.info
+
+
+# ------------------------------------------------------------------------------------------- the file
+def generate(directory, threads=4):
+    """write the three files of ``NAMES`` into ``directory`` -> what was planted (a dict of counts, the sites, the record count)"""
+    from tiddit_amd import bamio, synth_bam
+    table = contigs()
+    bam, fa, vcf = paths(directory)
+    seqs, sites = reference()
+    _write_fasta(fa, table, seqs)
+    _write_sites(vcf, table, sites)
+    bulk_path = bam + ".bulk"
+    synth_bam.write_wgs_sv_bam(bulk_path, table, depth=DEPTH, read_len=READ_LEN, seed=SEED, sv_per_mb=SV_PER_MB, threads=threads, ref_seqs=seqs)
+    rd = bamio.BamReader(bulk_path)
+    bulk = list(rd.batches())
+    rd.close()
+    os.remove(bulk_path)
+    raw = np.concatenate([np.asarray(b.raw, dtype=np.uint8) for b in bulk])
+    base = np.cumsum([0] + [len(b.raw) for b in bulk[:-1]])
+    ro = np.concatenate([b.rec_off.astype(np.int64) + o for b, o in zip(bulk, base)])
+    col = lambda k: np.concatenate([getattr(b, k) for b in bulk]).astype(np.int64)
+    u = lambda o, n: sum(raw[ro + o + j].astype(np.int64) << (8 * j) for j in range(n))
+    bs, l_name, n_cig = u(0, 4), u(12, 1), u(16, 2)
+    tid, pos, end, flag, tlen = col("tid"), col("pos"), col("end"), col("flag"), col("tlen")
+    simple = (n_cig == 1) & (col("cigar_first") == (READ_LEN << 4)) & (tid >= 0)
+    # the heterozygous sites: about half of the plain bulk reads over each get the alternative base
+    rng = np.random.default_rng([SEED, 3])
+    code = {"A": 1, "C": 2, "G": 4, "T": 8}
+    for t, s, ref, alt, het in sites:
+        if not het:
+            continue
+        for i in np.flatnonzero(simple & (tid == t) & (pos <= s) & (end > s)).tolist():
+            if rng.random() < 0.5:
+                qi = s - int(pos[i])
+                at = int(ro[i]) + 36 + int(l_name[i]) + 4 + (qi >> 1)
+                raw[at] = (raw[at] & 0xf0) | code[alt] if qi & 1 else (raw[at] & 0x0f) | (code[alt] << 4)
+    # MC on the proper pairs of two plain reads
+    mc = simple & ((flag & 0x3) == 0x3) & ((flag & 0xC) == 0) & (np.abs(tlen) >= READ_LEN)
+    mem = raw.tobytes()
+    tag = b"MCZ%dM\x00" % READ_LEN
+    records, keys = [], []
+    for i in range(len(ro)):
+        o, n = int(ro[i]), int(bs[i])
+        if mc[i]:
+            records.append(struct.pack("<i", n + len(tag)) + mem[o + 4:o + 4 + n] + tag)
+        else:
+            records.append(mem[o:o + 4 + n])
+    keys = [(int(t), int(p)) for t, p in zip(tid.tolist(), pos.tolist())]
+    planted, info = _plant(table, seqs)
+    for t, p, rec in planted:
+        records.append(rec)
+        keys.append((t, p))
+    tk = np.array([t if t >= 0 else 1 << 30 for t, _ in keys], dtype=np.int64)
+    pk = np.array([p for _, p in keys], dtype=np.int64)
+    order = np.lexsort((np.arange(len(keys)), pk, tk))               # (stable: equal positions keep bulk-then-planted order)
+    text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % c for c in table) + "@RG\tID:rg1\tSM:ALL\n"
+    w = bamio.BamWriter(bam, table, text=text)
+    for lo in range(0, len(order), 2048):
+        w._buf += b"".join(records[i] for i in order[lo:lo + 2048].tolist())
+        while len(w._buf) >= 0xff00:
+            w._f.write(bamio._bgzf_block(bytes(w._buf[:0xff00]), w.level))
+            del w._buf[:0xff00]
+    w.close()
+    info.update(n_records=len(records), n_planted=len(planted), sites=sites)
+    return info
+
+
+# ------------------------------------------------------------------------------------------- the definitions, batch by batch
+COLS = ("tid", "pos", "end", "mapq", "flag", "mate_tid", "mate_pos", "tlen", "sa_off")
+
+
+def host_batches(bam, batch_bytes=1 << 18):
+    from tiddit_amd import bamio
+    rd = bamio.BamReader(bam, batch_bytes=batch_bytes)
+    try:
+        return list(rd.batches())
+    finally:
+        rd.close()
+
+
+class _Merged:
+    def __len__(self):
+        return len(self.tid)
+
+
+def merged_batch(batches):
+    """the batches as ONE object with their columns and record bytes (what the definitions take)"""
+    from tiddit_amd import bamio
+    m = _Merged()
+    base = np.cumsum([0] + [len(b.raw) for b in batches[:-1]])
+    m.raw = np.concatenate([np.asarray(b.raw, dtype=np.uint8) for b in batches])
+    for k, _ in bamio._FIELDS:
+        if k == "rec_off":
+            m.rec_off = np.concatenate([b.rec_off + np.uint64(o) for b, o in zip(batches, base)])
+        elif k == "sa_off":
+            m.sa_off = np.concatenate([np.where(b.sa_off >= 0, b.sa_off + int(o), -1) for b, o in zip(batches, base)])
+        else:
+            setattr(m, k, np.concatenate([getattr(b, k) for b in batches]))
+    return m
+
+
+def compressed_offsets(bam):
+    """the file offset of the BGZF block every record starts in, int64[records] (how far apart two records lie in the compressed file)"""
+    data = open(bam, "rb").read()
+    cstart, ustart, o, un = [], [], 0, 0
+    while o < len(data):
+        bsize = struct.unpack_from("<H", data, o + 16)[0] + 1
+        cstart.append(o)
+        ustart.append(un)
+        un += struct.unpack_from("<I", data, o + bsize - 4)[0]
+        o += bsize
+    from tiddit_amd import bamio
+    rd = bamio.BamReader(bam)
+    head = rd.header_bytes
+    batches = list(rd.batches())
+    rd.close()
+    at = merged_batch(batches).rec_off.astype(np.int64) + head
+    return np.array(cstart, dtype=np.int64)[np.searchsorted(np.array(ustart, dtype=np.int64), at, side="right") - 1]
+
+
+def sites_table(directory):
+    from tiddit_amd import tiddit_alleles
+    table = contigs()
+    return tiddit_alleles.read_sites(paths(directory)[2], [n for n, _ in table], [l for _, l in table])
+
+
+def signal_selected(b, min_q=MIN_Q, max_ins=MAX_INS, min_contig=MIN_CONTIG, min_anchor=MIN_ANCHOR, min_clip=MIN_CLIP):
+    """the reads of a host batch the signal predicates select — clip | split | discordant, tiddit_signal.pyx:184-221 on whole columns"""
+    big = np.array([l >= min_contig for _, l in contigs()], dtype=bool)
+    tid, flag = b.tid.astype(np.int64), b.flag.astype(np.int64)
+    ok = np.zeros(len(tid), dtype=bool)
+    ok[tid >= 0] = big[tid[tid >= 0]]
+    primary = ok & ((flag & 0x404) == 0) & ((flag & 0x900) == 0) & (b.mapq >= min_q)
+    same, isize = b.mate_tid == b.tid, np.abs(b.tlen.astype(np.int64))
+    f_op, f_len, l_op, l_len = b.cigar_first & 0xf, b.cigar_first >> 4, b.cigar_last & 0xf, b.cigar_last >> 4
+    has = b.cigar_first != 0xffffffff
+    clip = primary & (isize < max_ins) & same & has & (((f_op == 4) & (f_len > min_clip) & (l_op == 0) & (l_len > min_anchor)) |
+                                                       ((l_op == 4) & (l_len > min_clip) & (f_op == 0) & (f_len > min_anchor)))
+    split = primary & (b.sa_off >= 0)
+    disc = primary & ((flag & 0x8) == 0) & ((flag & 0x1) != 0) & ((isize > max_ins) | ~same)
+    return clip | split | disc
+
+
+def partial(b, sites, ref):
+    """every consumer's definition over ONE host batch -> a dict :func:`combine` adds up"""
+    from tiddit_amd import tiddit_alleles, tiddit_dup, tiddit_indels, tiddit_qc
+    out = {"n": len(b)}
+    sn = {}
+    out["indel_keys"], out["indel_sn"] = tiddit_indels.keys_of_batch(b, sn, INDEL_Q), sn
+    sn = {}
+    out["norm_keys"], out["norm_sn"] = tiddit_indels.keys_of_batch(b, sn, INDEL_Q, ref), sn
+    sn = {}
+    k1, k2, m = tiddit_dup.keys_of_batch(b, sn)
+    out["dup_keys"], out["dup_sn"] = list(zip(k1.tolist(), k2.tolist(), m.tolist())), sn
+    qc = np.zeros(tiddit_qc.SIZE, dtype=np.int64)
+    tiddit_qc.count_batch_columns(qc, b)
+    out["qc"] = qc
+    table, stats = np.zeros((len(sites), 8), dtype=np.int64), [0, 0]
+    tiddit_alleles.count_batch(table, stats, sites.site_pos, sites.site_off, b, MIN_Q, MIN_BQ)
+    out["alleles"], out["allele_stats"] = table, stats
+    out["cols"] = {k: np.array(getattr(b, k)) for k in COLS}
+    return out
+
+
+def _sum_sn(parts, key):
+    sn = {}
+    for p in parts:
+        for k, v in p[key].items():
+            sn[k] = sn.get(k, 0) + v
+    return sn
+
+
+def key_rows(keys):
+    """[(K1, K2, ...)] -> the sorted rows of a multiset, uint64[n, width]"""
+    if not keys:
+        return np.zeros((0, 2), dtype=np.uint64)
+    a = np.array(keys, dtype=np.uint64)
+    return a[np.lexsort(a.T[::-1])]
+
+
+def _indel_summary(keys, sn):
+    from tiddit_amd import tiddit_indels
+    out = {}
+    for S in INDEL_SUPPORTS:
+        counts, rows = tiddit_indels.summarise(keys, sn, S)
+        cols = [np.array([r[c] for r in rows], dtype=dt) for c, dt in enumerate((np.uint64, np.uint64, np.uint32, np.uint32))]
+        out[S] = (counts, cols)
+    return out
+
+
+def combine(parts):
+    """the partial results of a sequence of batches -> every consumer's result:
+    indels / indels_norm: (sorted key rows, {S: (counts, [K1, K2, SUPPORT, REV])}[, norm_stats]); dups: (sorted key rows, counts); qc: uint64[];
+    alleles: (uint32[sites][8], reads_used, malformed); cov / track: {contig: float64 bins}; store: ({tid: (start, end, mate_pos, bits)}, int64 spans)"""
+    import oracle
+    import variant_stage_cases as V
+    from tiddit_amd import tiddit_dup, tiddit_indels
+    table = contigs()
+    res = {"records": sum(p["n"] for p in parts)}
+    keys = [k for p in parts for k in p["indel_keys"]]
+    res["indels"] = (key_rows(keys), _indel_summary(keys, _sum_sn(parts, "indel_sn")))
+    keys, sn = [k for p in parts for k in p["norm_keys"]], _sum_sn(parts, "norm_sn")
+    res["indels_norm"] = (key_rows(keys), _indel_summary(keys, sn), tuple(sn.get(k, 0) for k in tiddit_indels.NORM_SN))
+    keys = [k for p in parts for k in p["dup_keys"]]
+    res["dups"] = (key_rows(keys) if keys else np.zeros((0, 3), dtype=np.uint64), tiddit_dup.summarise(keys, _sum_sn(parts, "dup_sn")))
+    res["qc"] = sum(p["qc"] for p in parts).astype(np.uint64)
+    res["alleles"] = (sum(p["alleles"] for p in parts).astype(np.uint32), sum(p["allele_stats"][0] for p in parts), sum(p["allele_stats"][1] for p in parts))
+    cols = {k: np.concatenate([p["cols"][k] for p in parts]) for k in COLS}
+    res["cov"], res["track"] = {}, {}
+    for t, (name, L) in enumerate(table):
+        m = cols["tid"] == t
+        c = [cols[k][m] for k in ("pos", "end", "mapq", "flag")]
+        if L >= MIN_CONTIG:
+            res["cov"][name] = oracle.coverage_stream(*c, L, 50, MIN_Q)[0]
+        res["track"][name] = oracle.coverage_stream(*c, L, TRACK[0], TRACK[1])[0]
+    rec, spans = V.pack_reference(cols, MIN_Q, MAX_INS, len(table))
+    placed = cols["tid"][cols["tid"] >= 0]
+    res["store"] = ({t: store_fields(rec[placed == t]) for t in range(len(table))}, spans)
+    return res
+
+
+def store_fields(rec):
+    """a contig's packed records, field by field (the pad bytes are nobody's)"""
+    return tuple(np.ascontiguousarray(rec[f]) for f in ("start", "end", "mate_pos", "bits"))
+
+
+CONSUMERS = ("indels", "indels_norm", "dups", "qc", "alleles", "cov", "track", "store")
+
+
+def _eq(a, b):
+    if isinstance(a, dict):
+        return set(a) == set(b) and all(_eq(a[k], b[k]) for k in a)
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_eq(x, y) for x, y in zip(a, b))
+    if isinstance(a, np.ndarray):
+        return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
+    return a == b
+
+
+def differing(a, b):
+    """the consumers whose results differ between two :func:`combine` results"""
+    return [k for k in CONSUMERS if not _eq(a[k], b[k])]
+
+
+def partials(directory, batch_bytes=1 << 18):
+    sites, ref = sites_table(directory), host_reference()
+    return [partial(b, sites, ref) for b in host_batches(paths(directory)[0], batch_bytes)]
+
+
+def expected(directory):
+    """every consumer's result on the generated file, from the definitions over the host reader's 256-KiB batches"""
+    return combine(partials(directory))
