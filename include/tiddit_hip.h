@@ -813,6 +813,52 @@ int tdt_debug_refseq_fill(tdt_refseq *h, int tid, int byte);
 int tdt_indel_set_reference(tdt_indel *h, tdt_refseq *ref);
 int tdt_indel_norm_stats(tdt_indel *h, uint64_t *out3);
 
+/* ---- SNV candidates (TIDDIT_SNVS) ------------------------------------------------------------------------ *
+ * Every position where eligible reads carry a base that differs from the resident reference (csrc/tdt_snv.hip); the definition is
+ * tiddit_amd/tiddit_snvs.py's.  A handle keeps a store of keys in HBM — per keyed event (an M / = / X base of an eligible read whose
+ * 4-bit code and the reference's are both one of A C G T and differ, with a quality of at least min_bq or the absent-quality byte 0xff)
+ * K1 = tid << 32 | P (1-based) and K2 = ref2 << 3 | alt2 << 1 | rev, A C G T = 0 1 2 3 — and TDT_SNV_SN_N uint64 counters:
+ *   [0] records  [1] eligible  [2] malformed  [3] no_sequence  [4] off_reference  [5] aligned_bases  [6] low_quality  [7] noisy_reads
+ *   [8] reads_with_events  [9] mismatches  [10] distinct_events  [11] reported_events
+ * A record is eligible when flag & 0xF04 == 0, tid >= 0 and mapq >= min_mapq; the bytes of the others are never read.  A malformed
+ * record (the record bound of tdt_indel fails, an op code above 8, tid >= 2^24, pos < 0, pos + the CIGAR's reference length above
+ * 2^31 - 1, a CIGAR whose query length differs from l_seq when both are given) adds one to `malformed` and gives nothing else; one
+ * without CIGAR or sequence counts as `no_sequence`; one on a contig that is not loaded or reaching beyond its end as `off_reference`; a
+ * read with more than TDT_SNV_MAX_PER_READ keyed events adds one to `noisy_reads` and gives no key.  Nothing outside raw[0, raw_len) is
+ * ever read.  The reference (tdt_refseq) is given at create, is not owned, must lie on the context's device and outlive the handle.
+ * `capacity` is the store's first size in keys; it grows (1.5 x).  Before each launch room for TDT_SNV_MAX_PER_READ keys per read is
+ * reserved — 128 bytes of store per read of a batch, held as headroom — and a reserve that does not fit first asks the device how many
+ * keys there really are.  tdt_snv_push_device takes the pointer table tdt_ingest_arrays filled (TDT_COL_*), enqueues the launch on the
+ * context's stream and waits for nothing unless the reserve must ask or grow; tdt_snv_push uploads host columns, runs the same kernel
+ * and returns when it is done.  tdt_snv_finish sorts the store (two stable radix sorts and a gather: the finish of tdt_indel_finish),
+ * measures the runs of equal (K1, K2 >> 1) — SUPPORT their size, REV the members with bit 0 set — fills sn_out[TDT_SNV_SN_N] and keeps
+ * the runs with SUPPORT >= min_support as rows in key order; the store is left as it was.  tdt_snv_rows reads those rows out (K1, K2
+ * with bit 0 clear, SUPPORT, REV; *n in: room of the arrays, out: rows; all four arrays NULL: the count alone); tdt_snv_keys the store
+ * (the same convention).  tdt_snv_timing: device milliseconds of the last finish (sort by K2, gather, sort by K1, run lengths and
+ * rows).  tdt_snv_reserve_stats: out3 = how often the reserve asked, how often the store grew, its capacity now.
+ * Refusals: TDT_E_ARG (null pointers, a reference of another device, record offsets that decrease, n >= 2^31, tdt_snv_rows without a
+ * finish since the last push or reset), TDT_E_RANGE (more than 2^24 contigs, min_mapq outside 0 ... 255, min_bq outside 0 ...
+ * TDT_SNV_MAX_BQ, min_support outside 1 ... TDT_SNV_MAX_SUPPORT, too little room in tdt_snv_keys / tdt_snv_rows, 2^30 keys or more at
+ * the finish: the sort's limit); a refused call leaves its outputs untouched.  The read-out calls synchronise the stream.
+ * tdt_snv_sn_size() = TDT_SNV_SN_N. */
+#define TDT_SNV_SN_N 12
+#define TDT_SNV_MAX_PER_READ 8
+#define TDT_SNV_MAX_BQ 93
+#define TDT_SNV_MAX_SUPPORT 1000000
+typedef struct tdt_snv tdt_snv;
+int tdt_snv_create(tdt_ctx *ctx, int n_contigs, int min_mapq, int min_bq, size_t capacity, tdt_refseq *ref, tdt_snv **out);
+int tdt_snv_destroy(tdt_snv *h);
+int tdt_snv_reset(tdt_snv *h);
+int tdt_snv_push_device(tdt_snv *h, const void *const *d_arrays14, size_t n, size_t raw_len);
+int tdt_snv_push(tdt_snv *h, const uint16_t *flag, const int32_t *tid, const int32_t *pos, const uint8_t *mapq, const uint64_t *rec_off,
+                 size_t n, const uint8_t *raw, size_t raw_len);
+int tdt_snv_keys(tdt_snv *h, uint64_t *k1, uint64_t *k2, size_t *n);
+int tdt_snv_finish(tdt_snv *h, uint64_t min_support, uint64_t *sn_out, size_t *n_rows);
+int tdt_snv_rows(tdt_snv *h, uint64_t *k1, uint64_t *k2, uint32_t *support, uint32_t *rev, size_t *n);
+int tdt_snv_timing(tdt_snv *h, double *ms4);
+int tdt_snv_reserve_stats(tdt_snv *h, uint64_t *out3);
+size_t tdt_snv_sn_size(void);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

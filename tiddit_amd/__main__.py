@@ -56,6 +56,15 @@ needs an exchange of keys.
 place differently is one row (tiddit_indels.left_normalise has the definition).  Unset or empty is off; any other value, the switch
 without ``TIDDIT_INDELS``, or a contig of the BAM header that the FASTA lacks or holds at another length ends the job with an error
 before the scan.
+
+``TIDDIT_SNVS=1`` (minimum support 3, minimum MAPQ 20, minimum base quality 20), ``TIDDIT_SNVS=S``, ``S:Q`` or ``S:Q:B``: ``--sv`` also
+writes ``{o}.snvs.tab`` — every position where at least ``S`` eligible reads (MAPQ >= ``Q``) carry the same base of quality >= ``B`` that
+differs from the reference, with its support by strand and the job's own 50-bp coverage bin (tiddit_amd/tiddit_snvs.py has the
+definition and the file's format).  The reference FASTA is packed into HBM before the scan (once, shared with ``TIDDIT_INDELS_NORM``), a
+kernel compares every aligned base of every eligible read with it as the batches go by, and one sort follows the scan.  The file is a
+valid ``TIDDIT_ALLELES`` sites file as it stands.  Unset or empty is off; a value that is none of the four forms, or a contig of the BAM
+header that the FASTA lacks or holds at another length, ends the job with an error before the scan.  One process only, refused on N
+ranks like ``TIDDIT_INDELS``.
 """
 import argparse
 import os
@@ -286,6 +295,13 @@ def run_sv(args, version):
         # (the same)
         print("error, TIDDIT_INDELS_NORM={}: {}".format(os.environ.get("TIDDIT_INDELS_NORM"), e))
         sys.exit(1)
+    try:
+        from . import tiddit_snvs
+        snvs = tiddit_snvs.parse_switch(os.environ.get("TIDDIT_SNVS"))
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_SNVS={}: {}".format(os.environ.get("TIDDIT_SNVS"), e))
+        sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
     if genotype_depth and sites_path is None:
@@ -321,15 +337,18 @@ def run_sv(args, version):
     contig_number = {c: i for i, c in enumerate(contigs)}
     contig_length = {c["SN"]: c["LN"] for c in bam_header["SQ"]}
     prefix = args.o
-    if indels_norm:
-        # TIDDIT_INDELS_NORM: the contigs of the BAM header are matched to the FASTA's by name now — one that is missing or has another
-        # length ends the job before anything is made
+    if indels_norm or snvs is not None:
+        # TIDDIT_INDELS_NORM / TIDDIT_SNVS: the contigs of the BAM header are matched to the FASTA's by name now — one that is missing or
+        # has another length ends the job before anything is made
         from . import refseq
         norm_fasta = FastaFile(args.ref)
         try:
             refseq.check_against_bam(norm_fasta, chromosomes, [contig_length[c] for c in chromosomes])
         except ValueError as e:
-            print("error, TIDDIT_INDELS_NORM=1: {}".format(e))
+            if indels_norm:
+                print("error, TIDDIT_INDELS_NORM=1: {}".format(e))
+            else:
+                print("error, TIDDIT_SNVS={}: {}".format(os.environ.get("TIDDIT_SNVS"), e))
             sys.exit(1)
     allele_sites = None
     if alleles is not None:
@@ -367,6 +386,11 @@ def run_sv(args, version):
     if multi and indels is not None:
         # (the same: an event's support is spread over the shards, and merging per-rank rows needs an exchange of keys)
         print("error, TIDDIT_INDELS is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
+              "keys on another rank")
+        sys.exit(1)
+    if multi and snvs is not None:
+        # (the same: a set of equal keys can straddle the shards)
+        print("error, TIDDIT_SNVS is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
               "keys on another rank")
         sys.exit(1)
     if multi:
@@ -527,15 +551,21 @@ def run_sv(args, version):
     if indels is not None:
         # TIDDIT_INDELS: ... and a key per small indel of the reads' CIGARs, one launch per batch
         tiddit_signal.INDELS = indels
-    if indels_norm:
-        # TIDDIT_INDELS_NORM: the reference goes into HBM before the scan (every contig of the BAM header: read, uploaded, packed to
-        # 4-bit codes) and the scan's key kernel moves every event as far left as it allows
+    if indels_norm or snvs is not None:
+        # TIDDIT_INDELS_NORM / TIDDIT_SNVS: the reference goes into HBM before the scan (every contig of the BAM header: read, uploaded,
+        # packed to 4-bit codes), ONCE: the indel kernel moves every event as far left as it allows, the SNV kernel compares every
+        # aligned base with it, and both hold the same handle
         t_ref = time.time()
         reference, t_read, t_load = refseq.load_for_bam(norm_fasta, chromosomes, [contig_length[c] for c in chromosomes])
-        T["reference into HBM (TIDDIT_INDELS_NORM)"] = time.time() - t_ref
+        T["reference into HBM (%s)" % " + ".join(k for k, on in (("TIDDIT_INDELS_NORM", indels_norm), ("TIDDIT_SNVS", snvs is not None)) if on)] = time.time() - t_ref
         T["  reference: file read (host)"] = t_read
         T["  reference: upload + ref_pack (returns when packed)"] = t_load
-        tiddit_signal.INDEL_REFERENCE = reference
+        if indels_norm:
+            tiddit_signal.INDEL_REFERENCE = reference
+        if snvs is not None:
+            # TIDDIT_SNVS: ... and a key per base that differs from the reference, one launch per batch
+            tiddit_signal.SNVS = snvs
+            tiddit_signal.SNV_REFERENCE = reference
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -553,6 +583,8 @@ def run_sv(args, version):
             tiddit_signal.DUPS = None
             tiddit_signal.INDELS = None
             tiddit_signal.INDEL_REFERENCE = None      # (the counter holds it from here on)
+            tiddit_signal.SNVS = None
+            tiddit_signal.SNV_REFERENCE = None        # (the same)
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:
@@ -595,6 +627,14 @@ def run_sv(args, version):
         T["small indels ({o}.indels.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_indels.STAGE_SECONDS.items()})
         STAGE_NOTES.update(tiddit_indels.STAGE_NOTES)
+    if snvs is not None:
+        # (the same)
+        counter, tiddit_signal.SNV_COUNTER = tiddit_signal.SNV_COUNTER, None
+        t = time.time()
+        tiddit_snvs.main(counter, prefix, coverage_data, chromosomes, snvs[0])
+        T["snv candidates ({o}.snvs.tab)"] = time.time() - t
+        T.update({"  " + k: v for k, v in tiddit_snvs.STAGE_SECONDS.items()})
+        STAGE_NOTES.update(tiddit_snvs.STAGE_NOTES)
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,

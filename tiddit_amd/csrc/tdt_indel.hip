@@ -16,23 +16,19 @@
 //     The host knows only an upper bound of the keys stored (INDEL_MAX_PER_READ per read): room for it is reserved BEFORE the launch,
 //     and a growth first asks the device for the real count (dup_reserve's policy).  The kernel still tests every slot against the
 //     capacity it was given and raises a flag instead of writing.
-//   * tdt_indel_finish — once per job: the LSD sort of tdt_dup_finish (sort (K2, index); gather K1; sort (K1[perm], perm), stable;
-//     gather K2), then the runs of equal (K1, K2 >> 1) in plain launches, none of whose workgroups waits for another: indel_tile_heads
-//     notes each tile's last run head and last FULL-key head (a change of (K1, K2), strand included), indel_carry (one workgroup)
-//     carries both across the tiles, indel_runs<false> measures every run at its END — size = position - last head + 1; the sort puts
-//     rev = 0 first, so REV = position - last full-key head + 1 when the last member has bit 0 set, else 0 — and counts the runs it keeps
-//     per tile, indel_carry_sum turns those counts into offsets, indel_runs<true> writes the kept runs as rows in key order.
-#include "tdt_batch.h"
-#include "tdt_bam_record.h"
-#include "tdt_refseq.h"
-
+//   * tdt_indel_finish — once per job: the two stable sorts, the gathers and the run-length launches of tdt_keystore.h (ks_finish),
+//     which the SNV store (tdt_snv.hip) shares; the store, its reserve and its read-outs are that header's too.
 #include <vector>
+
+#include "tdt_keystore.h"
+#include "tdt_refseq.h"
 
 typedef unsigned long long ull;
 
 #define INDEL_BLOCK 256
 #define INDEL_K_TILE 512                      // reads of an indel_keys workgroup; it stages at most 4 x that many keys in LDS (32 KB)
-#define INDEL_TILE 4096                       // keys of a run-length workgroup: INDEL_BLOCK lanes, INDEL_TILE / INDEL_BLOCK rounds
+#define INDEL_TILE 4096                       // keys of a run-length workgroup (KS_TILE of tdt_keystore.h)
+static_assert(INDEL_TILE == KS_TILE && INDEL_BLOCK == KS_BLOCK, "the run-length tile is the key store's");
 #define INDEL_MAX_CONTIGS (1 << 24)
 #define INDEL_P_LIMIT (1ll << 31)
 #define INDEL_NORM_MAX_SHIFT TDT_INDEL_NORM_MAX_SHIFT   // CAP: no event is shifted further left than this (64 word steps)
@@ -48,7 +44,7 @@ static_assert(SN_N == TDT_INDEL_SN_N, "SN rows");
 // the state words behind the push counters: the OR of the keys and of their complements; the number of keys stored, in a cache line of its own
 // (and, words of their own in the counters' line, what the left-normalisation counted: events shifted, shifts that stopped at CAP, events
 // off the reference — the line of ST_N stays the store-slot atomic's alone)
-enum { ST_OR1 = SN_PUSH_N, ST_NAND1, ST_OR2, ST_NAND2, ST_SHIFTED, ST_CAPPED, ST_OFFREF, ST_N = 16, ST_OVERFLOW, ST_WORDS = 32 };
+enum { ST_OR1 = SN_PUSH_N, ST_NAND1, ST_OR2, ST_NAND2, ST_SHIFTED, ST_CAPPED, ST_OFFREF, ST_N = KS_N, ST_OVERFLOW = KS_OVERFLOW, ST_WORDS = KS_WORDS };
 static_assert(ST_OFFREF < ST_N && ST_N * 8 % 128 == 0, "state layout");
 static_assert(INDEL_NORM_MAX_SHIFT % 16 == 0, "CAP is whole word steps");
 
@@ -56,19 +52,8 @@ struct tdt_indel {
     tdt_ctx *ctx;
     int n_contigs, min_mapq;
     tdt_refseq *ref;                          // attached by tdt_indel_set_reference (not owned); NULL: keys as the aligner placed them
-    ull *k1, *k2;                             // the store: cap entries each
-    size_t cap, upper;                        // upper: no more than this many keys are stored (the device knows how many)
-    ull *d_state;                             // ST_WORDS
+    tdt_keystore S;                           // the keys, the state line (ST_WORDS), the finish's buffers and rows
     tdt_batch_io io;                          // columns + raw bytes of the host entry
-    void *d_work;                             // the finish's buffers (grows)
-    size_t work_cap;
-    ull *r_k1, *r_k2;                         // the rows of the last finish (inside d_work), n_rows of them
-    unsigned *r_sup, *r_rev;
-    size_t n_rows;
-    bool rows_valid;
-    ull asks, grows;                          // how often the reserve asked the device for the real count / made a bigger store
-    hipEvent_t ev[5];
-    double ms[4];
 };
 
 struct IndelIn {
@@ -349,178 +334,11 @@ __global__ __launch_bounds__(INDEL_BLOCK) void indel_keys(IndelIn I, int n, ull 
     }
 }
 
-// ---- the finish
-__global__ __launch_bounds__(INDEL_BLOCK) void indel_iota(unsigned *__restrict__ v, int n) {
-    const int i = blockIdx.x * INDEL_BLOCK + threadIdx.x;
-    if (i < n) v[i] = (unsigned)i;
-}
-
-__global__ __launch_bounds__(INDEL_BLOCK) void indel_gather(ull *__restrict__ dst, const ull *__restrict__ src, const unsigned *__restrict__ perm, int n) {
-    const int i = blockIdx.x * INDEL_BLOCK + threadIdx.x;
-    if (i < n) dst[i] = src[perm[i]];
-}
-
-// inclusive scan over the workgroup's 256 threads, in thread order (Op: tdt_max or tdt_sum; `none` its neutral element);
-// *total = the reduction of all (s: INDEL_BLOCK / 64 words)
-template <class Op> __device__ __forceinline__ int indel_block_scan(int v, int none, int *s, int t, int *total) {
-    const int lane = t & 63, wave = t >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o);
-        if (lane >= o) v = Op::of(v, u);
-    }
-    if (lane == 63) s[wave] = v;
-    __syncthreads();
-    int all = none;
-#pragma unroll
-    for (int w = 0; w < INDEL_BLOCK / 64; w++) {
-        const int c = s[w];
-        if (w < wave) v = Op::of(v, c);
-        all = Op::of(all, c);
-    }
-    __syncthreads();
-    *total = all;
-    return v;
-}
-
-// a run head: the first key, or a key whose (K1, K2 >> 1) differs from the one in front of it; a full head: (K1, K2) differs
-__device__ __forceinline__ bool indel_head(const ull *__restrict__ a, const ull *__restrict__ b, int i) {
-    return i == 0 || a[i] != a[i - 1] || (b[i] >> 1) != (b[i - 1] >> 1);
-}
-__device__ __forceinline__ bool indel_full_head(const ull *__restrict__ a, const ull *__restrict__ b, int i) {
-    return i == 0 || a[i] != a[i - 1] || b[i] != b[i - 1];
-}
-
-// tile_last[tile] = the position of the tile's last run head, tile_last[ntiles + tile] = of its last full head; -1 when it has none
-__global__ __launch_bounds__(INDEL_BLOCK) void indel_tile_heads(const ull *__restrict__ a, const ull *__restrict__ b, int n, int ntiles,
-                                                                int *__restrict__ tile_last) {
-    __shared__ int s[INDEL_BLOCK / 64];
-    const int t = threadIdx.x;
-    const int t0 = blockIdx.x * INDEL_TILE;
-    int best = -1, bestf = -1;
-    for (int r = 0; r < INDEL_TILE / INDEL_BLOCK; r++) {
-        const int i = t0 + r * INDEL_BLOCK + t;
-        if (i < n) {
-            if (indel_head(a, b, i)) best = i;                     // (i grows with r)
-            if (indel_full_head(a, b, i)) bestf = i;
-        }
-    }
-    int all, allf;
-    (void)indel_block_scan<tdt_max>(best, -1, s, t, &all);
-    (void)indel_block_scan<tdt_max>(bestf, -1, s, t, &allf);
-    if (t == 0) tile_last[blockIdx.x] = all, tile_last[ntiles + blockIdx.x] = allf;
-}
-
-// ONE workgroup: both halves of tile_last become running maxima over the tiles
-__global__ __launch_bounds__(INDEL_BLOCK) void indel_carry(int *__restrict__ tile_last, int ntiles) {
-    __shared__ int s[INDEL_BLOCK / 64];
-    const int t = threadIdx.x;
-    for (int half = 0; half < 2; half++) {
-        int *v_ = tile_last + (size_t)half * ntiles;
-        int running = -1;
-        for (int c = 0; c < ntiles; c += INDEL_BLOCK) {            // (uniform)
-            const int k = c + t;
-            int all;
-            int v = indel_block_scan<tdt_max>(k < ntiles ? v_[k] : -1, -1, s, t, &all);
-            v = v > running ? v : running;
-            if (k < ntiles) v_[k] = v;
-            running = all > running ? all : running;
-        }
-    }
-}
-
-// ONE workgroup: tile_kept[k] = the kept runs of the tiles in front of tile k (an exclusive sum; the total is below 2^30)
-__global__ __launch_bounds__(INDEL_BLOCK) void indel_carry_sum(int *__restrict__ tile_kept, int ntiles) {
-    __shared__ int s[INDEL_BLOCK / 64];
-    const int t = threadIdx.x;
-    int running = 0;
-    for (int c = 0; c < ntiles; c += INDEL_BLOCK) {                // (uniform)
-        const int k = c + t;
-        const int mine = k < ntiles ? tile_kept[k] : 0;
-        int all;
-        const int v = indel_block_scan<tdt_sum>(mine, 0, s, t, &all);
-        if (k < ntiles) tile_kept[k] = running + v - mine;
-        running += all;
-    }
-}
-
-// every run measured at its end.  WRITE false: tile_kept[tile] = the runs of the tile with size >= min_support, out[0] += its runs,
-// out[1] += the kept ones.  WRITE true: tile_kept holds the exclusive sums and the kept runs become rows, in key order.
-template <bool WRITE>
-__global__ __launch_bounds__(INDEL_BLOCK) void indel_runs(const ull *__restrict__ a, const ull *__restrict__ b, int n, int ntiles,
-                                                          const int *__restrict__ tile_last, int *__restrict__ tile_kept, unsigned min_support,
-                                                          ull *__restrict__ out, ull *__restrict__ r_k1, ull *__restrict__ r_k2,
-                                                          unsigned *__restrict__ r_sup, unsigned *__restrict__ r_rev) {
-    __shared__ int s[INDEL_BLOCK / 64];
-    __shared__ int s_w[INDEL_BLOCK / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int t0 = blockIdx.x * INDEL_TILE;
-    int running = blockIdx.x ? tile_last[blockIdx.x - 1] : -1, runningf = blockIdx.x ? tile_last[ntiles + blockIdx.x - 1] : -1;
-    int kept = 0, runs = 0;                                        // (uniform over the workgroup)
-    const int row0 = WRITE ? tile_kept[blockIdx.x] : 0;
-    for (int r = 0; r < INDEL_TILE / INDEL_BLOCK; r++) {           // (uniform: every thread takes every round)
-        const int i = t0 + r * INDEL_BLOCK + t;
-        const bool valid = i < n;
-        ull ka = 0, kb = 0;
-        bool head = false, fhead = false, end = false;
-        if (valid) {
-            ka = a[i];
-            kb = b[i];
-            head = indel_head(a, b, i);
-            fhead = indel_full_head(a, b, i);
-            end = i == n - 1 || a[i + 1] != ka || (b[i + 1] >> 1) != (kb >> 1);
-        }
-        int all, allf;
-        int last = indel_block_scan<tdt_max>(head ? i : -1, -1, s, t, &all);
-        int lastf = indel_block_scan<tdt_max>(fhead ? i : -1, -1, s, t, &allf);
-        last = last > running ? last : running;
-        lastf = lastf > runningf ? lastf : runningf;
-        running = all > running ? all : running;
-        runningf = allf > runningf ? allf : runningf;
-        const unsigned size = end ? (unsigned)(i - last + 1) : 0u;
-        const bool keep = end && size >= min_support;
-        const ull m_keep = __ballot(keep), m_end = __ballot(end);
-        const tdt_slots S = tdt_block_slots<INDEL_BLOCK / 64>(m_keep, s_w, lane, wave);
-        if (WRITE && keep) {
-            const size_t row = (size_t)row0 + (size_t)(kept + S.base + tdt_lane_rank(m_keep, lane));       // (< n: a row per run)
-            r_k1[row] = ka;
-            r_k2[row] = kb & ~1ull;
-            r_sup[row] = size;
-            r_rev[row] = (kb & 1ull) ? (unsigned)(i - lastf + 1) : 0u;
-        }
-        kept += S.total;
-        if (!WRITE) {
-            const tdt_slots E = tdt_block_slots<INDEL_BLOCK / 64>(m_end, s, lane, wave);
-            runs += E.total;
-            __syncthreads();                                       // (s is the next round's scan buffer)
-        }
-    }
-    if (!WRITE && t == 0) {
-        tile_kept[blockIdx.x] = kept;
-        if (runs) atomicAdd(&out[0], (ull)runs);
-        if (kept) atomicAdd(&out[1], (ull)kept);
-    }
-}
-
+// ---- the handle: the store, its reserve and the finish are tdt_keystore.h's
 static void indel_free(tdt_indel *h) {
-    if (h->k1) (void)hipFree(h->k1);
-    if (h->k2) (void)hipFree(h->k2);
-    if (h->d_state) (void)hipFree(h->d_state);
+    ks_free(&h->S);
     if (h->io.d) (void)hipFree(h->io.d);
-    if (h->d_work) (void)hipFree(h->d_work);
-    for (int k = 0; k < 5; k++)
-        if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     delete h;
-}
-
-// two device arrays of `cap` store entries; on failure nothing is left allocated
-static hipError_t indel_alloc_store(size_t cap, ull **k1, ull **k2) {
-    *k1 = *k2 = nullptr;
-    if (tdt_dev_malloc((void **)k1, cap * 8) == hipSuccess && tdt_dev_malloc((void **)k2, cap * 8) == hipSuccess) return hipSuccess;
-    if (*k1) (void)hipFree(*k1);
-    if (*k2) (void)hipFree(*k2);
-    *k1 = *k2 = nullptr;
-    return hipErrorOutOfMemory;
 }
 
 extern "C" size_t tdt_indel_sn_size(void) { return TDT_INDEL_SN_N; }
@@ -539,17 +357,10 @@ extern "C" int tdt_indel_create(tdt_ctx *ctx, int n_contigs, int min_mapq, size_
     h->ctx = ctx;
     h->n_contigs = n_contigs;
     h->min_mapq = min_mapq;
-    if (tdt_dev_malloc((void **)&h->d_state, ST_WORDS * 8) != hipSuccess || (capacity && indel_alloc_store(capacity, &h->k1, &h->k2) != hipSuccess)) {
+    const int rc = ks_init(&h->S, ctx, "tdt_indel", ST_OR1, capacity);
+    if (rc) {
         indel_free(h);
-        tdt_set_error("tdt_indel_create: out of device memory (%zu keys)", capacity);
-        return TDT_E_NOMEM;
-    }
-    h->cap = capacity;
-    hipError_t e = hipMemsetAsync(h->d_state, 0, ST_WORDS * 8, ctx->stream);
-    for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipEventCreate(&h->ev[k]);
-    if (e != hipSuccess) {
-        indel_free(h);
-        TDT_HIP(e);
+        return rc;
     }
     *out = h;
     return TDT_OK;
@@ -568,76 +379,23 @@ extern "C" int tdt_indel_reset(tdt_indel *h) {
         tdt_set_error("tdt_indel_reset: bad argument");
         return TDT_E_ARG;
     }
-    TDT_HIP(hipSetDevice(h->ctx->device));
-    TDT_HIP(hipMemsetAsync(h->d_state, 0, ST_WORDS * 8, h->ctx->stream));
-    h->upper = 0;
-    h->n_rows = 0;
-    h->rows_valid = false;
-    return TDT_OK;
-}
-
-// how many keys the store holds (the stream is synchronised)
-static int indel_stored(tdt_indel *h, ull *state) {
-    hipStream_t st = h->ctx->stream;
-    TDT_HIP(hipMemcpyAsync(state, h->d_state, ST_WORDS * 8, hipMemcpyDeviceToHost, st));
-    TDT_HIP(hipStreamSynchronize(st));
-    if (state[ST_OVERFLOW] || state[ST_N] > h->cap) {
-        tdt_set_error("tdt_indel: the key store overflowed (%llu keys, capacity %zu)", state[ST_N], h->cap);
-        return TDT_E_RANGE;
-    }
-    return TDT_OK;
-}
-
-// room for `more` keys behind the (at most) h->upper stored ones, as dup_reserve makes it: a growth first asks the device how many
-// keys there really are; then a bigger store (1.5 x), the keys so far copied over on the device, the old one freed once the copy is done.
-static int indel_reserve(tdt_indel *h, size_t more) {
-    if (h->upper + more <= h->cap) return TDT_OK;
-    ull state[ST_WORDS];
-    int rc = indel_stored(h, state);
-    if (rc) return rc;
-    h->asks++;
-    h->upper = (size_t)state[ST_N];
-    if (h->upper + more <= h->cap) return TDT_OK;
-    size_t want = h->cap + h->cap / 2;
-    if (want < h->upper + more) want = h->upper + more;
-    ull *k1, *k2;
-    if (indel_alloc_store(want, &k1, &k2) != hipSuccess) {
-        tdt_set_error("tdt_indel: out of device memory growing to %zu keys", want);
-        return TDT_E_NOMEM;
-    }
-    hipStream_t st = h->ctx->stream;
-    hipError_t e = hipSuccess;
-    if (h->upper) {
-        e = hipMemcpyAsync(k1, h->k1, h->upper * 8, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(k2, h->k2, h->upper * 8, hipMemcpyDeviceToDevice, st);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipFree(k1), (void)hipFree(k2);
-        TDT_HIP(e);
-    }
-    if (h->k1) (void)hipFree(h->k1);
-    if (h->k2) (void)hipFree(h->k2);
-    h->k1 = k1, h->k2 = k2;
-    h->cap = want;
-    h->grows++;
-    return TDT_OK;
+    return ks_reset(&h->S);
 }
 
 static int indel_launch(tdt_indel *h, const IndelIn &I, size_t n, size_t raw_len) {
     const size_t room = n * TDT_INDEL_MAX_PER_READ;                // the bound a read's cap gives
-    int rc = indel_reserve(h, room);
+    int rc = ks_reserve(&h->S, room);
     if (rc) return rc;
     const dim3 grid((unsigned)((n + INDEL_K_TILE - 1) / INDEL_K_TILE));
     if (h->ref)
-        hipLaunchKernelGGL(indel_keys<true>, grid, dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, h->k1, h->k2,
-                           (ull)h->cap, h->d_state, tdt_refview{h->ref->d_store, h->ref->d_off, h->ref->d_len, h->ref->n_contigs});
+        hipLaunchKernelGGL(indel_keys<true>, grid, dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, h->S.k1, h->S.k2,
+                           (ull)h->S.cap, h->S.d_state, tdt_refview{h->ref->d_store, h->ref->d_off, h->ref->d_len, h->ref->n_contigs});
     else
-        hipLaunchKernelGGL(indel_keys<false>, grid, dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, h->k1, h->k2,
-                           (ull)h->cap, h->d_state, tdt_refview{nullptr, nullptr, nullptr, 0});
+        hipLaunchKernelGGL(indel_keys<false>, grid, dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, h->S.k1, h->S.k2,
+                           (ull)h->S.cap, h->S.d_state, tdt_refview{nullptr, nullptr, nullptr, 0});
     TDT_CHECK_LAUNCH();
-    h->upper += room;
-    h->rows_valid = false;
+    h->S.upper += room;
+    h->S.rows_valid = false;
     return TDT_OK;
 }
 
@@ -674,52 +432,7 @@ extern "C" int tdt_indel_push(tdt_indel *h, const uint16_t *flag, const int32_t 
 
 // The store read out, in the order it lies in HBM.  On entry *n = the room of the two arrays (ignored when both are NULL: the call then
 // only reports the count); on return *n = the keys stored.  Too little room: TDT_E_RANGE, nothing written.
-extern "C" int tdt_indel_keys(tdt_indel *h, uint64_t *k1, uint64_t *k2, size_t *n) {
-    if (!h || !n || ((k1 || k2) && !(k1 && k2))) {
-        tdt_set_error("tdt_indel_keys: bad argument");
-        return TDT_E_ARG;
-    }
-    TDT_HIP(hipSetDevice(h->ctx->device));
-    ull state[ST_WORDS];
-    int rc = indel_stored(h, state);
-    if (rc) return rc;
-    const size_t have = (size_t)state[ST_N];
-    if (k1) {
-        if (*n < have) {
-            tdt_set_error("tdt_indel_keys: room for %zu keys, %zu stored", *n, have);
-            return TDT_E_RANGE;
-        }
-        hipStream_t st = h->ctx->stream;
-        if (have) {
-            TDT_HIP(hipMemcpyAsync(k1, h->k1, have * 8, hipMemcpyDeviceToHost, st));
-            TDT_HIP(hipMemcpyAsync(k2, h->k2, have * 8, hipMemcpyDeviceToHost, st));
-            TDT_HIP(hipStreamSynchronize(st));
-        }
-    }
-    *n = have;
-    return TDT_OK;
-}
-
-struct IndelWork {
-    ull *ka, *kb, *d_out, *r_k1, *r_k2;
-    unsigned *ia, *ib, *r_sup, *r_rev;
-    int *tile_last, *tile_kept;
-    size_t lay(void *base, size_t n, size_t ntiles) {
-        tdt_carver cv(base);
-        ka = cv.take<ull>(n), kb = cv.take<ull>(n), ia = cv.take<unsigned>(n), ib = cv.take<unsigned>(n);
-        r_k1 = cv.take<ull>(n), r_k2 = cv.take<ull>(n), r_sup = cv.take<unsigned>(n), r_rev = cv.take<unsigned>(n);
-        tile_last = cv.take<int>(2 * ntiles), tile_kept = cv.take<int>(ntiles), d_out = cv.take<ull>(2);
-        return cv.size;
-    }
-};
-
-// the sort mask of a key column: every bit from the lowest to the highest one that differs between two stored keys (one run of set
-// bits: at most eight digits, whatever a hashed payload looks like)
-static ull indel_mask(ull differ) {
-    if (!differ) return 0;
-    const int lo = __builtin_ctzll(differ), hi = 63 - __builtin_clzll(differ);
-    return (hi == 63 ? ~0ull : (1ull << (hi + 1)) - 1ull) & ~((1ull << lo) - 1ull);
-}
+extern "C" int tdt_indel_keys(tdt_indel *h, uint64_t *k1, uint64_t *k2, size_t *n) { return ks_keys(h ? &h->S : nullptr, "tdt_indel", k1, k2, n); }
 
 // sn_out: uint64[TDT_INDEL_SN_N], the push counters and the sets of everything pushed so far; *n_rows: the rows tdt_indel_rows will
 // give.  The store is left as it was.
@@ -732,127 +445,24 @@ extern "C" int tdt_indel_finish(tdt_indel *h, uint64_t min_support, uint64_t *sn
         tdt_set_error("tdt_indel_finish: min_support %llu (1 ... %d)", (ull)min_support, TDT_INDEL_MAX_SUPPORT);
         return TDT_E_RANGE;
     }
-    tdt_ctx *ctx = h->ctx;
-    TDT_HIP(hipSetDevice(ctx->device));
-    ull state[ST_WORDS];
-    int rc = indel_stored(h, state);
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    ull state[ST_WORDS], got[2];
+    int rc = ks_stored(&h->S, state);
+    if (rc == TDT_OK) rc = ks_finish(&h->S, state, min_support, got);
     if (rc) return rc;
-    const size_t n_ = (size_t)state[ST_N];
-    if (n_ >= (1ull << 30)) {
-        tdt_set_error("tdt_indel_finish: %zu keys; the sort handles fewer than 2^30", n_);
-        return TDT_E_RANGE;
-    }
     uint64_t res[SN_N] = {};
     for (int k = 0; k < SN_PUSH_N; k++) res[k] = state[k];
-    for (int k = 0; k < 4; k++) h->ms[k] = 0;
-    h->rows_valid = false;
-    h->n_rows = 0;
-    if (n_) {
-        const int n = (int)n_;
-        const size_t ntiles = (n_ + INDEL_TILE - 1) / INDEL_TILE;
-        IndelWork W;
-        const size_t bytes = W.lay(nullptr, n_, ntiles);
-        if (bytes > h->work_cap) {
-            if (h->d_work) TDT_HIP(hipFree(h->d_work));
-            h->d_work = nullptr;
-            h->work_cap = 0;
-            if (tdt_dev_malloc(&h->d_work, bytes) != hipSuccess) {
-                tdt_set_error("tdt_indel_finish: out of device memory (%zu keys)", n_);
-                return TDT_E_NOMEM;
-            }
-            h->work_cap = bytes;
-        }
-        W.lay(h->d_work, n_, ntiles);
-        hipStream_t st = ctx->stream;
-        const unsigned grid = (unsigned)((n_ + INDEL_BLOCK - 1) / INDEL_BLOCK);
-        TDT_HIP(hipMemsetAsync(W.d_out, 0, 2 * 8, st));
-        TDT_HIP(hipMemcpyAsync(W.ka, h->k2, n_ * 8, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(indel_iota, dim3(grid), dim3(INDEL_BLOCK), 0, st, W.ia, n);
-        TDT_CHECK_LAUNCH();
-        // PRECONDITION of tdt_radix_sort_pairs: the key bits outside the mask are equal in ALL keys.  The push kept the OR of the keys
-        // and of their complements: a bit differs exactly when it is set in both, and indel_mask covers every such bit.
-        const ull mask1 = indel_mask(state[ST_OR1] & state[ST_NAND1]), mask2 = indel_mask(state[ST_OR2] & state[ST_NAND2]);
-        ull *k2s, *k1s;
-        unsigned *perm, *perm2;
-        TDT_HIP(hipEventRecord(h->ev[0], st));
-        rc = tdt_radix_sort_pairs(ctx, W.ka, W.ia, W.kb, W.ib, n_, mask2, &k2s, &perm);
-        if (rc) return rc;
-        TDT_HIP(hipEventRecord(h->ev[1], st));
-        ull *free_k = k2s == W.ka ? W.kb : W.ka;                   // (the sorted K2 are not needed again: K2 comes from the store below)
-        unsigned *free_i = perm == W.ia ? W.ib : W.ia;
-        hipLaunchKernelGGL(indel_gather, dim3(grid), dim3(INDEL_BLOCK), 0, st, free_k, (const ull *)h->k1, (const unsigned *)perm, n);
-        TDT_CHECK_LAUNCH();
-        TDT_HIP(hipEventRecord(h->ev[2], st));
-        rc = tdt_radix_sort_pairs(ctx, free_k, perm, k2s, free_i, n_, mask1, &k1s, &perm2);           // (the same precondition, mask1)
-        if (rc) return rc;
-        TDT_HIP(hipEventRecord(h->ev[3], st));
-        ull *k2f = k1s == W.ka ? W.kb : W.ka;
-        const int nt = (int)ntiles;
-        hipLaunchKernelGGL(indel_gather, dim3(grid), dim3(INDEL_BLOCK), 0, st, k2f, (const ull *)h->k2, (const unsigned *)perm2, n);
-        TDT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(indel_tile_heads, dim3((unsigned)ntiles), dim3(INDEL_BLOCK), 0, st, (const ull *)k1s, (const ull *)k2f, n, nt, W.tile_last);
-        TDT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(indel_carry, dim3(1), dim3(INDEL_BLOCK), 0, st, W.tile_last, nt);
-        TDT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(indel_runs<false>, dim3((unsigned)ntiles), dim3(INDEL_BLOCK), 0, st, (const ull *)k1s, (const ull *)k2f, n, nt,
-                           (const int *)W.tile_last, W.tile_kept, (unsigned)min_support, W.d_out, W.r_k1, W.r_k2, W.r_sup, W.r_rev);
-        TDT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(indel_carry_sum, dim3(1), dim3(INDEL_BLOCK), 0, st, W.tile_kept, nt);
-        TDT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(indel_runs<true>, dim3((unsigned)ntiles), dim3(INDEL_BLOCK), 0, st, (const ull *)k1s, (const ull *)k2f, n, nt,
-                           (const int *)W.tile_last, W.tile_kept, (unsigned)min_support, W.d_out, W.r_k1, W.r_k2, W.r_sup, W.r_rev);
-        TDT_CHECK_LAUNCH();
-        TDT_HIP(hipEventRecord(h->ev[4], st));
-        ull got[2] = {0, 0};
-        TDT_HIP(hipMemcpyAsync(got, W.d_out, 2 * 8, hipMemcpyDeviceToHost, st));
-        rc = tdt_ctx_sync(ctx);                                    // (also reports the sort's bounded-spin word)
-        if (rc) return rc;
-        res[SN_DISTINCT] = got[0];
-        res[SN_REPORTED] = got[1];
-        for (int k = 0; k < 4; k++) {
-            float ms = 0;
-            TDT_HIP(hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
-            h->ms[k] = ms;
-        }
-        h->r_k1 = W.r_k1, h->r_k2 = W.r_k2, h->r_sup = W.r_sup, h->r_rev = W.r_rev;
-        h->n_rows = (size_t)got[1];
-    }
-    h->rows_valid = true;
+    res[SN_DISTINCT] = got[0];
+    res[SN_REPORTED] = got[1];
     memcpy(sn_out, res, sizeof res);
-    *n_rows = h->n_rows;
+    *n_rows = h->S.n_rows;
     return TDT_OK;
 }
 
 // The rows of the last finish, ascending by (K1, K2 >> 1): K1, K2 with bit 0 clear, SUPPORT, REV.  *n in: the room of the four arrays
 // (ignored when all four are NULL), out: the rows.  A push or a reset since the finish: TDT_E_ARG.  Too little room: TDT_E_RANGE.
 extern "C" int tdt_indel_rows(tdt_indel *h, uint64_t *k1, uint64_t *k2, uint32_t *support, uint32_t *rev, size_t *n) {
-    const bool any = k1 || k2 || support || rev;
-    if (!h || !n || (any && !(k1 && k2 && support && rev))) {
-        tdt_set_error("tdt_indel_rows: bad argument");
-        return TDT_E_ARG;
-    }
-    if (!h->rows_valid) {
-        tdt_set_error("tdt_indel_rows: no finish since the last push or reset");
-        return TDT_E_ARG;
-    }
-    const size_t have = h->n_rows;
-    if (any) {
-        if (*n < have) {
-            tdt_set_error("tdt_indel_rows: room for %zu rows, %zu kept", *n, have);
-            return TDT_E_RANGE;
-        }
-        if (have) {
-            TDT_HIP(hipSetDevice(h->ctx->device));
-            hipStream_t st = h->ctx->stream;
-            TDT_HIP(hipMemcpyAsync(k1, h->r_k1, have * 8, hipMemcpyDeviceToHost, st));
-            TDT_HIP(hipMemcpyAsync(k2, h->r_k2, have * 8, hipMemcpyDeviceToHost, st));
-            TDT_HIP(hipMemcpyAsync(support, h->r_sup, have * 4, hipMemcpyDeviceToHost, st));
-            TDT_HIP(hipMemcpyAsync(rev, h->r_rev, have * 4, hipMemcpyDeviceToHost, st));
-            TDT_HIP(hipStreamSynchronize(st));
-        }
-    }
-    *n = have;
-    return TDT_OK;
+    return ks_rows(h ? &h->S : nullptr, "tdt_indel", k1, k2, support, rev, n);
 }
 
 // device milliseconds of the last finish: [0] sort by K2, [1] gather of K1, [2] sort by K1, [3] gather of K2 + the run-length launches
@@ -861,7 +471,7 @@ extern "C" int tdt_indel_timing(tdt_indel *h, double *ms4) {
         tdt_set_error("tdt_indel_timing: bad argument");
         return TDT_E_ARG;
     }
-    for (int k = 0; k < 4; k++) ms4[k] = h->ms[k];
+    for (int k = 0; k < 4; k++) ms4[k] = h->S.ms[k];
     return TDT_OK;
 }
 
@@ -871,7 +481,7 @@ extern "C" int tdt_indel_reserve_stats(tdt_indel *h, uint64_t *out3) {
         tdt_set_error("tdt_indel_reserve_stats: bad argument");
         return TDT_E_ARG;
     }
-    out3[0] = h->asks, out3[1] = h->grows, out3[2] = h->cap;
+    out3[0] = h->S.asks, out3[1] = h->S.grows, out3[2] = h->S.cap;
     return TDT_OK;
 }
 
@@ -895,7 +505,7 @@ extern "C" int tdt_indel_norm_stats(tdt_indel *h, uint64_t *out3) {
     }
     TDT_HIP(hipSetDevice(h->ctx->device));
     ull state[ST_WORDS];
-    const int rc = indel_stored(h, state);
+    const int rc = ks_stored(&h->S, state);
     if (rc) return rc;
     out3[0] = state[ST_SHIFTED], out3[1] = state[ST_CAPPED], out3[2] = state[ST_OFFREF];
     return TDT_OK;

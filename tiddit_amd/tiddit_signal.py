@@ -299,12 +299,13 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
 
     ``COV_TRACK = (bin_size, min_q)``: a second histogram over EVERY contig of the header is filled from the same batches (their second
     coverage-record column, written by the ingest kernel in the pass that decodes them) and its bins are left in ``COV_TRACK_BINS``."""
-    global COV_TRACK_BINS, ALLELE_COUNTER, QC_COUNTER, DUP_COUNTER, INDEL_COUNTER
+    global COV_TRACK_BINS, ALLELE_COUNTER, QC_COUNTER, DUP_COUNTER, INDEL_COUNTER, SNV_COUNTER
     COV_TRACK_BINS = None
     ALLELE_COUNTER = None
     QC_COUNTER = None
     DUP_COUNTER = None
     INDEL_COUNTER = None
+    SNV_COUNTER = None
     track = COV_TRACK
     max_ins = int(max_ins)         # the reference's `int max_ins` argument truncates a float percentile (:147,:230; probed with Cython 3.2)
     from . import bamio
@@ -391,6 +392,15 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             # TIDDIT_INDELS_NORM: the same launch, its events left-normalised against the resident reference
             indels.set_reference(INDEL_REFERENCE)
         T["indel keys (push)"] = 0.0
+    snvs = None
+    if SNVS is not None:
+        # TIDDIT_SNVS: a key store in HBM and the resident reference; every batch costs one more launch on the columns and bytes it already holds there
+        from . import tiddit_snvs
+        # (the indel counter's capacity rule; room for 8 keys per read is reserved before each launch, behind which a reserve asks the
+        #  device for the real count)
+        snvs = tiddit_snvs.SnvCounter(len(names), SNV_REFERENCE, SNVS[1], SNVS[2], capacity=min(max(os.path.getsize(bam_file_name) // 16, 1 << 16), 1 << 26),
+                                      ctx=getattr(reader, "ctx", None))
+        T["snv keys (push)"] = 0.0
     tables = data = splits = clips = None
     if isinstance(reader, DeviceBamReader):
         from .sigtab import SignalTables
@@ -463,6 +473,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                     t3b = time.time()
                     T["indel keys (push)"] += t3b - t3
                     t3 = t3b
+                if snvs is not None:                            # (the same, beside the indel push)
+                    snvs.push_device_batch(b)
+                    t3b = time.time()
+                    T["snv keys (push)"] += t3b - t3
+                    t3 = t3b
                 # the per-read chain of worker (:171-221) on the device; only the selected reads come back (fields + raw records)
                 # (once the scan's kernels are enqueued nothing will read the batch's raw bytes again: the next span's inflate is started
                 #  behind them — DeviceBamReader.ahead() — and runs while this thread waits for the selected reads and hands them on)
@@ -499,6 +514,10 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 t1b = time.time()
                 indels.push_host_batch(b)
                 T["indel keys (push)"] += time.time() - t1b
+            if snvs is not None:
+                t1b = time.time()
+                snvs.push_host_batch(b)
+                T["snv keys (push)"] += time.time() - t1b
             tid = b.tid
             flag = b.flag.astype(numpy.int32)
             placed = tid >= 0
@@ -567,6 +586,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             dups.close()
         if indels is not None:
             indels.close()
+        if snvs is not None:
+            snvs.close()
         raise
     finally:
         pool.shutdown(wait=True)                              # (also on an error: no row thread outlives the scan)
@@ -587,11 +608,14 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         dups.ctx.sync()                                         # (the same)
     if indels is not None:
         indels.ctx.sync()                                       # (the same)
+    if snvs is not None:
+        snvs.ctx.sync()                                         # (the same)
     reader.close()
     ALLELE_COUNTER = alleles                                    # (the caller reads the counters and closes it)
     QC_COUNTER = qc                                             # (the same)
     DUP_COUNTER = dups                                          # (the same: the caller runs its finish and closes it)
     INDEL_COUNTER = indels                                      # (the same)
+    SNV_COUNTER = snvs                                          # (the same)
     if store is not None:
         from . import tiddit_variant
         if tiddit_variant.LIVE_STORE is not None:
@@ -647,6 +671,9 @@ DUPS = None                 # True: the scan also stores a duplicate key per fra
 DUP_COUNTER = None          # that counter after the last scan that had DUPS set (the caller runs its finish and closes it), else None
 INDELS = None               # (min_support, min_mapq): the scan also stores a key per small indel of the reads' CIGARs (tiddit_indels.IndelCounter), one launch per batch
 INDEL_REFERENCE = None      # a refseq.RefSeq: the indel counter of the scan left-normalises its events against it (TIDDIT_INDELS_NORM)
+SNVS = None                 # (min_support, min_mapq, min_bq): the scan also stores a key per base that differs from SNV_REFERENCE (tiddit_snvs.SnvCounter), one launch per batch
+SNV_REFERENCE = None        # a refseq.RefSeq: the reference the SNV counter compares with (TIDDIT_SNVS; the same handle as INDEL_REFERENCE when both are set)
+SNV_COUNTER = None          # that counter after the last scan that had SNVS set (the caller runs its finish and closes it), else None
 INDEL_COUNTER = None        # that counter after the last scan that had INDELS set (the caller runs its finish and closes it), else None
 KEEP_EVIDENCE = False       # the scan packs every placed record into an evidence store for the variant stage (tiddit_variant.LIVE_STORE)
 AFTER_SCAN = []             # callables main() invokes once the file has been scanned, before the tables are written (host-only work from there on)
