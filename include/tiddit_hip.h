@@ -859,6 +859,54 @@ int tdt_snv_timing(tdt_snv *h, double *ms4);
 int tdt_snv_reserve_stats(tdt_snv *h, uint64_t *out3);
 size_t tdt_snv_sn_size(void);
 
+/* ---- clipped-read breakpoint sites (TIDDIT_CLIPS) -------------------------------------------------------- *
+ * Every reference position where eligible reads are soft-clipped on one side, with a consensus of the clipped bases beside the
+ * breakpoint (csrc/tdt_clip.hip); the definition is tiddit_amd/tiddit_clips.py's.  A handle keeps a store of keys in HBM — per clip of at
+ * least min_clip bases (the S at CIGAR index 0, or 1 behind an H; the S at the last index, or the last but one in front of an H)
+ * K1 = tid << 32 | P (1-based: the first aligned base for a leading clip, the last for a trailing one) and
+ * K2 = side << 63 | n << 58 | bases << 2 | rev, `bases` the first n <= TDT_CLIP_COLS clipped bases outward from the breakpoint, two bits
+ * each, A C G T = 0 1 2 3, cut at the first other code — and TDT_CLIP_SN_N uint64 counters:
+ *   [0] records  [1] eligible  [2] malformed  [3] no_sequence  [4] no_alignment  [5] short_clips  [6] left_clips  [7] right_clips
+ *   [8] clipped_reads  [9] cut_at_other_base  [10] distinct_sequences  [11] distinct_sites  [12] reported_sites
+ * ([10] ... [12] are the finish's).  Eligible: flag & 0xF04 == 0, tid >= 0, mapq >= min_mapq.  An eligible record is bounded and judged
+ * malformed exactly as tdt_snv does it; one without CIGAR or sequence counts as `no_sequence`, one whose CIGAR has a reference length
+ * of 0 as `no_alignment`.  Nothing outside raw[0, raw_len) is ever read.  `capacity` is the store's first size in keys; it grows
+ * (1.5 x).  Before each launch room for TDT_CLIP_MAX_PER_READ keys per read is reserved, and a reserve that does not fit first asks the
+ * device how many keys there really are.  tdt_clip_push_device takes the pointer table tdt_ingest_arrays filled (TDT_COL_*), enqueues
+ * the launch on the context's stream and waits for nothing unless the reserve must ask or grow; tdt_clip_push uploads host columns, runs
+ * the same kernel and returns when it is done.  tdt_clip_finish sorts the store (the finish of tdt_snv_finish, with a minimum support
+ * of 1: its rows are the distinct sequences (K1, K2 >> 1)), finds the sites — runs of equal (K1, side) — and per site SUPPORT, REV, SEQS
+ * and a vote per column: depth_j = the events with n > j, CLEN = the leading columns with depth_j >= min_support, the consensus base of
+ * a column the one with the most votes (a tie to the smaller code), AGREE / TOTAL the winning votes / the depths summed over the CLEN
+ * columns.  It fills sn_out[TDT_CLIP_SN_N] and keeps the sites with SUPPORT >= min_support as rows in key order; the store is left as it
+ * was.  tdt_clip_rows reads those rows out (K1, side, SUPPORT, REV, SEQS, CLEN, the consensus packed like `bases`, AGREE, TOTAL; *n in:
+ * room of the arrays, out: rows; all nine arrays NULL: the count alone); tdt_clip_keys the store (the same convention).
+ * tdt_clip_timing: device milliseconds of the last finish (sort by K2, gather, sort by K1, run lengths and rows, the site launches).
+ * tdt_clip_reserve_stats: out3 = how often the reserve asked, how often the store grew, its capacity now.
+ * Refusals: TDT_E_ARG (null pointers, record offsets that decrease, n >= 2^31, tdt_clip_rows without a finish since the last push or
+ * reset), TDT_E_RANGE (more than 2^24 contigs, min_mapq outside 0 ... 255, min_clip outside 1 ... TDT_CLIP_MAX_CLIP, min_support outside
+ * 1 ... TDT_CLIP_MAX_SUPPORT, too little room in tdt_clip_keys / tdt_clip_rows, 2^30 keys or more at the finish: the sort's limit); a
+ * refused call leaves its outputs untouched.  The read-out calls synchronise the stream.  tdt_clip_sn_size() = TDT_CLIP_SN_N. */
+#define TDT_CLIP_SN_N 13
+#define TDT_CLIP_MAX_PER_READ 2
+#define TDT_CLIP_COLS 28
+#define TDT_CLIP_MAX_CLIP 65535
+#define TDT_CLIP_MAX_SUPPORT 1000000
+typedef struct tdt_clip tdt_clip;
+int tdt_clip_create(tdt_ctx *ctx, int n_contigs, int min_mapq, int min_clip, size_t capacity, tdt_clip **out);
+int tdt_clip_destroy(tdt_clip *h);
+int tdt_clip_reset(tdt_clip *h);
+int tdt_clip_push_device(tdt_clip *h, const void *const *d_arrays14, size_t n, size_t raw_len);
+int tdt_clip_push(tdt_clip *h, const uint16_t *flag, const int32_t *tid, const int32_t *pos, const uint8_t *mapq, const uint64_t *rec_off,
+                  size_t n, const uint8_t *raw, size_t raw_len);
+int tdt_clip_keys(tdt_clip *h, uint64_t *k1, uint64_t *k2, size_t *n);
+int tdt_clip_finish(tdt_clip *h, uint64_t min_support, uint64_t *sn_out, size_t *n_rows);
+int tdt_clip_rows(tdt_clip *h, uint64_t *k1, uint32_t *side, uint32_t *support, uint32_t *rev, uint32_t *seqs, uint32_t *clen, uint64_t *consensus,
+                  uint64_t *agree, uint64_t *total, size_t *n);
+int tdt_clip_timing(tdt_clip *h, double *ms5);
+int tdt_clip_reserve_stats(tdt_clip *h, uint64_t *out3);
+size_t tdt_clip_sn_size(void);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

@@ -65,6 +65,13 @@ kernel compares every aligned base of every eligible read with it as the batches
 valid ``TIDDIT_ALLELES`` sites file as it stands.  Unset or empty is off; a value that is none of the four forms, or a contig of the BAM
 header that the FASTA lacks or holds at another length, ends the job with an error before the scan.  One process only, refused on N
 ranks like ``TIDDIT_INDELS``.
+
+``TIDDIT_CLIPS=1`` (minimum support 3, minimum MAPQ 20, minimum clip length 10), ``TIDDIT_CLIPS=S``, ``S:Q`` or ``S:Q:L``: ``--sv`` also
+writes ``{o}.clips.tab`` — every position where at least ``S`` eligible reads (MAPQ >= ``Q``) are soft-clipped by ``L`` bases or more on
+the same side, with the support by strand, a consensus of up to 28 clipped bases beside the breakpoint and the job's own 50-bp coverage
+bin (tiddit_amd/tiddit_clips.py has the definition and the file's format), from a key store the scan fills in HBM, one sort and a vote
+per site behind it.  Unset or empty is off; a value that is none of the four forms ends the job with an error before the scan.  One
+process only, refused on N ranks like ``TIDDIT_INDELS``.
 """
 import argparse
 import os
@@ -302,6 +309,13 @@ def run_sv(args, version):
         # (the same)
         print("error, TIDDIT_SNVS={}: {}".format(os.environ.get("TIDDIT_SNVS"), e))
         sys.exit(1)
+    try:
+        from . import tiddit_clips
+        clips = tiddit_clips.parse_switch(os.environ.get("TIDDIT_CLIPS"))
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_CLIPS={}: {}".format(os.environ.get("TIDDIT_CLIPS"), e))
+        sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
     if genotype_depth and sites_path is None:
@@ -391,6 +405,11 @@ def run_sv(args, version):
     if multi and snvs is not None:
         # (the same: a set of equal keys can straddle the shards)
         print("error, TIDDIT_SNVS is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
+              "keys on another rank")
+        sys.exit(1)
+    if multi and clips is not None:
+        # (the same: a site's keys can straddle the shards)
+        print("error, TIDDIT_CLIPS is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
               "keys on another rank")
         sys.exit(1)
     if multi:
@@ -566,6 +585,9 @@ def run_sv(args, version):
             # TIDDIT_SNVS: ... and a key per base that differs from the reference, one launch per batch
             tiddit_signal.SNVS = snvs
             tiddit_signal.SNV_REFERENCE = reference
+    if clips is not None:
+        # TIDDIT_CLIPS: ... and a key per soft clip of the reads, one launch per batch
+        tiddit_signal.CLIPS = clips
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -585,6 +607,7 @@ def run_sv(args, version):
             tiddit_signal.INDEL_REFERENCE = None      # (the counter holds it from here on)
             tiddit_signal.SNVS = None
             tiddit_signal.SNV_REFERENCE = None        # (the same)
+            tiddit_signal.CLIPS = None
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:
@@ -635,6 +658,14 @@ def run_sv(args, version):
         T["snv candidates ({o}.snvs.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_snvs.STAGE_SECONDS.items()})
         STAGE_NOTES.update(tiddit_snvs.STAGE_NOTES)
+    if clips is not None:
+        # (the same)
+        counter, tiddit_signal.CLIP_COUNTER = tiddit_signal.CLIP_COUNTER, None
+        t = time.time()
+        tiddit_clips.main(counter, prefix, coverage_data, chromosomes, clips[0])
+        T["clip sites ({o}.clips.tab)"] = time.time() - t
+        T.update({"  " + k: v for k, v in tiddit_clips.STAGE_SECONDS.items()})
+        STAGE_NOTES.update(tiddit_clips.STAGE_NOTES)
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,

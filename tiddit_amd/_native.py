@@ -180,6 +180,17 @@ SYMBOLS = {
     "tdt_snv_timing": (_i, [_P, _P]),
     "tdt_snv_reserve_stats": (_i, [_P, _P]),
     "tdt_snv_sn_size": (_sz, []),
+    "tdt_clip_create": (_i, [_P, _i, _i, _i, _sz, _PP]),
+    "tdt_clip_destroy": (_i, [_P]),
+    "tdt_clip_reset": (_i, [_P]),
+    "tdt_clip_push_device": (_i, [_P, _P, _sz, _sz]),
+    "tdt_clip_push": (_i, [_P] * 6 + [_sz, _P, _sz]),
+    "tdt_clip_keys": (_i, [_P, _P, _P, ctypes.POINTER(_sz)]),
+    "tdt_clip_finish": (_i, [_P, ctypes.c_uint64, _P, ctypes.POINTER(_sz)]),
+    "tdt_clip_rows": (_i, [_P] * 10 + [ctypes.POINTER(_sz)]),
+    "tdt_clip_timing": (_i, [_P, _P]),
+    "tdt_clip_reserve_stats": (_i, [_P, _P]),
+    "tdt_clip_sn_size": (_sz, []),
     "tdt_refseq_create": (_i, [_P, _i, _P, _PP]),
     "tdt_refseq_destroy": (_i, [_P]),
     "tdt_refseq_load_fasta": (_i, [_P, _i, _P, _i64, _i64, _i, _i]),

@@ -299,13 +299,14 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
 
     ``COV_TRACK = (bin_size, min_q)``: a second histogram over EVERY contig of the header is filled from the same batches (their second
     coverage-record column, written by the ingest kernel in the pass that decodes them) and its bins are left in ``COV_TRACK_BINS``."""
-    global COV_TRACK_BINS, ALLELE_COUNTER, QC_COUNTER, DUP_COUNTER, INDEL_COUNTER, SNV_COUNTER
+    global COV_TRACK_BINS, ALLELE_COUNTER, QC_COUNTER, DUP_COUNTER, INDEL_COUNTER, SNV_COUNTER, CLIP_COUNTER
     COV_TRACK_BINS = None
     ALLELE_COUNTER = None
     QC_COUNTER = None
     DUP_COUNTER = None
     INDEL_COUNTER = None
     SNV_COUNTER = None
+    CLIP_COUNTER = None
     track = COV_TRACK
     max_ins = int(max_ins)         # the reference's `int max_ins` argument truncates a float percentile (:147,:230; probed with Cython 3.2)
     from . import bamio
@@ -401,6 +402,15 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         snvs = tiddit_snvs.SnvCounter(len(names), SNV_REFERENCE, SNVS[1], SNVS[2], capacity=min(max(os.path.getsize(bam_file_name) // 16, 1 << 16), 1 << 26),
                                       ctx=getattr(reader, "ctx", None))
         T["snv keys (push)"] = 0.0
+    clipc = None
+    if CLIPS is not None:
+        # TIDDIT_CLIPS: a key store in HBM; every batch costs one more launch on the columns and bytes it already holds there
+        from . import tiddit_clips
+        # (room for 2 keys per read is reserved before each launch: a read per ~90 compressed bytes makes file size / 32 about 1.4 x the whole
+        #  file's bound; the store grows 1.5x when a batch does not fit)
+        clipc = tiddit_clips.ClipCounter(len(names), CLIPS[1], CLIPS[2], capacity=min(max(os.path.getsize(bam_file_name) // 32, 1 << 16), 1 << 26),
+                                         ctx=getattr(reader, "ctx", None))
+        T["clip keys (push)"] = 0.0
     tables = data = splits = clips = None
     if isinstance(reader, DeviceBamReader):
         from .sigtab import SignalTables
@@ -478,6 +488,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                     t3b = time.time()
                     T["snv keys (push)"] += t3b - t3
                     t3 = t3b
+                if clipc is not None:                           # (the same, beside the SNV push)
+                    clipc.push_device_batch(b)
+                    t3b = time.time()
+                    T["clip keys (push)"] += t3b - t3
+                    t3 = t3b
                 # the per-read chain of worker (:171-221) on the device; only the selected reads come back (fields + raw records)
                 # (once the scan's kernels are enqueued nothing will read the batch's raw bytes again: the next span's inflate is started
                 #  behind them — DeviceBamReader.ahead() — and runs while this thread waits for the selected reads and hands them on)
@@ -518,6 +533,10 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 t1b = time.time()
                 snvs.push_host_batch(b)
                 T["snv keys (push)"] += time.time() - t1b
+            if clipc is not None:
+                t1b = time.time()
+                clipc.push_host_batch(b)
+                T["clip keys (push)"] += time.time() - t1b
             tid = b.tid
             flag = b.flag.astype(numpy.int32)
             placed = tid >= 0
@@ -588,6 +607,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             indels.close()
         if snvs is not None:
             snvs.close()
+        if clipc is not None:
+            clipc.close()
         raise
     finally:
         pool.shutdown(wait=True)                              # (also on an error: no row thread outlives the scan)
@@ -610,12 +631,15 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         indels.ctx.sync()                                       # (the same)
     if snvs is not None:
         snvs.ctx.sync()                                         # (the same)
+    if clipc is not None:
+        clipc.ctx.sync()                                        # (the same)
     reader.close()
     ALLELE_COUNTER = alleles                                    # (the caller reads the counters and closes it)
     QC_COUNTER = qc                                             # (the same)
     DUP_COUNTER = dups                                          # (the same: the caller runs its finish and closes it)
     INDEL_COUNTER = indels                                      # (the same)
     SNV_COUNTER = snvs                                          # (the same)
+    CLIP_COUNTER = clipc                                        # (the same)
     if store is not None:
         from . import tiddit_variant
         if tiddit_variant.LIVE_STORE is not None:
@@ -674,6 +698,8 @@ INDEL_REFERENCE = None      # a refseq.RefSeq: the indel counter of the scan lef
 SNVS = None                 # (min_support, min_mapq, min_bq): the scan also stores a key per base that differs from SNV_REFERENCE (tiddit_snvs.SnvCounter), one launch per batch
 SNV_REFERENCE = None        # a refseq.RefSeq: the reference the SNV counter compares with (TIDDIT_SNVS; the same handle as INDEL_REFERENCE when both are set)
 SNV_COUNTER = None          # that counter after the last scan that had SNVS set (the caller runs its finish and closes it), else None
+CLIPS = None                # (min_support, min_mapq, min_clip): the scan also stores a key per soft clip of the reads (tiddit_clips.ClipCounter), one launch per batch
+CLIP_COUNTER = None         # that counter after the last scan that had CLIPS set (the caller runs its finish and closes it), else None
 INDEL_COUNTER = None        # that counter after the last scan that had INDELS set (the caller runs its finish and closes it), else None
 KEEP_EVIDENCE = False       # the scan packs every placed record into an evidence store for the variant stage (tiddit_variant.LIVE_STORE)
 AFTER_SCAN = []             # callables main() invokes once the file has been scanned, before the tables are written (host-only work from there on)
