@@ -10,6 +10,8 @@ supports the finish is asked for), ``family``, ``claims`` (a sentence) and ``row
 stated by the read itself (``events`` / ``short`` / ``cut``) where the record is patched.  A literal row is
 ``(tid, P, side, SUPPORT, REV, SEQS, CLEN, consensus outward from the breakpoint, AGREE, TOTAL)``."""
 import collections
+import os
+import re
 import struct
 
 import numpy as np
@@ -358,5 +360,27 @@ case("store", "700 reads in three pushes, a store made for 64 keys",
      "40 reads need 80 slots of a store of 64 (it grows), the next 560 (three workgroups of reads) need 1120 more (it grows again), the last 100 "
      "fit behind the real count; lengths 10 ... 32, both sides, both strands, every fourth read below the MAPQ cut",
      [_many[:40], _many[40:600], _many[600:]], capacity=64)
+
+# ---- the workgroup of clip_keys: the compaction, the staging and the emit on their edges
+# the reads of a clip_keys workgroup, from the `#define` line of csrc/tdt_clip.hip: the cases stay on its edges when it is retuned
+CLIP_BLOCK = int(re.search(r"^[ \t]*#[ \t]*define[ \t]+CLIP_K_TILE[ \t]+([0-9]+)[ \t]*(?://[^\n]*)?$",
+                           open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tiddit_amd", "csrc", "tdt_clip.hip")).read(), re.M).group(1))
+for _n in (CLIP_BLOCK - 1, CLIP_BLOCK, CLIP_BLOCK + 1):
+    case("store", "%d reads with one clip each" % _n,
+         "a batch of one workgroup less one read, of exactly one, and of one read more (a second workgroup with a single read); every seventh read "
+         "is below the MAPQ cut, so the compaction moves the reads behind it; leading and trailing clips alternate",
+         [[rd(pos=2000 + 3 * (k % 50), lead=bases(12, k % 4) if k % 2 else "", trail="" if k % 2 else bases(11 + k % 3, k % 3), flag=REV * (k % 3 == 0),
+              mapq=3 if k % 7 == 3 else 60, kind=NOT_ELIGIBLE if k % 7 == 3 else OK) for k in range(_n)]])
+case("store", "every read of two workgroups has both clips",
+     "512 reads with a leading and a trailing clip of at least L bases: the staging of both workgroups is full at two keys per read, and the "
+     "store, made for exactly 2 x 512 keys, is full too",
+     [[rd(pos=3000 + k % 20, lead=bases(10 + k % 5, k % 4), trail=bases(10 + k % 4, k % 3), flag=REV * (k & 1)) for k in range(2 * CLIP_BLOCK)]],
+     S=(1, 3), capacity=2 * 2 * CLIP_BLOCK)
+case("store", "only the last lane of each workgroup holds an eligible read",
+     "513 reads, read k eligible only for k % 256 == 255: the compaction hands that read to lane 0, three waves of each workgroup emit nothing, and "
+     "the third workgroup holds one ineligible read and emits no key",
+     [[rd(pos=4000, lead=bases(12), trail=bases(12, 1), mapq=60 if k % CLIP_BLOCK == CLIP_BLOCK - 1 else 3,
+          kind=OK if k % CLIP_BLOCK == CLIP_BLOCK - 1 else NOT_ELIGIBLE) for k in range(2 * CLIP_BLOCK + 1)]],
+     rows={2: [(0, 4001, L_SIDE, 2, 0, 1, 12, bases(12)[::-1], 24, 24), (0, 4020, R_SIDE, 2, 0, 1, 12, bases(12, 1), 24, 24)]})
 
 N_CASES = len(CASES)

@@ -483,6 +483,12 @@ case("shape", "every read of a workgroup gives 4 events", [R(_D4 + [(0, 2)], pos
 _ONE = lambda n: ([R(_F, pos=10 * i) for i in range(n)], [((K1(0, 10 * i + 5), DEL(1)), 1) for i in range(n)], plain(n, reads_with_events=n, deletions=n))
 case("shape", "a store that grows once from a capacity of 64", *_ONE(30), cuts=(10,), capacity=64, grows=1, asks=1)
 case("shape", "a store that grows twice from a capacity of 64", *_ONE(60), cuts=(10, 30), capacity=64, grows=2, asks=2)
+# (the push kernel's compaction and emit with nothing to do in most of a workgroup: the eligible read goes to lane 0, three waves of every
+#  round emit nothing, and the third workgroup holds one read below the MAPQ cut and emits no key)
+_NL = 2 * INDEL_K_TILE + 1
+_LAST = [i for i in range(_NL) if i % INDEL_BLOCK == INDEL_BLOCK - 1]
+case("shape", "only the last lane of every round holds an eligible read", [R(_F, pos=10 * i, mapq=60 if i in _LAST else 3) for i in range(_NL)],
+     [((K1(0, 10 * i + 5), DEL(1)), 1) for i in _LAST], {"records": _NL, "eligible": len(_LAST), "reads_with_events": len(_LAST), "deletions": len(_LAST)})
 
-N_CASES = 52
+N_CASES = 53
 FAMILIES = sorted({c["family"] for c in CASES})

@@ -134,7 +134,7 @@ def defined():
 
 # ---- the cases -----------------------------------------------------------------------------------------------------------------
 def test_the_cases_are_the_stated_ones():
-    assert D.N_CASES == len(D.CASES) == 30 and len({c["name"] for c in D.CASES}) == 30
+    assert D.N_CASES == len(D.CASES) == 35 and len({c["name"] for c in D.CASES}) == 35
     assert {c["family"] for c in D.CASES} == {"length", "phase", "other", "hard", "both", "nothing", "malformed", "filter", "strand", "site", "vote", "depth",
                                               "support", "store"}
     assert all(c["claims"] for c in D.CASES)

@@ -124,8 +124,8 @@ def test_both_entries_equal_the_definition(case, entry, wanted, ctx):
 
 
 def test_the_stated_count_of_case_entry_pairs_ran():
-    assert len(D.CASES) == D.N_CASES == 30
-    assert len(set(PAIRS)) == 2 * 30, len(set(PAIRS))
+    assert len(D.CASES) == D.N_CASES == 35
+    assert len(set(PAIRS)) == 2 * 35, len(set(PAIRS))
 
 
 # ---- structure cases for the site launches: keys made by pushes of tiny records --------------------------------------------------

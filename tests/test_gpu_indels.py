@@ -113,8 +113,8 @@ def test_push_device_from_a_small_bam_equals_the_reference(case, wanted, tmp_pat
 
 
 def test_the_stated_count_of_case_entry_pairs_ran():
-    assert len(D.CASES) == D.N_CASES == 52 and len(READER_OK) == 33
-    assert len(set(PAIRS)) == 52 + 33, len(set(PAIRS))
+    assert len(D.CASES) == D.N_CASES == 53 and len(READER_OK) == 34
+    assert len(set(PAIRS)) == 53 + 34, len(set(PAIRS))
 
 
 def _case(name):

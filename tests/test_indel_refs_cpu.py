@@ -16,7 +16,7 @@ def refs():
 
 
 def test_the_stated_number_of_cases_in_seven_families():
-    assert len(D.CASES) == D.N_CASES == 52 and len({c["name"] for c in D.CASES}) == 52
+    assert len(D.CASES) == D.N_CASES == 53 and len({c["name"] for c in D.CASES}) == 53
     assert D.FAMILIES == ["cap", "filters", "malformed", "sequence", "sets", "shape", "walk"]
     assert sorted(set(D.MUTANTS.values())) == ["cap", "filters", "sequence", "sets", "walk"] and len(D.MUTANTS) == 8
     assert T.SN == D.SN and T.SIZE == D.SIZE == 11 and T.INDEL_MAX_PER_READ == 4

@@ -371,6 +371,11 @@ def host_columns(b, names):
     return cols, raw
 
 
+def _raw_of(b):
+    """the raw record bytes of a batch as the read-by-read definitions index them: bytes-like, a byte per index"""
+    return b.raw if isinstance(b.raw, (bytes, bytearray)) else memoryview(np.ascontiguousarray(b.raw, dtype=np.uint8))
+
+
 class DeviceBatch:
     """One ingest batch resident in HBM (csrc/tdt_ingest.hip).  ``dev[name]`` is the device pointer of a field array,
     ``runs`` the per-contig record ranges ``[(tid, lo, hi)]``; reading a field attribute (``b.pos``, ``b.raw`` ...)

@@ -1,5 +1,6 @@
-// Device side of a consumer of the --sv scan that reads raw BAM record bytes (tdt_alleles / tdt_qc / tdt_dup): the record bound, the
-// unaligned load, the wave reduction and the in-workgroup compaction, each written once.  Host side: tdt_batch.h.
+// Device side of a consumer of the --sv scan that reads raw BAM record bytes (tdt_alleles / tdt_qc / tdt_dup / tdt_indel / tdt_snv /
+// tdt_clip): the record bound, the unaligned load, the CIGAR op classes and span, the 4-bit base read, the wave reduction and the
+// in-workgroup compaction, each written once.  Host side: tdt_batch.h.
 #pragma once
 #include "tdt_common.h"
 
@@ -35,6 +36,50 @@ struct tdt_rec {
 #define TDT_REC_READ(raw, ro)                                                                                                             \
     tdt_rec{(ro), tdt_ld_u32((raw) + (ro)), ((raw) + (ro) + 4)[8], (unsigned)((raw) + (ro) + 4)[12] | ((unsigned)((raw) + (ro) + 4)[13] << 8), \
             (int)tdt_ld_u32((raw) + (ro) + 4 + 16)}
+
+// ---- the CIGAR and the sequence of an opened record
+// the ops whose length lies on the reference (M D N = X) / on the query (M I S = X)
+__device__ __forceinline__ bool tdt_cig_on_ref(unsigned op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
+__device__ __forceinline__ bool tdt_cig_on_query(unsigned op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
+
+// the 4-bit code of query base `at` of the sequence at raw[seq ...] (the even base in the high nibble)
+__device__ __forceinline__ unsigned tdt_rec_base(const uint8_t *__restrict__ raw, unsigned long long seq, unsigned long long at) {
+    return (raw[seq + (at >> 1)] >> ((at & 1ull) ? 0 : 4)) & 0xfu;
+}
+
+// ONE pass over the n_cig words at cig: the CIGAR's reference and query lengths and whether an op code above 8 was seen; with EDGES
+// also the first two words and the last two (w0 w1 ... wy wz; zero where there is none, one word twice for n_cig == 1: w0 == wz).
+// EDGES is a template argument because the tests on j peel the loop even where the words are never used: snv_keys, which does not
+// want them, was slower with them (profiles/keyed_emit_240mb.md).  malformed(): the verdicts every consumer of the span shares — an
+// op code above 8, pos + the reference length beyond 2^31 - 1, a query length that differs from l_seq (where both a sequence and a
+// CIGAR are there).
+struct tdt_cig_span {
+    unsigned long long ref_len, query_len;
+    unsigned w0, w1, wy, wz;
+    bool bad_op;
+    __device__ __forceinline__ bool malformed(int pos, int l_seq, unsigned n_cig) const {
+        bool worse = bad_op;
+        worse |= (unsigned long long)pos + ref_len > 0x7fffffffull;
+        worse |= l_seq >= 1 && n_cig >= 1 && query_len != (unsigned long long)l_seq;
+        return worse;
+    }
+};
+template <bool EDGES = false> __device__ __forceinline__ tdt_cig_span tdt_cig_span_of(const uint8_t *cig, unsigned n_cig) {
+    tdt_cig_span s{0, 0, 0, 0, 0, 0, false};
+    for (unsigned j = 0; j < n_cig; j++) {
+        const unsigned w = tdt_ld_u32(cig + 4ull * j), op = w & 0xfu, len = w >> 4;
+        s.bad_op |= op > 8;
+        s.ref_len += tdt_cig_on_ref(op) ? (unsigned long long)len : 0ull;
+        s.query_len += tdt_cig_on_query(op) ? (unsigned long long)len : 0ull;
+        if constexpr (EDGES) {
+            if (j == 0) s.w0 = w;
+            if (j == 1) s.w1 = w;
+            s.wy = s.wz;
+            s.wz = w;
+        }
+    }
+    return s;
+}
 
 // ---- a value of every lane reduced over the wave by a butterfly: all 64 lanes call it and all receive the result
 struct tdt_sum { template <class T> __device__ static T of(T a, T b) { return a + b; } };

@@ -5,14 +5,13 @@
 // breakpoint, two bits each; equal (K1, K2 >> 1) is one distinct sequence, equal (K1, side) one site.  Every result is an
 // order-independent integer, so it equals the definition exactly.
 //   * clip_keys — ONE launch per batch, on the columns and record bytes that are already resident, enqueued beside snv_keys and waiting
-//     for nothing.  Lane = read for the filters (flag, tid, mapq: coalesced columns).  The reads that need their bytes are compacted
-//     inside the workgroup (tdt_block_slots), then lane = compacted read: the record is bounded with TDT_REC_*, exactly as tdt_snv
-//     bounds one; ONE pass over the CIGAR sums its reference and query lengths and looks for an op code above 8; the first two and
-//     the last two words decide the clips; up to 28 nibbles per clip are read byte by byte from the sequence (a leading clip is
-//     walked backwards from its last base, a trailing one forwards from its first, so both nibble phases occur on both sides), and
+//     for nothing.  The read gate (ks_read_gate), the record open (KS_OPEN) and the key emit (ks_stage, ks_flush) are tdt_keystore.h's,
+//     shared with indel_keys and snv_keys.  Behind the gate lane = compacted read: ONE pass over the CIGAR (tdt_cig_span_of<true>,
+//     tdt_bam_record.h) sums its reference and query lengths, looks for an op code above 8 and keeps the first two and the last two
+//     words, which decide the clips; up to 28 nibbles per clip are read byte by byte from the sequence (tdt_rec_base; a leading clip
+//     is walked backwards from its last base, a trailing one forwards from its first, so both nibble phases occur on both sides), and
 //     the walk stops at the first code that is not A C G T.  At most two keys per read are staged in LDS (256 reads x 2 keys x 16 B =
-//     8 KB) and appended to the store behind ONE atomic per workgroup; the counters and the sort masks are merged per wave and then
-//     over the workgroup, one atomic per workgroup and non-zero word.
+//     8 KB) and flushed once.
 //     WHICH reads need their bytes: every eligible one.  The ingest's CIGAR_FIRST / CIGAR_LAST columns do equal the record's own first
 //     and last words (tdt_ingest.hip's decode writes `n_cig ? ld_u32(cig) : 0xffffffff` and `n_cig ? ld_u32(cig + 4 * (n_cig - 1)) :
 //     0xffffffff`: one word twice for n_cig == 1, an op code of 15 for n_cig == 0), but they cannot stand in for the bytes here: the
@@ -41,8 +40,6 @@ typedef unsigned long long ull;
 #define CLIP_K_TILE 256                       // reads of a clip_keys workgroup (one round); it stages at most 2 x that many keys in LDS (8 KB)
 #define CLIP_VOTE_BLOCK 64                    // one wavefront per site
 #define CLIP_VOTE_GRID 4096                   // workgroups of clip_vote at most (grid-strided over the sites)
-#define CLIP_MAX_CONTIGS (1 << 24)
-#define CLIP_END_LIMIT 0x7fffffffll           // pos + the CIGAR's reference length is at most this
 
 static_assert(CLIP_K_TILE == CLIP_BLOCK, "one round per workgroup");
 static_assert(TDT_CLIP_MAX_PER_READ == 2, "a leading and a trailing clip");
@@ -79,111 +76,62 @@ struct tdt_clip {
     double ms_sites;
 };
 
-struct ClipIn {
-    const uint16_t *flag;
-    const int32_t *tid, *pos;
-    const uint8_t *mapq;
-    const uint64_t *rec_off;
-    const uint8_t *raw;
-};
-
-// the 4-bit code of query base qi of the sequence at raw[seq ...] (the even base in the high nibble)
-__device__ __forceinline__ unsigned clip_base(const uint8_t *__restrict__ raw, ull seq, ull qi) {
-    const unsigned v = raw[seq + (qi >> 1)];
-    return (qi & 1ull) ? v & 0xfu : v >> 4;
-}
-
-__global__ __launch_bounds__(CLIP_BLOCK) void clip_keys(ClipIn I, int n, ull raw_len, unsigned min_mapq, unsigned min_clip, ull *__restrict__ k1s,
+__global__ __launch_bounds__(CLIP_BLOCK) void clip_keys(ks_cols I, int n, ull raw_len, unsigned min_mapq, unsigned min_clip, ull *__restrict__ k1s,
                                                         ull *__restrict__ k2s, ull cap, ull *__restrict__ st) {
     __shared__ ull s_k1[CLIP_K_TILE * TDT_CLIP_MAX_PER_READ], s_k2[CLIP_K_TILE * TDT_CLIP_MAX_PER_READ];   // the tile's keys, in the order they were made
-    __shared__ int s_read[CLIP_BLOCK];
-    __shared__ int s_wsum[CLIP_BLOCK / 64], s_wkeys[CLIP_BLOCK / 64];
-    __shared__ ull s_cnt[CLIP_BLOCK / 64][SN_PUSH_N + 4];         // per wave: the push counters, then the OR / NAND words
-    __shared__ ull s_base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const long long lo = (long long)blockIdx.x * CLIP_K_TILE, hi = lo + CLIP_K_TILE < n ? lo + CLIP_K_TILE : n;
     ull cnt[SN_PUSH_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};          // (short_clips, cut: this lane's; the others: wave-uniform sums of ballots)
-    ull or1 = 0, nand1 = 0, or2 = 0, nand2 = 0;                   // (this lane's keys; merged over the wave at the end)
-    // ---- lane = read: the filters on the columns
-    const long long i = lo + t;
-    bool elig = false;
-    if (i < hi) elig = (I.flag[i] & 0xF04u) == 0 && I.tid[i] >= 0 && (unsigned)I.mapq[i] >= min_mapq;
-    const ull m_rec = __ballot(i < hi), m_el = __ballot(elig);
-    cnt[SN_RECORDS] = (ull)__popcll(m_rec);
-    cnt[SN_ELIGIBLE] = (ull)__popcll(m_el);
-    const tdt_slots S = tdt_block_slots<CLIP_BLOCK / 64>(m_el, s_wsum, lane, wave);
-    if (elig) s_read[S.base + tdt_lane_rank(m_el, lane)] = (int)i;
-    __syncthreads();
-    // ---- lane = compacted read: bound the record, sum its CIGAR, take its clips
-    const bool live = t < S.total;
+    // ---- lane = read: the filters on the columns; then lane = compacted read
+    const ks_gated G = ks_read_gate<CLIP_BLOCK>(I, lo, hi, min_mapq, cnt[SN_RECORDS], cnt[SN_ELIGIBLE]);
+    const bool live = (int)threadIdx.x < G.live;
     bool bad = live, noseq = false, noaln = false;
     unsigned nshort = 0, ncut = 0;
     bool ev[2] = {false, false};                                   // the leading clip's event, the trailing clip's
     ull eK1[2] = {0, 0}, eK2[2] = {0, 0};
+    ks_read A{};
     const uint8_t *__restrict__ raw = I.raw;
-    if (live) {
-        const int ri = s_read[t];
-        const unsigned rev = ((unsigned)I.flag[ri] >> 4) & 1u;
-        const int tid = I.tid[ri], pos = I.pos[ri];
-        const ull ro = I.rec_off[ri];
-        if (tid < CLIP_MAX_CONTIGS && pos >= 0 && TDT_REC_HEADER_INSIDE(raw_len, ro)) {
-            tdt_rec R = TDT_REC_READ(raw, ro);
-            const int l_seq = R.l_seq;
-            R.l_seq = l_seq < 0 ? 0 : l_seq;                       // (clamped: the body's sum never sees a negative length)
-            if (l_seq >= 0 && TDT_REC_FITS(R, raw_len)) {
-                const uint8_t *cig = raw + R.cig();
-                const unsigned nc = R.n_cig;
-                ull rl = 0, ql = 0;
-                bool worse = false;
-                unsigned w0 = 0, w1 = 0, wy = 0, wz = 0;           // the first two words and the last two (wz the last)
-                for (unsigned j = 0; j < nc; j++) {
-                    const unsigned w = tdt_ld_u32(cig + 4ull * j), op = w & 0xfu, len = w >> 4;
-                    worse |= op > 8;
-                    rl += (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? (ull)len : 0ull;
-                    ql += (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) ? (ull)len : 0ull;
-                    if (j == 0) w0 = w;
-                    if (j == 1) w1 = w;
-                    wy = wz;
-                    wz = w;
-                }
-                worse |= (ull)pos + rl > (ull)CLIP_END_LIMIT;
-                worse |= l_seq >= 1 && nc >= 1 && ql != (ull)l_seq;
-                bad = worse;
-                if (!bad) {
-                    noseq = nc == 0 || l_seq == 0;
-                    noaln = !noseq && rl == 0;
-                }
-                if (!bad && !noseq && !noaln) {
-                    // the CIGAR spans exactly l_seq bases: a leading clip is query [0, len), a trailing one [l_seq - len, l_seq)
-                    const ull seq = R.seq();
-                    const bool lead = (w0 & 0xfu) == 4u || ((w0 & 0xfu) == 5u && nc >= 2 && (w1 & 0xfu) == 4u);
-                    const bool trail = (wz & 0xfu) == 4u || ((wz & 0xfu) == 5u && nc >= 2 && (wy & 0xfu) == 4u);
-                    const unsigned llen = ((w0 & 0xfu) == 4u ? w0 : w1) >> 4, tlen = ((wz & 0xfu) == 4u ? wz : wy) >> 4;
+    if (live && KS_OPEN(A, I, G.read, raw_len)) {
+        // ---- the record is bounded: sum its CIGAR, take its clips
+        const tdt_rec &R = A.R;
+        const int tid = A.tid, pos = A.pos, l_seq = R.l_seq;
+        const unsigned nc = R.n_cig;
+        const tdt_cig_span C = tdt_cig_span_of<true>(raw + R.cig(), nc);
+        const unsigned w0 = C.w0, w1 = C.w1, wy = C.wy, wz = C.wz;  // the first two words and the last two (wz the last)
+        const ull rl = C.ref_len;
+        bad = C.malformed(pos, l_seq, nc);
+        if (!bad) {
+            noseq = nc == 0 || l_seq == 0;
+            noaln = !noseq && rl == 0;
+        }
+        if (!bad && !noseq && !noaln) {
+            // the CIGAR spans exactly l_seq bases: a leading clip is query [0, len), a trailing one [l_seq - len, l_seq)
+            const ull seq = R.seq();
+            const bool lead = (w0 & 0xfu) == 4u || ((w0 & 0xfu) == 5u && nc >= 2 && (w1 & 0xfu) == 4u);
+            const bool trail = (wz & 0xfu) == 4u || ((wz & 0xfu) == 5u && nc >= 2 && (wy & 0xfu) == 4u);
+            const unsigned llen = ((w0 & 0xfu) == 4u ? w0 : w1) >> 4, tlen = ((wz & 0xfu) == 4u ? wz : wy) >> 4;
 #pragma unroll
-                    for (int side = 0; side < 2; side++) {
-                        const bool has = side ? trail : lead;
-                        const unsigned clen = side ? tlen : llen;
-                        if (!has) continue;
-                        if (clen < min_clip) {
-                            nshort++;
-                            continue;
-                        }
-                        const unsigned want = clen < (unsigned)TDT_CLIP_COLS ? clen : (unsigned)TDT_CLIP_COLS;
-                        const ull q0 = side ? (ull)l_seq - clen : (ull)clen - 1ull;      // column 0's query index; column j: q0 + j (R), q0 - j (L)
-                        unsigned nb = 0;
-                        ull bases = 0;
-                        while (nb < want) {
-                            const unsigned c = clip_base(raw, seq, side ? q0 + nb : q0 - nb);
-                            if (__popc(c) != 1) break;
-                            bases |= (ull)__builtin_ctz(c) << (2u * nb);
-                            nb++;
-                        }
-                        ncut += nb < want;
-                        ev[side] = true;
-                        eK1[side] = ((ull)(unsigned)tid << 32) | (side ? (ull)pos + rl : (ull)pos + 1ull);
-                        eK2[side] = ((ull)side << 63) | ((ull)nb << 58) | (bases << 2) | (ull)rev;
-                    }
+            for (int side = 0; side < 2; side++) {
+                const bool has = side ? trail : lead;
+                const unsigned clen = side ? tlen : llen;
+                if (!has) continue;
+                if (clen < min_clip) {
+                    nshort++;
+                    continue;
                 }
+                const unsigned want = clen < (unsigned)TDT_CLIP_COLS ? clen : (unsigned)TDT_CLIP_COLS;
+                const ull q0 = side ? (ull)l_seq - clen : (ull)clen - 1ull;      // column 0's query index; column j: q0 + j (R), q0 - j (L)
+                unsigned nb = 0;
+                ull bases = 0;
+                while (nb < want) {
+                    const unsigned c = tdt_rec_base(raw, seq, side ? q0 + nb : q0 - nb);
+                    if (__popc(c) != 1) break;
+                    bases |= (ull)__builtin_ctz(c) << (2u * nb);
+                    nb++;
+                }
+                ncut += nb < want;
+                ev[side] = true;
+                eK1[side] = ((ull)(unsigned)tid << 32) | (side ? (ull)pos + rl : (ull)pos + 1ull);
+                eK2[side] = ((ull)side << 63) | ((ull)nb << 58) | (bases << 2) | (ull)A.rev;
             }
         }
     }
@@ -195,60 +143,20 @@ __global__ __launch_bounds__(CLIP_BLOCK) void clip_keys(ClipIn I, int n, ull raw
     cnt[SN_CLIPPED_READS] = (ull)__popcll(__ballot(ev[0] || ev[1]));
     cnt[SN_SHORT_CLIPS] = tdt_wave_reduce<tdt_sum>((ull)nshort);
     cnt[SN_CUT] = tdt_wave_reduce<tdt_sum>((ull)ncut);
-    // ---- the tile's keys in LDS: slots by a prefix sum of the reads' event counts
-    const int mine = (int)ev[0] + (int)ev[1];
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(incl, o);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) s_wkeys[wave] = incl;
-    __syncthreads();
-    int base = 0, nk = 0;                                          // nk: the keys of the tile (uniform over the workgroup)
-#pragma unroll
-    for (int w = 0; w < CLIP_BLOCK / 64; w++) {
-        base += w < wave ? s_wkeys[w] : 0;
-        nk += s_wkeys[w];
-    }
-    int slot = base + incl - mine;                                 // (+ mine <= nk <= 2 x the reads of the tile)
+    // ---- the tile's keys in LDS, then the emit (tdt_keystore.h)
+    int nk;                                                        // the keys of the tile (uniform over the workgroup)
+    int slot = ks_stage<CLIP_BLOCK>((int)ev[0] + (int)ev[1], &nk);        // (+ mine <= nk <= 2 x the reads of the tile)
+    ks_masks M;
 #pragma unroll
     for (int side = 0; side < 2; side++) {
         if (ev[side]) {
-            const ull k1 = eK1[side], k2 = eK2[side];
-            or1 |= k1, nand1 |= ~k1, or2 |= k2, nand2 |= ~k2;
-            s_k1[slot] = k1;
-            s_k2[slot] = k2;
+            M.add(eK1[side], eK2[side]);
+            s_k1[slot] = eK1[side];
+            s_k2[slot] = eK2[side];
             slot++;
         }
     }
-    // ---- the tile's counters: merged per wave, then over the workgroup, ONE atomic per non-zero counter
-    or1 = tdt_wave_reduce<tdt_or>(or1), nand1 = tdt_wave_reduce<tdt_or>(nand1), or2 = tdt_wave_reduce<tdt_or>(or2), nand2 = tdt_wave_reduce<tdt_or>(nand2);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < SN_PUSH_N; k++) s_cnt[wave][k] = cnt[k];
-        s_cnt[wave][SN_PUSH_N] = or1, s_cnt[wave][SN_PUSH_N + 1] = nand1, s_cnt[wave][SN_PUSH_N + 2] = or2, s_cnt[wave][SN_PUSH_N + 3] = nand2;
-    }
-    __syncthreads();
-    if (t == 0) s_base = nk ? atomicAdd(&st[KS_N], (ull)nk) : 0ull;          // the workgroup's slots of the store behind ONE atomic
-    if (t < SN_PUSH_N + 4) {
-        ull v = 0;
-        for (int w = 0; w < CLIP_BLOCK / 64; w++) v = t < SN_PUSH_N ? v + s_cnt[w][t] : v | s_cnt[w][t];
-        if (v) {
-            if (t < SN_PUSH_N) atomicAdd(&st[t], v);
-            else atomicOr(&st[ST_OR1 + (t - SN_PUSH_N)], v);
-        }
-    }
-    __syncthreads();
-    for (int k = t; k < nk; k += CLIP_BLOCK) {                     // (consecutive lanes, consecutive slots)
-        const ull at = s_base + (ull)k;
-        if (at < cap) {
-            k1s[at] = s_k1[k];
-            k2s[at] = s_k2[k];
-        } else {
-            st[KS_OVERFLOW] = 1;                                   // (cannot happen: the host reserved 2 slots for every read of the batch)
-        }
-    }
+    ks_flush<CLIP_BLOCK, SN_PUSH_N>(cnt, M, nk, s_k1, s_k2, k1s, k2s, cap, st);
 }
 
 // ---- the sites of the finish's rows (a = K1, b = K2 with bit 0 clear, ascending by (K1, K2); n rows)
@@ -371,7 +279,7 @@ extern "C" int tdt_clip_create(tdt_ctx *ctx, int n_contigs, int min_mapq, int mi
         tdt_set_error("tdt_clip_create: bad argument");
         return TDT_E_ARG;
     }
-    if (n_contigs > CLIP_MAX_CONTIGS || min_mapq < 0 || min_mapq > 255 || min_clip < 1 || min_clip > TDT_CLIP_MAX_CLIP || capacity >= (1ull << 40)) {
+    if (!ks_create_in_range(n_contigs, min_mapq, capacity) || min_clip < 1 || min_clip > TDT_CLIP_MAX_CLIP) {
         tdt_set_error("tdt_clip_create: %d contigs (at most 2^24), min_mapq %d (0 ... 255), min_clip %d (1 ... %d), capacity %zu", n_contigs, min_mapq,
                       min_clip, TDT_CLIP_MAX_CLIP, capacity);
         return TDT_E_RANGE;
@@ -399,66 +307,34 @@ extern "C" int tdt_clip_create(tdt_ctx *ctx, int n_contigs, int min_mapq, int mi
     return TDT_OK;
 }
 
-extern "C" int tdt_clip_destroy(tdt_clip *h) {
-    if (!h) return TDT_OK;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);        // (no kernel of the stream still writes the store)
-    clip_free(h);
-    return TDT_OK;
-}
+extern "C" int tdt_clip_destroy(tdt_clip *h) { return ks_destroy(h, clip_free); }
 
 extern "C" int tdt_clip_reset(tdt_clip *h) {
-    if (!h) {
-        tdt_set_error("tdt_clip_reset: bad argument");
-        return TDT_E_ARG;
-    }
-    h->n_rows = 0;
-    return ks_reset(&h->S);
+    if (h) h->n_rows = 0;
+    return ks_reset_checked(h ? &h->S : nullptr, "tdt_clip");
 }
 
-static int clip_launch(tdt_clip *h, const ClipIn &I, size_t n, size_t raw_len) {
-    const size_t room = n * TDT_CLIP_MAX_PER_READ;                 // the bound two clips per read give
-    int rc = ks_reserve(&h->S, room);
-    if (rc) return rc;
-    const dim3 grid((unsigned)((n + CLIP_K_TILE - 1) / CLIP_K_TILE));
-    hipLaunchKernelGGL(clip_keys, grid, dim3(CLIP_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, (unsigned)h->min_clip, h->S.k1,
-                       h->S.k2, (ull)h->S.cap, h->S.d_state);
-    TDT_CHECK_LAUNCH();
-    h->S.upper += room;
-    h->S.rows_valid = false;
-    h->n_rows = 0;
-    return TDT_OK;
+// the launch of one batch: TDT_CLIP_MAX_PER_READ slots of the store per read, the bound two clips per read give
+static auto clip_launch(tdt_clip *h, size_t n, size_t raw_len) {
+    return [=](const ks_cols &I) {
+        const int rc = ks_launch(&h->S, n * TDT_CLIP_MAX_PER_READ, [&] {
+            const dim3 grid((unsigned)((n + CLIP_K_TILE - 1) / CLIP_K_TILE));
+            hipLaunchKernelGGL(clip_keys, grid, dim3(CLIP_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, (unsigned)h->min_clip,
+                               h->S.k1, h->S.k2, (ull)h->S.cap, h->S.d_state);
+        });
+        if (rc == TDT_OK) h->n_rows = 0;
+        return rc;
+    };
 }
 
-#define CLIP_NEED (TDT_NEED(FLAG) | TDT_NEED(TID) | TDT_NEED(POS) | TDT_NEED(MAPQ) | TDT_NEED(REC_OFF) | TDT_NEED(RAW))
-
-// One batch of the device ingest: d_arrays14 = the pointer table tdt_ingest_arrays filled (TDT_COL_*: a host array of TDT_NCOL device
-// pointers).  The launch is enqueued on the context's stream and nothing is waited for — unless the reserve must ask or grow.
+// the two entries of a batch: ks_push_device / ks_push of tdt_keystore.h
 extern "C" int tdt_clip_push_device(tdt_clip *h, const void *const *d_arrays14, size_t n, size_t raw_len) {
-    tdt_batch B;
-    const int rc = tdt_batch_view("tdt_clip_push_device", h, d_arrays14, n, raw_len, CLIP_NEED, &B);
-    if (rc) return rc;
-    if (n == 0) return TDT_OK;
-    TDT_HIP(hipSetDevice(h->ctx->device));
-    return clip_launch(h, ClipIn{B.flag, B.tid, B.pos, B.mapq, B.rec_off, B.raw}, n, raw_len);
+    return ks_push_device("tdt_clip_push_device", h, d_arrays14, n, raw_len, clip_launch(h, n, raw_len));
 }
 
-// The same kernel on host columns and host record bytes (uploaded into the handle's own block).  The stream is synchronised before the
-// return: the caller's arrays are free again.
 extern "C" int tdt_clip_push(tdt_clip *h, const uint16_t *flag, const int32_t *tid, const int32_t *pos, const uint8_t *mapq, const uint64_t *rec_off, size_t n,
                              const uint8_t *raw, size_t raw_len) {
-    tdt_batch H{}, B;
-    H.flag = flag, H.tid = tid, H.pos = pos, H.mapq = mapq, H.rec_off = rec_off, H.raw = raw;
-    int rc = tdt_batch_host("tdt_clip_push", h, H, n, raw_len, CLIP_NEED);
-    if (rc == TDT_OK) rc = tdt_batch_offsets_ascend("tdt_clip_push", rec_off, n);
-    if (rc) return rc;
-    if (n == 0) return TDT_OK;
-    TDT_HIP(hipSetDevice(h->ctx->device));
-    rc = tdt_batch_upload("tdt_clip_push", h->ctx, &h->io, H, CLIP_NEED, n, raw_len, &B);
-    if (rc == TDT_OK) rc = clip_launch(h, ClipIn{B.flag, B.tid, B.pos, B.mapq, B.rec_off, B.raw}, n, raw_len);
-    if (rc) return rc;
-    TDT_HIP(hipStreamSynchronize(h->ctx->stream));
-    return TDT_OK;
+    return ks_push("tdt_clip_push", h, ks_cols{flag, tid, pos, mapq, rec_off, raw}, n, raw_len, clip_launch(h, n, raw_len));
 }
 
 extern "C" int tdt_clip_keys(tdt_clip *h, uint64_t *k1, uint64_t *k2, size_t *n) { return ks_keys(h ? &h->S : nullptr, "tdt_clip", k1, k2, n); }
@@ -533,25 +409,16 @@ static int clip_sites_of_rows(tdt_clip *h, size_t n_, unsigned min_support, ull 
 // sn_out: uint64[TDT_CLIP_SN_N], the push counters and the sequences and sites of everything pushed so far; *n_rows: the rows
 // tdt_clip_rows will give.  The store is left as it was.
 extern "C" int tdt_clip_finish(tdt_clip *h, uint64_t min_support, uint64_t *sn_out, size_t *n_rows) {
-    if (!h || !sn_out || !n_rows) {
-        tdt_set_error("tdt_clip_finish: bad argument");
-        return TDT_E_ARG;
-    }
-    if (min_support < 1 || min_support > TDT_CLIP_MAX_SUPPORT) {
-        tdt_set_error("tdt_clip_finish: min_support %llu (1 ... %d)", (ull)min_support, TDT_CLIP_MAX_SUPPORT);
-        return TDT_E_RANGE;
-    }
-    TDT_HIP(hipSetDevice(h->ctx->device));
-    ull state[KS_WORDS], seqs[2], sites[2];
-    int rc = ks_stored(&h->S, state);
-    if (rc == TDT_OK) rc = ks_finish(&h->S, state, 1, seqs);       // (a minimum support of 1: every distinct sequence is a row)
-    if (rc == TDT_OK) {
-        rc = clip_sites_of_rows(h, h->S.n_rows, (unsigned)min_support, sites);
-        if (rc) h->S.rows_valid = false;
-    }
-    if (rc) return rc;
     uint64_t res[SN_N] = {};
-    for (int k = 0; k < SN_PUSH_N; k++) res[k] = state[k];
+    ull seqs[2], sites[2];
+    // (a minimum support of 1 for the runs: every distinct sequence is a row)
+    int rc = ks_finish_counted(h ? &h->S : nullptr, "tdt_clip", h && sn_out && n_rows, min_support, TDT_CLIP_MAX_SUPPORT, 1, SN_PUSH_N, res, seqs);
+    if (rc) return rc;
+    rc = clip_sites_of_rows(h, h->S.n_rows, (unsigned)min_support, sites);
+    if (rc) {
+        h->S.rows_valid = false;
+        return rc;
+    }
     res[SN_DISTINCT_SEQS] = seqs[0];
     res[SN_DISTINCT_SITES] = sites[0];
     res[SN_REPORTED] = sites[1];
@@ -599,24 +466,11 @@ extern "C" int tdt_clip_rows(tdt_clip *h, uint64_t *k1, uint32_t *side, uint32_t
     return TDT_OK;
 }
 
-// device milliseconds of the last finish: [0] sort by K2, [1] gather of K1, [2] sort by K1, [3] gather of K2 + the run-length launches,
-// [4] the site launches (heads, vote, rows)
+// device milliseconds of the last finish: ks_timing's four, then [4] the site launches (heads, vote, rows)
 extern "C" int tdt_clip_timing(tdt_clip *h, double *ms5) {
-    if (!h || !ms5) {
-        tdt_set_error("tdt_clip_timing: bad argument");
-        return TDT_E_ARG;
-    }
-    for (int k = 0; k < 4; k++) ms5[k] = h->S.ms[k];
-    ms5[4] = h->ms_sites;
-    return TDT_OK;
+    const int rc = ks_timing(h ? &h->S : nullptr, "tdt_clip", ms5);
+    if (rc == TDT_OK) ms5[4] = h->ms_sites;
+    return rc;
 }
 
-// out3: how often the reserve asked the device for the real count, how often it made a bigger store, the store's capacity now
-extern "C" int tdt_clip_reserve_stats(tdt_clip *h, uint64_t *out3) {
-    if (!h || !out3) {
-        tdt_set_error("tdt_clip_reserve_stats: bad argument");
-        return TDT_E_ARG;
-    }
-    out3[0] = h->S.asks, out3[1] = h->S.grows, out3[2] = h->S.cap;
-    return TDT_OK;
-}
+extern "C" int tdt_clip_reserve_stats(tdt_clip *h, uint64_t *out3) { return ks_reserve_stats(h ? &h->S : nullptr, "tdt_clip", out3); }

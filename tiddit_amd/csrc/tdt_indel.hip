@@ -2,22 +2,18 @@
 // (TIDDIT_INDELS), with its support by strand.  The definition is tiddit_indels.py's: per keyed event K1 = tid << 32 | P and
 // K2 = type << 63 | len << 47 | kind << 45 | payload << 1 | rev; the sets of equal (K1, K2 >> 1) are the distinct events.  Every result
 // is an order-independent integer, so it equals the definition exactly.
-//   * indel_keys — ONE launch per batch, on the columns and record bytes that are already resident.  Lane = read for the filters (flag,
-//     tid, mapq: coalesced columns); the eligible reads are compacted inside the workgroup as dup_keys compacts its reads, then lane =
-//     compacted read: the record is bounded exactly as tdt_dup / tdt_qc / tdt_alleles bound one, its CIGAR is walked ONCE with the op in
-//     front and the op behind at hand (the flank test), and its at most INDEL_MAX_PER_READ keyed events stay in registers (P, len and
-//     type, the query offset: three words each).  A fifth keyed event is counted and not kept; the walk goes on to its end, because an op
-//     code above 8 or a P outside [1, 2^31) further on still makes the record malformed.  Malformed / noisy / ok is decided behind the
-//     walk: a read gives all of its events or none.  Only then are the inserted bases read (4-bit codes at the query offset the walk
-//     summed) — the first kernel here that emits a variable number of items per read.  A workgroup owns INDEL_K_TILE consecutive reads,
-//     INDEL_BLOCK at a time; a round's keys go behind the tile's earlier ones in LDS (slots by a prefix sum of the reads' event counts)
-//     and the tile's keys are appended to the store (two uint64 columns in HBM) behind ONE atomic.  The counters and the OR of the keys
-//     and of their complements are merged per wave and then over the workgroup: one atomic per workgroup and non-zero word.
-//     The host knows only an upper bound of the keys stored (INDEL_MAX_PER_READ per read): room for it is reserved BEFORE the launch,
-//     and a growth first asks the device for the real count (dup_reserve's policy).  The kernel still tests every slot against the
-//     capacity it was given and raises a flag instead of writing.
-//   * tdt_indel_finish — once per job: the two stable sorts, the gathers and the run-length launches of tdt_keystore.h (ks_finish),
-//     which the SNV store (tdt_snv.hip) shares; the store, its reserve and its read-outs are that header's too.
+//   * indel_keys — ONE launch per batch, on the columns and record bytes that are already resident.  The read gate (ks_read_gate), the
+//     record open (KS_OPEN) and the key emit (ks_stage, ks_flush) are tdt_keystore.h's, shared with snv_keys and clip_keys; what is
+//     this kernel's own: behind the gate lane = compacted read, the CIGAR is walked ONCE with the op in front and the op behind at
+//     hand (the flank test), and the at most INDEL_MAX_PER_READ keyed events stay in registers (P, len and type, the query offset:
+//     three words each).  A fifth keyed event is counted and not kept; the walk goes on to its end, because an op code above 8 or a P
+//     outside [1, 2^31) further on still makes the record malformed.  Malformed / noisy / ok is decided behind the walk: a read gives
+//     all of its events or none.  Only then are the inserted bases read (tdt_rec_base at the query offset the walk summed).  A
+//     workgroup owns INDEL_K_TILE consecutive reads, INDEL_BLOCK at a time: the gate and the stage run once per round, a round's keys
+//     go behind the tile's earlier ones in LDS, and ONE flush appends the tile's keys to the store.  NORM's three counters ride on the
+//     flush's barriers.  The host reserves INDEL_MAX_PER_READ slots per read BEFORE the launch (ks_launch).
+//   * tdt_indel_finish — once per job: the two stable sorts, the gathers and the run-length launches of tdt_keystore.h (ks_finish);
+//     the store, its reserve, the push path of the two entries and the read-outs are that header's too.
 #include <vector>
 
 #include "tdt_keystore.h"
@@ -29,7 +25,6 @@ typedef unsigned long long ull;
 #define INDEL_K_TILE 512                      // reads of an indel_keys workgroup; it stages at most 4 x that many keys in LDS (32 KB)
 #define INDEL_TILE 4096                       // keys of a run-length workgroup (KS_TILE of tdt_keystore.h)
 static_assert(INDEL_TILE == KS_TILE && INDEL_BLOCK == KS_BLOCK, "the run-length tile is the key store's");
-#define INDEL_MAX_CONTIGS (1 << 24)
 #define INDEL_P_LIMIT (1ll << 31)
 #define INDEL_NORM_MAX_SHIFT TDT_INDEL_NORM_MAX_SHIFT   // CAP: no event is shifted further left than this (64 word steps)
 #define INDEL_PACK_MAX 22                     // the longest insertion whose bases fit the 44-bit payload, two bits each
@@ -56,14 +51,6 @@ struct tdt_indel {
     tdt_batch_io io;                          // columns + raw bytes of the host entry
 };
 
-struct IndelIn {
-    const uint16_t *flag;
-    const int32_t *tid, *pos;
-    const uint8_t *mapq;
-    const uint64_t *rec_off;
-    const uint8_t *raw;
-};
-
 __device__ __forceinline__ bool indel_is_match(unsigned op) { return op == 0 || op == 7 || op == 8; }
 
 // K2 of an insertion of len bases at query offset q of a sequence of l_seq bases at raw[seq ...]
@@ -73,8 +60,7 @@ __device__ __forceinline__ ull indel_ins_key(const uint8_t *__restrict__ raw, ul
     ull h = 0xcbf29ce484222325ull, pack = 0;
     bool acgt = len <= INDEL_PACK_MAX;
     for (unsigned i = 0; i < len; i++) {
-        const unsigned at = q + i;
-        const unsigned b = (raw[seq + (at >> 1)] >> ((at & 1u) ? 0 : 4)) & 0xfu;
+        const unsigned b = tdt_rec_base(raw, seq, q + i);
         h = (h ^ (ull)b) * 0x100000001b3ull;
         const unsigned code = b == 1 ? 0u : b == 2 ? 1u : b == 4 ? 2u : 3u;
         acgt = acgt && (b == 1 || b == 2 || b == 4 || b == 8);
@@ -102,10 +88,7 @@ __device__ __forceinline__ unsigned indel_shift(const uint8_t *__restrict__ stor
             const unsigned m = lim - k < 16u ? lim - k : 16u;
             const ull x = tdt_ref_left16(store, g0 - k - 1ull);
             ull y = 0;
-            for (unsigned t = 0; t < m; t++) {
-                const unsigned at = q + n - 1u - k - t;
-                y |= (ull)((raw[seq + (at >> 1)] >> ((at & 1u) ? 0 : 4)) & 0xfu) << (4u * t);
-            }
+            for (unsigned t = 0; t < m; t++) y |= (ull)tdt_rec_base(raw, seq, q + n - 1u - k - t) << (4u * t);
             ull stop = (x ^ y) | tdt_ref_not_acgt(x);
             if (m < 16u) stop |= ~0ull << (4u * m);
             const unsigned run = stop ? (unsigned)__builtin_ctzll(stop) >> 2 : 16u;
@@ -131,8 +114,7 @@ __device__ __forceinline__ ull indel_ins_key_rotated(const uint8_t *__restrict__
     ull h = 0xcbf29ce484222325ull, pack = 0;
     bool acgt = len <= INDEL_PACK_MAX;
     for (unsigned i = 0; i < len; i++) {
-        const unsigned at = q + i - k;                             // (used where i >= k)
-        const unsigned b = i < k ? tdt_ref_code(store, off, (long long)p - k + i) : (raw[seq + (at >> 1)] >> ((at & 1u) ? 0 : 4)) & 0xfu;
+        const unsigned b = i < k ? tdt_ref_code(store, off, (long long)p - k + i) : tdt_rec_base(raw, seq, q + i - k);
         h = (h ^ (ull)b) * 0x100000001b3ull;
         const unsigned code = b == 1 ? 0u : b == 2 ? 1u : b == 4 ? 2u : 3u;
         acgt = acgt && (b == 1 || b == 2 || b == 4 || b == 8);
@@ -144,85 +126,64 @@ __device__ __forceinline__ ull indel_ins_key_rotated(const uint8_t *__restrict__
 
 // NORM false is the kernel of TIDDIT_INDELS alone; NORM true shifts a read's events between the walk and the keying (Rf: the reference)
 template <bool NORM>
-__global__ __launch_bounds__(INDEL_BLOCK) void indel_keys(IndelIn I, int n, ull raw_len, unsigned min_mapq, ull *__restrict__ k1s, ull *__restrict__ k2s,
+__global__ __launch_bounds__(INDEL_BLOCK) void indel_keys(ks_cols I, int n, ull raw_len, unsigned min_mapq, ull *__restrict__ k1s, ull *__restrict__ k2s,
                                                           ull cap, ull *__restrict__ st, tdt_refview Rf) {
     __shared__ ull s_k1[INDEL_K_TILE * TDT_INDEL_MAX_PER_READ], s_k2[INDEL_K_TILE * TDT_INDEL_MAX_PER_READ];   // the tile's keys, in the order they were made
-    __shared__ int s_read[INDEL_BLOCK];
-    __shared__ int s_wsum[INDEL_BLOCK / 64], s_wkeys[INDEL_BLOCK / 64];
-    __shared__ ull s_cnt[INDEL_BLOCK / 64][SN_PUSH_N + 4];        // per wave: the push counters, then the OR / NAND words
-    __shared__ ull s_base;
     __shared__ ull s_norm[NORM ? INDEL_BLOCK / 64 : 1][3];         // per wave: shifted, capped, off the reference
     ull nshift = 0, ncap = 0, noff = 0;                            // (this lane's)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const long long lo = (long long)blockIdx.x * INDEL_K_TILE, hi = lo + INDEL_K_TILE < n ? lo + INDEL_K_TILE : n;
     ull cnt[SN_PUSH_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0};             // (records .. noisy, reads_with_events: wave-uniform sums of ballots; the others: this lane's)
-    ull or1 = 0, nand1 = 0, or2 = 0, nand2 = 0;                   // (this lane's keys; merged over the wave at the end)
+    ks_masks M;
     int nk = 0;                                                   // keys of the tile so far (uniform over the workgroup)
     for (long long first = lo; first < hi; first += INDEL_BLOCK) {       // (uniform: the bounds are the workgroup's)
-        // ---- lane = read: the filters on the columns
-        const long long i = first + t;
-        bool elig = false;
-        if (i < hi) elig = (I.flag[i] & 0xF04u) == 0 && I.tid[i] >= 0 && (unsigned)I.mapq[i] >= min_mapq;
-        const ull m_rec = __ballot(i < hi), m_el = __ballot(elig);
-        cnt[SN_RECORDS] += (ull)__popcll(m_rec);
-        cnt[SN_ELIGIBLE] += (ull)__popcll(m_el);
-        const tdt_slots S = tdt_block_slots<INDEL_BLOCK / 64>(m_el, s_wsum, lane, wave);
-        if (elig) s_read[S.base + tdt_lane_rank(m_el, lane)] = (int)i;
-        __syncthreads();
-        // ---- lane = compacted read: bound the record, walk its CIGAR once
-        const bool live = t < S.total;
+        // ---- lane = read: the filters on the columns; then lane = compacted read: bound the record, walk its CIGAR once
+        const ks_gated G = ks_read_gate<INDEL_BLOCK>(I, first, hi, min_mapq, cnt[SN_RECORDS], cnt[SN_ELIGIBLE]);
+        const bool live = t < G.live;
         bool bad = live;
         unsigned ne = 0, un = 0, tl = 0;                           // keyed events seen (all of them), unanchored, too long
         unsigned eP[TDT_INDEL_MAX_PER_READ] = {0, 0, 0, 0}, eL[TDT_INDEL_MAX_PER_READ] = {0, 0, 0, 0}, eQ[TDT_INDEL_MAX_PER_READ] = {0, 0, 0, 0};
-        unsigned rev = 0;
-        int tid = 0, l_seq = 0;
+        int l_seq = 0;
         ull seq = 0;
+        ks_read A{};
         const uint8_t *__restrict__ raw = I.raw;
-        if (live) {
-            const int ri = s_read[t];
-            rev = ((unsigned)I.flag[ri] >> 4) & 1u;
-            tid = I.tid[ri];
-            const int pos = I.pos[ri];
-            const ull ro = I.rec_off[ri];
-            if (tid < INDEL_MAX_CONTIGS && pos >= 0 && TDT_REC_HEADER_INSIDE(raw_len, ro)) {
-                tdt_rec R = TDT_REC_READ(raw, ro);
-                l_seq = R.l_seq;
-                R.l_seq = l_seq < 0 ? 0 : l_seq;                   // (clamped: the body's sum never sees a negative length)
-                if (l_seq >= 0 && TDT_REC_FITS(R, raw_len)) {
-                    bad = false;
-                    seq = R.seq();
-                    const uint8_t *cig = raw + R.cig();
-                    long long r = pos, q = 0;
-                    unsigned prev = 9u;                            // (no op in front: no match code)
-                    unsigned cw = R.n_cig ? tdt_ld_u32(cig) : 0u;
-                    for (unsigned j = 0; j < R.n_cig; j++) {
-                        const bool has_next = j + 1 < R.n_cig;
-                        const unsigned nw = has_next ? tdt_ld_u32(cig + 4ull * (j + 1)) : 0u;
-                        const unsigned nop = has_next ? nw & 0xfu : 9u;
-                        const unsigned op = cw & 0xfu, len = cw >> 4;
-                        bad |= op > 8;
-                        if (op == 1 || op == 2) {
-                            if (!(indel_is_match(prev) && indel_is_match(nop)) || len == 0) {
-                                un++;
-                            } else if (len >= TDT_INDEL_MAX_LEN) {
-                                tl++;
-                            } else {
-                                bad |= r < 1 || r >= INDEL_P_LIMIT;
-                                const unsigned qs = q > 0x7fffffffll ? 0x7fffffffu : (unsigned)q;      // (saturated: such a span lies outside any l_seq)
+        if (live && KS_OPEN(A, I, G.read, raw_len)) {
+            const tdt_rec &R = A.R;
+            bad = false;
+            l_seq = R.l_seq;
+            seq = R.seq();
+            const uint8_t *cig = raw + R.cig();
+            long long r = A.pos, q = 0;
+            unsigned prev = 9u;                                    // (no op in front: no match code)
+            unsigned cw = R.n_cig ? tdt_ld_u32(cig) : 0u;
+            for (unsigned j = 0; j < R.n_cig; j++) {
+                const bool has_next = j + 1 < R.n_cig;
+                const unsigned nw = has_next ? tdt_ld_u32(cig + 4ull * (j + 1)) : 0u;
+                const unsigned nop = has_next ? nw & 0xfu : 9u;
+                const unsigned op = cw & 0xfu, len = cw >> 4;
+                bad |= op > 8;
+                if (op == 1 || op == 2) {
+                    if (!(indel_is_match(prev) && indel_is_match(nop)) || len == 0) {
+                        un++;
+                    } else if (len >= TDT_INDEL_MAX_LEN) {
+                        tl++;
+                    } else {
+                        bad |= r < 1 || r >= INDEL_P_LIMIT;
+                        const unsigned qs = q > 0x7fffffffll ? 0x7fffffffu : (unsigned)q;      // (saturated: such a span lies outside any l_seq)
 #pragma unroll
-                                for (int k = 0; k < TDT_INDEL_MAX_PER_READ; k++)
-                                    if (ne == (unsigned)k) eP[k] = (unsigned)r, eL[k] = (len << 1) | (op == 1 ? 1u : 0u), eQ[k] = qs;
-                                ne++;
-                            }
-                        }
-                        r += (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? (long long)len : 0;
-                        q += (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) ? (long long)len : 0;
-                        prev = op;
-                        cw = nw;
+                        for (int k = 0; k < TDT_INDEL_MAX_PER_READ; k++)
+                            if (ne == (unsigned)k) eP[k] = (unsigned)r, eL[k] = (len << 1) | (op == 1 ? 1u : 0u), eQ[k] = qs;
+                        ne++;
                     }
                 }
+                r += tdt_cig_on_ref(op) ? (long long)len : 0;
+                q += tdt_cig_on_query(op) ? (long long)len : 0;
+                prev = op;
+                cw = nw;
             }
         }
+        const int tid = A.tid;
+        const unsigned rev = A.rev;
         const bool walked = live && !bad, noisy = walked && ne > TDT_INDEL_MAX_PER_READ, ok = walked && !noisy;
         cnt[SN_MALFORMED] += (ull)__popcll(__ballot(live && bad));
         cnt[SN_NOISY] += (ull)__popcll(__ballot(noisy));
@@ -254,23 +215,10 @@ __global__ __launch_bounds__(INDEL_BLOCK) void indel_keys(IndelIn I, int n, ull 
                 }
             }
         }
-        // ---- the round's keys behind the tile's earlier ones, in LDS: slots by a prefix sum of the reads' event counts
+        // ---- the round's keys behind the tile's earlier ones, in LDS
         const int mine = ok ? (int)ne : 0;
-        int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(incl, o);
-            if (lane >= o) incl += u;
-        }
-        if (lane == 63) s_wkeys[wave] = incl;
-        __syncthreads();
-        int base = nk, total = 0;
-#pragma unroll
-        for (int w = 0; w < INDEL_BLOCK / 64; w++) {
-            base += w < wave ? s_wkeys[w] : 0;
-            total += s_wkeys[w];
-        }
-        int slot = base + incl - mine;                             // (+ mine <= nk + total <= 4 x the reads of the tile so far)
+        int total;
+        const int slot = nk + ks_stage<INDEL_BLOCK>(mine, &total);      // (+ mine <= nk + total <= 4 x the reads of the tile so far)
 #pragma unroll
         for (int k = 0; k < TDT_INDEL_MAX_PER_READ; k++) {
             if (k < mine) {
@@ -285,53 +233,22 @@ __global__ __launch_bounds__(INDEL_BLOCK) void indel_keys(IndelIn I, int n, ull 
                     k2 = ((ull)len << 47) | rev;
                     cnt[SN_DELETIONS]++;
                 }
-                or1 |= k1, nand1 |= ~k1, or2 |= k2, nand2 |= ~k2;
+                M.add(k1, k2);
                 s_k1[slot + k] = k1;
                 s_k2[slot + k] = k2;
             }
         }
         nk += total;
     }
-    // ---- the tile's counters: merged per wave, then over the workgroup, ONE atomic per non-zero counter
+    // ---- the lane sums over the wave, then the emit (tdt_keystore.h); NORM's three counters ride on its barriers
     cnt[SN_UNANCHORED] = tdt_wave_reduce<tdt_sum>(cnt[SN_UNANCHORED]), cnt[SN_TOO_LONG] = tdt_wave_reduce<tdt_sum>(cnt[SN_TOO_LONG]);
     cnt[SN_INSERTIONS] = tdt_wave_reduce<tdt_sum>(cnt[SN_INSERTIONS]), cnt[SN_DELETIONS] = tdt_wave_reduce<tdt_sum>(cnt[SN_DELETIONS]);
-    or1 = tdt_wave_reduce<tdt_or>(or1), nand1 = tdt_wave_reduce<tdt_or>(nand1), or2 = tdt_wave_reduce<tdt_or>(or2), nand2 = tdt_wave_reduce<tdt_or>(nand2);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < SN_PUSH_N; k++) s_cnt[wave][k] = cnt[k];
-        s_cnt[wave][SN_PUSH_N] = or1, s_cnt[wave][SN_PUSH_N + 1] = nand1, s_cnt[wave][SN_PUSH_N + 2] = or2, s_cnt[wave][SN_PUSH_N + 3] = nand2;
-    }
     if constexpr (NORM) {
         nshift = tdt_wave_reduce<tdt_sum>(nshift), ncap = tdt_wave_reduce<tdt_sum>(ncap), noff = tdt_wave_reduce<tdt_sum>(noff);
         if (lane == 0) s_norm[wave][0] = nshift, s_norm[wave][1] = ncap, s_norm[wave][2] = noff;
     }
-    __syncthreads();
-    if constexpr (NORM) {
-        if (t >= 64 && t < 64 + 3) {                               // (a wave the push counters' atomics leave idle)
-            ull v = 0;
-            for (int w = 0; w < INDEL_BLOCK / 64; w++) v += s_norm[w][t - 64];
-            if (v) atomicAdd(&st[ST_SHIFTED + (t - 64)], v);
-        }
-    }
-    if (t == 0) s_base = nk ? atomicAdd(&st[ST_N], (ull)nk) : 0ull;        // the workgroup's slots of the store behind ONE atomic
-    if (t < SN_PUSH_N + 4) {
-        ull v = 0;
-        for (int w = 0; w < INDEL_BLOCK / 64; w++) v = t < SN_PUSH_N ? v + s_cnt[w][t] : v | s_cnt[w][t];
-        if (v) {
-            if (t < SN_PUSH_N) atomicAdd(&st[t], v);
-            else atomicOr(&st[ST_OR1 + (t - SN_PUSH_N)], v);
-        }
-    }
-    __syncthreads();
-    for (int k = t; k < nk; k += INDEL_BLOCK) {                    // (consecutive lanes, consecutive slots)
-        const ull slot = s_base + (ull)k;
-        if (slot < cap) {
-            k1s[slot] = s_k1[k];
-            k2s[slot] = s_k2[k];
-        } else {
-            st[ST_OVERFLOW] = 1;                                   // (cannot happen: the host reserved 4 slots for every read of the batch)
-        }
-    }
+    ks_flush<INDEL_BLOCK, SN_PUSH_N>(cnt, M, nk, s_k1, s_k2, k1s, k2s, cap, st);
+    if constexpr (NORM) ks_flush_extra<INDEL_BLOCK, 3>(s_norm, st, ST_SHIFTED);
 }
 
 // ---- the handle: the store, its reserve and the finish are tdt_keystore.h's
@@ -348,7 +265,7 @@ extern "C" int tdt_indel_create(tdt_ctx *ctx, int n_contigs, int min_mapq, size_
         tdt_set_error("tdt_indel_create: bad argument");
         return TDT_E_ARG;
     }
-    if (n_contigs > INDEL_MAX_CONTIGS || min_mapq < 0 || min_mapq > 255 || capacity >= (1ull << 40)) {
+    if (!ks_create_in_range(n_contigs, min_mapq, capacity)) {
         tdt_set_error("tdt_indel_create: %d contigs (at most 2^24), min_mapq %d (0 ... 255), capacity %zu", n_contigs, min_mapq, capacity);
         return TDT_E_RANGE;
     }
@@ -366,68 +283,33 @@ extern "C" int tdt_indel_create(tdt_ctx *ctx, int n_contigs, int min_mapq, size_
     return TDT_OK;
 }
 
-extern "C" int tdt_indel_destroy(tdt_indel *h) {
-    if (!h) return TDT_OK;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);        // (no kernel of the stream still writes the store)
-    indel_free(h);
-    return TDT_OK;
+extern "C" int tdt_indel_destroy(tdt_indel *h) { return ks_destroy(h, indel_free); }
+
+extern "C" int tdt_indel_reset(tdt_indel *h) { return ks_reset_checked(h ? &h->S : nullptr, "tdt_indel"); }
+
+// the launch of one batch: TDT_INDEL_MAX_PER_READ slots of the store per read, the bound a read's cap gives
+static auto indel_launch(tdt_indel *h, size_t n, size_t raw_len) {
+    return [=](const ks_cols &I) {
+        return ks_launch(&h->S, n * TDT_INDEL_MAX_PER_READ, [&] {
+            const dim3 grid((unsigned)((n + INDEL_K_TILE - 1) / INDEL_K_TILE));
+            if (h->ref)
+                hipLaunchKernelGGL(indel_keys<true>, grid, dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, h->S.k1, h->S.k2,
+                                   (ull)h->S.cap, h->S.d_state, tdt_refview{h->ref->d_store, h->ref->d_off, h->ref->d_len, h->ref->n_contigs});
+            else
+                hipLaunchKernelGGL(indel_keys<false>, grid, dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, h->S.k1, h->S.k2,
+                                   (ull)h->S.cap, h->S.d_state, tdt_refview{nullptr, nullptr, nullptr, 0});
+        });
+    };
 }
 
-extern "C" int tdt_indel_reset(tdt_indel *h) {
-    if (!h) {
-        tdt_set_error("tdt_indel_reset: bad argument");
-        return TDT_E_ARG;
-    }
-    return ks_reset(&h->S);
-}
-
-static int indel_launch(tdt_indel *h, const IndelIn &I, size_t n, size_t raw_len) {
-    const size_t room = n * TDT_INDEL_MAX_PER_READ;                // the bound a read's cap gives
-    int rc = ks_reserve(&h->S, room);
-    if (rc) return rc;
-    const dim3 grid((unsigned)((n + INDEL_K_TILE - 1) / INDEL_K_TILE));
-    if (h->ref)
-        hipLaunchKernelGGL(indel_keys<true>, grid, dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, h->S.k1, h->S.k2,
-                           (ull)h->S.cap, h->S.d_state, tdt_refview{h->ref->d_store, h->ref->d_off, h->ref->d_len, h->ref->n_contigs});
-    else
-        hipLaunchKernelGGL(indel_keys<false>, grid, dim3(INDEL_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, h->S.k1, h->S.k2,
-                           (ull)h->S.cap, h->S.d_state, tdt_refview{nullptr, nullptr, nullptr, 0});
-    TDT_CHECK_LAUNCH();
-    h->S.upper += room;
-    h->S.rows_valid = false;
-    return TDT_OK;
-}
-
-#define INDEL_NEED (TDT_NEED(FLAG) | TDT_NEED(TID) | TDT_NEED(POS) | TDT_NEED(MAPQ) | TDT_NEED(REC_OFF) | TDT_NEED(RAW))
-
-// One batch of the device ingest: d_arrays14 = the pointer table tdt_ingest_arrays filled (TDT_COL_*: a host array of TDT_NCOL device
-// pointers).  The launch is enqueued on the context's stream and nothing is waited for — unless the reserve must ask or grow.
+// the two entries of a batch: ks_push_device / ks_push of tdt_keystore.h
 extern "C" int tdt_indel_push_device(tdt_indel *h, const void *const *d_arrays14, size_t n, size_t raw_len) {
-    tdt_batch B;
-    const int rc = tdt_batch_view("tdt_indel_push_device", h, d_arrays14, n, raw_len, INDEL_NEED, &B);
-    if (rc) return rc;
-    if (n == 0) return TDT_OK;
-    TDT_HIP(hipSetDevice(h->ctx->device));
-    return indel_launch(h, IndelIn{B.flag, B.tid, B.pos, B.mapq, B.rec_off, B.raw}, n, raw_len);
+    return ks_push_device("tdt_indel_push_device", h, d_arrays14, n, raw_len, indel_launch(h, n, raw_len));
 }
 
-// The same kernel on host columns and host record bytes (uploaded into the handle's own block).  The stream is synchronised before the
-// return: the caller's arrays are free again.
 extern "C" int tdt_indel_push(tdt_indel *h, const uint16_t *flag, const int32_t *tid, const int32_t *pos, const uint8_t *mapq, const uint64_t *rec_off,
                               size_t n, const uint8_t *raw, size_t raw_len) {
-    tdt_batch H{}, B;
-    H.flag = flag, H.tid = tid, H.pos = pos, H.mapq = mapq, H.rec_off = rec_off, H.raw = raw;
-    int rc = tdt_batch_host("tdt_indel_push", h, H, n, raw_len, INDEL_NEED);
-    if (rc == TDT_OK) rc = tdt_batch_offsets_ascend("tdt_indel_push", rec_off, n);
-    if (rc) return rc;
-    if (n == 0) return TDT_OK;
-    TDT_HIP(hipSetDevice(h->ctx->device));
-    rc = tdt_batch_upload("tdt_indel_push", h->ctx, &h->io, H, INDEL_NEED, n, raw_len, &B);
-    if (rc == TDT_OK) rc = indel_launch(h, IndelIn{B.flag, B.tid, B.pos, B.mapq, B.rec_off, B.raw}, n, raw_len);
-    if (rc) return rc;
-    TDT_HIP(hipStreamSynchronize(h->ctx->stream));
-    return TDT_OK;
+    return ks_push("tdt_indel_push", h, ks_cols{flag, tid, pos, mapq, rec_off, raw}, n, raw_len, indel_launch(h, n, raw_len));
 }
 
 // The store read out, in the order it lies in HBM.  On entry *n = the room of the two arrays (ignored when both are NULL: the call then
@@ -437,21 +319,10 @@ extern "C" int tdt_indel_keys(tdt_indel *h, uint64_t *k1, uint64_t *k2, size_t *
 // sn_out: uint64[TDT_INDEL_SN_N], the push counters and the sets of everything pushed so far; *n_rows: the rows tdt_indel_rows will
 // give.  The store is left as it was.
 extern "C" int tdt_indel_finish(tdt_indel *h, uint64_t min_support, uint64_t *sn_out, size_t *n_rows) {
-    if (!h || !sn_out || !n_rows) {
-        tdt_set_error("tdt_indel_finish: bad argument");
-        return TDT_E_ARG;
-    }
-    if (min_support < 1 || min_support > TDT_INDEL_MAX_SUPPORT) {
-        tdt_set_error("tdt_indel_finish: min_support %llu (1 ... %d)", (ull)min_support, TDT_INDEL_MAX_SUPPORT);
-        return TDT_E_RANGE;
-    }
-    TDT_HIP(hipSetDevice(h->ctx->device));
-    ull state[ST_WORDS], got[2];
-    int rc = ks_stored(&h->S, state);
-    if (rc == TDT_OK) rc = ks_finish(&h->S, state, min_support, got);
-    if (rc) return rc;
     uint64_t res[SN_N] = {};
-    for (int k = 0; k < SN_PUSH_N; k++) res[k] = state[k];
+    ull got[2];
+    const int rc = ks_finish_counted(h ? &h->S : nullptr, "tdt_indel", h && sn_out && n_rows, min_support, TDT_INDEL_MAX_SUPPORT, min_support, SN_PUSH_N, res, got);
+    if (rc) return rc;
     res[SN_DISTINCT] = got[0];
     res[SN_REPORTED] = got[1];
     memcpy(sn_out, res, sizeof res);
@@ -465,25 +336,9 @@ extern "C" int tdt_indel_rows(tdt_indel *h, uint64_t *k1, uint64_t *k2, uint32_t
     return ks_rows(h ? &h->S : nullptr, "tdt_indel", k1, k2, support, rev, n);
 }
 
-// device milliseconds of the last finish: [0] sort by K2, [1] gather of K1, [2] sort by K1, [3] gather of K2 + the run-length launches
-extern "C" int tdt_indel_timing(tdt_indel *h, double *ms4) {
-    if (!h || !ms4) {
-        tdt_set_error("tdt_indel_timing: bad argument");
-        return TDT_E_ARG;
-    }
-    for (int k = 0; k < 4; k++) ms4[k] = h->S.ms[k];
-    return TDT_OK;
-}
+extern "C" int tdt_indel_timing(tdt_indel *h, double *ms4) { return ks_timing(h ? &h->S : nullptr, "tdt_indel", ms4); }
 
-// out3: how often the reserve asked the device for the real count, how often it made a bigger store, the store's capacity now
-extern "C" int tdt_indel_reserve_stats(tdt_indel *h, uint64_t *out3) {
-    if (!h || !out3) {
-        tdt_set_error("tdt_indel_reserve_stats: bad argument");
-        return TDT_E_ARG;
-    }
-    out3[0] = h->S.asks, out3[1] = h->S.grows, out3[2] = h->S.cap;
-    return TDT_OK;
-}
+extern "C" int tdt_indel_reserve_stats(tdt_indel *h, uint64_t *out3) { return ks_reserve_stats(h ? &h->S : nullptr, "tdt_indel", out3); }
 
 // The reference the pushes from here on normalise against (tdt_refseq.hip; it must outlive the handle or be detached first, and lie on
 // the handle's device); NULL detaches it: the keys are again what they are without one.  The store and the counters stay as they are.

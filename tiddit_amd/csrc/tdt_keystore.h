@@ -1,9 +1,13 @@
-// A store of (K1, K2) keys in HBM and its finish, written once for the consumers of the --sv scan that key events and count the sets of
-// equal keys (tdt_indel.hip, tdt_snv.hip; each translation unit instantiates its own copy: everything here has internal linkage).
+// A store of (K1, K2) keys in HBM, the push into it and its finish, written once for the consumers of the --sv scan that key events and
+// count the sets of equal keys (tdt_indel.hip, tdt_snv.hip, tdt_clip.hip; each translation unit instantiates its own copy: everything here
+// has internal linkage).
 //   * the store: two uint64 columns of `cap` entries and a state line of KS_WORDS words — the consumer's push counters in front, the OR
 //     of the keys and of their complements at or1 ... or1 + 3 (K1, ~K1, K2, ~K2), the number of keys stored at KS_N in a cache line of its
 //     own, the overflow flag at KS_OVERFLOW.  The host knows only an upper bound of the keys stored: ks_reserve makes room BEFORE a launch,
 //     and a growth first asks the device for the real count (dup_reserve's policy).
+//   * the push — device side: the read gate (ks_read_gate), the record open (KS_OPEN) and the key emit (ks_stage, ks_flush), which write
+//     the state line laid out here; host side: ks_launch round a consumer's launch, ks_push_device / ks_push for its two entries, and the
+//     small entries of a handle (ks_finish_counted, ks_timing, ks_reserve_stats, ks_reset_checked, ks_destroy).
 //   * ks_finish — once per job: the LSD sort of tdt_dup_finish (sort (K2, index); gather K1; sort (K1[perm], perm), stable; gather K2),
 //     then the runs of equal (K1, K2 >> 1) in plain launches, none of whose workgroups waits for another: ks_tile_heads notes each
 //     tile's last run head and last FULL-key head (a change of (K1, K2), bit 0 included), ks_carry (one workgroup) carries both across
@@ -73,6 +77,140 @@ template <class Op> __device__ __forceinline__ int ks_block_scan(int v, int none
     __syncthreads();
     *total = all;
     return v;
+}
+
+// ---- the push side: what every *_keys kernel does in front of and behind its own walk of a record
+#define KS_MAX_CONTIGS (1 << 24)              // K1 = tid << 32 | P: a tid of 2^24 or more is malformed
+
+struct ks_cols {                              // the kernel argument: the six columns of a batch a keyed consumer reads (device pointers)
+    const uint16_t *flag;
+    const int32_t *tid, *pos;
+    const uint8_t *mapq;
+    const uint64_t *rec_off;
+    const uint8_t *raw;
+};
+#define KS_NEED (TDT_NEED(FLAG) | TDT_NEED(TID) | TDT_NEED(POS) | TDT_NEED(MAPQ) | TDT_NEED(REC_OFF) | TDT_NEED(RAW))
+static inline ks_cols ks_cols_of(const tdt_batch &B) { return ks_cols{B.flag, B.tid, B.pos, B.mapq, B.rec_off, B.raw}; }
+
+// THE READ GATE, lane = read: reads [first, first + BLOCK) below hi pass the filters on the coalesced columns (flag, tid, mapq), the
+// two ballots ADD to records / eligible (wave-uniform), and the eligible reads are compacted into s_read in thread order.  Called by
+// every thread; two barriers inside (tdt_block_slots' and the one behind the writes of s_read).  -> live: the eligible reads of the
+// workgroup; thread t < live owns read `read`.  (The LDS of the gate, the stage and the flush is their own: BLOCK + 2 * BLOCK / 64
+// ints, BLOCK / 64 * (NCNT + 4) + 1 words.)
+struct ks_gated { int live, read; };
+template <int BLOCK>
+__device__ __forceinline__ ks_gated ks_read_gate(const ks_cols &I, long long first, long long hi, unsigned min_mapq, ks_ull &records, ks_ull &eligible) {
+    __shared__ int s_read[BLOCK], s_wsum[BLOCK / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const long long i = first + t;
+    bool elig = false;
+    if (i < hi) elig = (I.flag[i] & 0xF04u) == 0 && I.tid[i] >= 0 && (unsigned)I.mapq[i] >= min_mapq;
+    const ks_ull m_rec = __ballot(i < hi), m_el = __ballot(elig);
+    records += (ks_ull)__popcll(m_rec);
+    eligible += (ks_ull)__popcll(m_el);
+    const tdt_slots S = tdt_block_slots<BLOCK / 64>(m_el, s_wsum, lane, wave);
+    if (elig) s_read[S.base + tdt_lane_rank(m_el, lane)] = (int)i;
+    __syncthreads();
+    return ks_gated{S.total, t < S.total ? s_read[t] : 0};
+}
+
+// THE RECORD OPEN behind the gate, for a live lane: rev, tid and pos from the columns, then the record bounded with TDT_REC_*.  true:
+// tid < 2^24, pos >= 0, the header inside raw, l_seq >= 0 and the body fits — A.R is the record.  false: malformed, A.R is not to be
+// used.  A MACRO for the reason written above TDT_REC_*: as a __forceinline__ function its `&&` reaches the caller as selects, and
+// indel_keys<false> was 2 % slower on the one batch of the bench file where it is slowest (profiles/keyed_emit_240mb.md).
+struct ks_read {
+    tdt_rec R;
+    int tid, pos;
+    unsigned rev;
+};
+#define KS_OPEN(A, I, ri, raw_len)                                                                                                       \
+    ((A).rev = ((unsigned)(I).flag[ri] >> 4) & 1u, (A).tid = (I).tid[ri], (A).pos = (I).pos[ri], (A).R.ro = (I).rec_off[ri],              \
+     (A).tid < KS_MAX_CONTIGS && (A).pos >= 0 && TDT_REC_HEADER_INSIDE(raw_len, (A).R.ro) &&                                             \
+         ((A).R = TDT_REC_READ((I).raw, (A).R.ro), (A).R.l_seq >= 0 && TDT_REC_FITS((A).R, raw_len)))
+
+// THE KEY EMIT of a workgroup of BLOCK threads with NCNT push counters, which lie in front of the state line with the OR / NAND words
+// behind them (tdt_keystore::or1 == NCNT).  The consumer keeps what is its own: which counters are ballots and which lane sums, and
+// how a key is built.  It stages its keys in LDS of its own (s_k1 / s_k2) at the slots ks_stage hands out, ORs them into a ks_masks, and ends
+// with ks_flush.
+struct ks_masks {                                                  // the OR of this lane's keys and of their complements (the sort masks)
+    ks_ull or1 = 0, nand1 = 0, or2 = 0, nand2 = 0;
+    __device__ __forceinline__ void add(ks_ull k1, ks_ull k2) { or1 |= k1, nand1 |= ~k1, or2 |= k2, nand2 |= ~k2; }
+};
+
+// STAGE: each lane's key count `mine` -> its first slot among the workgroup's keys of this call, in thread order; *total = all of
+// them (uniform).  Called by every thread; ONE barrier inside.
+template <int BLOCK> __device__ __forceinline__ int ks_stage(int mine, int *total) {
+    __shared__ int s_wkeys[BLOCK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(incl, o);
+        if (lane >= o) incl += u;
+    }
+    if (lane == 63) s_wkeys[wave] = incl;
+    __syncthreads();
+    int base = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; w++) {
+        base += w < wave ? s_wkeys[w] : 0;
+        all += s_wkeys[w];
+    }
+    *total = all;
+    return base + incl - mine;
+}
+
+// FLUSH: cnt[] = this wave's push counters (wave-uniform: the consumer reduced its lane sums), M = this lane's masks, nk = the staged
+// keys (uniform over the workgroup).  The masks are merged over the wave, the waves' rows over the workgroup: ONE atomic per workgroup
+// and non-zero word (add for a counter, OR for a mask), ONE atomicAdd on KS_N for the workgroup's slots of the store, then the append —
+// every slot is tested against the capacity, and a slot beyond it raises KS_OVERFLOW instead of being written (cannot happen: the
+// host reserved the per-read cap for every read of the batch).  Called by every thread; two barriers inside.
+template <int BLOCK, int NCNT>
+__device__ __forceinline__ void ks_flush(const ks_ull (&cnt)[NCNT], ks_masks M, int nk, const ks_ull *s_k1, const ks_ull *s_k2, ks_ull *__restrict__ k1s,
+                                         ks_ull *__restrict__ k2s, ks_ull cap, ks_ull *__restrict__ st) {
+    static_assert(NCNT + 4 <= KS_N && NCNT + 4 <= BLOCK, "state layout");
+    __shared__ ks_ull s_cnt[BLOCK / 64][NCNT + 4];                  // per wave: the push counters, then the OR / NAND words
+    __shared__ ks_ull s_base;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    M.or1 = tdt_wave_reduce<tdt_or>(M.or1), M.nand1 = tdt_wave_reduce<tdt_or>(M.nand1);
+    M.or2 = tdt_wave_reduce<tdt_or>(M.or2), M.nand2 = tdt_wave_reduce<tdt_or>(M.nand2);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NCNT; k++) s_cnt[wave][k] = cnt[k];
+        s_cnt[wave][NCNT] = M.or1, s_cnt[wave][NCNT + 1] = M.nand1, s_cnt[wave][NCNT + 2] = M.or2, s_cnt[wave][NCNT + 3] = M.nand2;
+    }
+    __syncthreads();
+    if (t == 0) s_base = nk ? atomicAdd(&st[KS_N], (ks_ull)nk) : 0ull;
+    if (t < NCNT + 4) {
+        ks_ull v = 0;
+        for (int w = 0; w < BLOCK / 64; w++) v = t < NCNT ? v + s_cnt[w][t] : v | s_cnt[w][t];
+        if (v) {
+            if (t < NCNT) atomicAdd(&st[t], v);
+            else atomicOr(&st[t], v);
+        }
+    }
+    __syncthreads();
+    for (int k = t; k < nk; k += BLOCK) {                          // (consecutive lanes, consecutive slots)
+        const ks_ull at = s_base + (ks_ull)k;
+        if (at < cap) {
+            k1s[at] = s_k1[k];
+            k2s[at] = s_k2[k];
+        } else {
+            st[KS_OVERFLOW] = 1;
+        }
+    }
+}
+
+// NX further counters of a consumer at st[at ...] (below KS_N), per wave in s_x: written before ks_flush and added behind it, so its
+// barriers stand between.  One atomic per non-zero word, from a wave the push counters' atomics leave idle.
+template <int BLOCK, int NX> __device__ __forceinline__ void ks_flush_extra(const ks_ull (&s_x)[BLOCK / 64][NX], ks_ull *__restrict__ st, int at) {
+    static_assert(BLOCK >= 128 && NX <= 64, "the second wave");
+    const int t = threadIdx.x;
+    if (t >= 64 && t < 64 + NX) {
+        ks_ull v = 0;
+        for (int w = 0; w < BLOCK / 64; w++) v += s_x[w][t - 64];
+        if (v) atomicAdd(&st[at + (t - 64)], v);
+    }
 }
 
 // a run head: the first key, or a key whose (K1, K2 >> 1) differs from the one in front of it; a full head: (K1, K2) differs
@@ -453,6 +591,111 @@ int ks_rows(tdt_keystore *h, const char *name, uint64_t *k1, uint64_t *k2, uint3
         }
     }
     *n = have;
+    return TDT_OK;
+}
+
+// ---- the push path and the small entries of a consumer's handle H: H has `ctx`, the store `S` and the host entry's block `io`.  A
+// handle may be NULL wherever the C entry refuses one; `name` is the consumer's prefix ("tdt_indel"), `fn` a whole entry name.
+
+// around a consumer's launch: room for the `room` keys the batch can give at most is reserved BEFORE it; behind it the bound grows
+// and the rows of an earlier finish are gone.  launch(): enqueues the kernel (it reads S->k1, S->k2, S->cap only now)
+template <class Launch> int ks_launch(tdt_keystore *S, size_t room, Launch launch) {
+    const int rc = ks_reserve(S, room);
+    if (rc) return rc;
+    launch();
+    TDT_CHECK_LAUNCH();
+    S->upper += room;
+    S->rows_valid = false;
+    return TDT_OK;
+}
+
+// One batch of the device ingest: table = the pointer table tdt_ingest_arrays filled (TDT_COL_*: a host array of TDT_NCOL device
+// pointers).  launch(I) is the consumer's ks_launch on the columns I; it is enqueued on the context's stream and nothing is waited
+// for — unless the reserve must ask or grow.
+template <class H, class Launch> int ks_push_device(const char *fn, H *h, const void *const *table, size_t n, size_t raw_len, Launch launch) {
+    tdt_batch B;
+    const int rc = tdt_batch_view(fn, h, table, n, raw_len, KS_NEED, &B);
+    if (rc) return rc;
+    if (n == 0) return TDT_OK;
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    return launch(ks_cols_of(B));
+}
+
+// The same kernel on host columns and host record bytes (C: the caller's HOST pointers), uploaded into the handle's own block.  The
+// stream is synchronised before the return: the caller's arrays are free again.
+template <class H, class Launch> int ks_push(const char *fn, H *h, const ks_cols &C, size_t n, size_t raw_len, Launch launch) {
+    tdt_batch host{}, B;
+    host.flag = C.flag, host.tid = C.tid, host.pos = C.pos, host.mapq = C.mapq, host.rec_off = C.rec_off, host.raw = C.raw;
+    int rc = tdt_batch_host(fn, h, host, n, raw_len, KS_NEED);
+    if (rc == TDT_OK) rc = tdt_batch_offsets_ascend(fn, C.rec_off, n);
+    if (rc) return rc;
+    if (n == 0) return TDT_OK;
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    rc = tdt_batch_upload(fn, h->ctx, &h->io, host, KS_NEED, n, raw_len, &B);
+    if (rc == TDT_OK) rc = launch(ks_cols_of(B));
+    if (rc) return rc;
+    TDT_HIP(hipStreamSynchronize(h->ctx->stream));
+    return TDT_OK;
+}
+
+// what every create checks behind its arguments (the error text is the consumer's: its own parameters stand in the middle of it)
+bool ks_create_in_range(int n_contigs, int min_mapq, size_t capacity) {
+    return n_contigs <= KS_MAX_CONTIGS && min_mapq >= 0 && min_mapq <= 255 && capacity < (1ull << 40);
+}
+
+// The front of every finish: ok = the entry's pointer arguments are there; min_support in 1 ... max_support; then the state line and
+// ks_finish with `run_support`.  res[0, push_n) = the push counters (the SN rows' first), got = what ks_finish counted.
+int ks_finish_counted(tdt_keystore *S, const char *name, bool ok, uint64_t min_support, int max_support, uint64_t run_support, int push_n, uint64_t *res,
+                      ks_ull *got) {
+    if (!ok) {
+        tdt_set_error("%s_finish: bad argument", name);
+        return TDT_E_ARG;
+    }
+    if (min_support < 1 || min_support > (uint64_t)max_support) {
+        tdt_set_error("%s_finish: min_support %llu (1 ... %d)", name, (ks_ull)min_support, max_support);
+        return TDT_E_RANGE;
+    }
+    TDT_HIP(hipSetDevice(S->ctx->device));
+    ks_ull state[KS_WORDS];
+    int rc = ks_stored(S, state);
+    if (rc == TDT_OK) rc = ks_finish(S, state, run_support, got);
+    if (rc) return rc;
+    for (int k = 0; k < push_n; k++) res[k] = state[k];
+    return TDT_OK;
+}
+
+int ks_reset_checked(tdt_keystore *S, const char *name) {
+    if (S) return ks_reset(S);
+    tdt_set_error("%s_reset: bad argument", name);
+    return TDT_E_ARG;
+}
+
+// device milliseconds of the last finish: [0] sort by K2, [1] gather of K1, [2] sort by K1, [3] gather of K2 + the run-length launches
+int ks_timing(const tdt_keystore *S, const char *name, double *ms4) {
+    if (!S || !ms4) {
+        tdt_set_error("%s_timing: bad argument", name);
+        return TDT_E_ARG;
+    }
+    for (int k = 0; k < 4; k++) ms4[k] = S->ms[k];
+    return TDT_OK;
+}
+
+// out3: how often the reserve asked the device for the real count, how often it made a bigger store, the store's capacity now
+int ks_reserve_stats(const tdt_keystore *S, const char *name, uint64_t *out3) {
+    if (!S || !out3) {
+        tdt_set_error("%s_reserve_stats: bad argument", name);
+        return TDT_E_ARG;
+    }
+    out3[0] = S->asks, out3[1] = S->grows, out3[2] = S->cap;
+    return TDT_OK;
+}
+
+// the stream is drained (no kernel of it still writes the store), then free_(h) frees the store, the block and the handle
+template <class H> int ks_destroy(H *h, void (*free_)(H *)) {
+    if (!h) return TDT_OK;
+    (void)hipSetDevice(h->ctx->device);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    free_(h);
     return TDT_OK;
 }
 

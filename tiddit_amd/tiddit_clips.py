@@ -50,13 +50,13 @@ NOT built: the clip's full length, or more than 28 bases of it; joining the site
 alone is no clip, and the bases it removed are not in the record); supplementary records (0x800 is not eligible); N ranks (refused in
 ``__main__.run_sv``: a site's keys can straddle shards).
 """
-import ctypes
 import struct
 import time
 
 import numpy
 
-from . import _native, bamio
+from .bamio import _raw_of
+from .keyed_counter import KeyedCounter
 
 CLIP_COLS = 28
 CLIP_MAX_PER_READ = 2
@@ -157,10 +157,6 @@ def events_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq=DEFAULT_MAPQ, mi
     return OK, keys, short, cut
 
 
-def _raw_of(b):
-    return b.raw if isinstance(b.raw, (bytes, bytearray)) else memoryview(numpy.ascontiguousarray(b.raw, dtype=numpy.uint8))
-
-
 def _count(sn, kind, keys, short, cut):
     add = lambda k, n: sn.__setitem__(k, sn.get(k, 0) + n) if n else None
     add("records", 1)
@@ -232,81 +228,16 @@ def consensus_text(side, clen, cons):
 
 
 # ------------------------------------------------------------------------------------------- the device handle
-class ClipCounter:
-    """``tdt_clip_*``: the key store and the counters in HBM; one push per batch of the scan, one finish per job"""
+class ClipCounter(KeyedCounter):
+    """``tdt_clip_*``: the key store and the counters in HBM; one push per batch of the scan, one finish per job (one sort of the store
+    and the vote over its rows).  ``rows()``: (K1 uint64[], side, SUPPORT, REV, SEQS, CLEN uint32[], consensus, AGREE, TOTAL uint64[]) of
+    the last finish, ascending by (K1, side); ``timing()``: the key store's four and [4] site heads + vote + site rows."""
+    PREFIX, SIZE, DEFAULT_SUPPORT = "tdt_clip", SIZE, DEFAULT_SUPPORT
+    ROW_DTYPES, N_TIMES = ROW_DTYPES, 5
 
     def __init__(self, n_contigs, min_mapq=DEFAULT_MAPQ, min_clip=DEFAULT_CLIP, capacity=1 << 20, ctx=None):
-        self.ctx = ctx or _native.default_context()
-        assert self.ctx.lib.tdt_clip_sn_size() == SIZE
-        h = ctypes.c_void_p()
-        _native.check(self.ctx.lib.tdt_clip_create(self.ctx.handle, int(n_contigs), int(min_mapq), int(min_clip), int(capacity), ctypes.byref(h)))
-        self.handle = h
+        self._create(ctx, int(n_contigs), int(min_mapq), int(min_clip), int(capacity))
         self.min_mapq, self.min_clip = int(min_mapq), int(min_clip)
-        self._n_rows = 0
-
-    def push_device_batch(self, b):
-        """one DeviceBatch: enqueued on the reader's stream; nothing is waited for unless the reserve must ask or grow (call before the
-        batch's buffers are handed on)"""
-        _native.check(self.ctx.lib.tdt_clip_push_device(self.handle, b.pointer_table(), len(b), b._raw_len))
-
-    def push_host_batch(self, b):
-        """one host-decoded batch (or any object with its columns): uploaded, then the same kernel"""
-        cols, raw = bamio.host_columns(b, ("flag", "tid", "pos", "mapq", "rec_off"))            # (the arguments of tdt_clip_push, in order)
-        _native.check(self.ctx.lib.tdt_clip_push(self.handle, *[_native.ptr(c) for c in cols], len(cols[0]), _native.ptr(raw), len(raw)))
-
-    def keys(self):
-        """-> (K1 uint64[], K2 uint64[]): the store as it lies in HBM (its order is not the file's)"""
-        n = ctypes.c_size_t(0)
-        _native.check(self.ctx.lib.tdt_clip_keys(self.handle, None, None, ctypes.byref(n)))
-        k1, k2 = numpy.zeros(n.value, dtype=numpy.uint64), numpy.zeros(n.value, dtype=numpy.uint64)
-        if n.value:
-            _native.check(self.ctx.lib.tdt_clip_keys(self.handle, _native.ptr(k1), _native.ptr(k2), ctypes.byref(n)))
-        return k1, k2
-
-    def finish(self, min_support=DEFAULT_SUPPORT):
-        """-> uint64[SIZE]: the push counters and, from one sort of the store and the vote over its rows, the sites (the store is left
-        as it was)"""
-        out = numpy.zeros(SIZE, dtype=numpy.uint64)
-        n = ctypes.c_size_t(0)
-        _native.check(self.ctx.lib.tdt_clip_finish(self.handle, int(min_support), _native.ptr(out), ctypes.byref(n)))
-        self._n_rows = n.value
-        return out
-
-    def rows(self):
-        """-> (K1 uint64[], side, SUPPORT, REV, SEQS, CLEN uint32[], consensus, AGREE, TOTAL uint64[]) of the last finish, ascending by
-        (K1, side)"""
-        n = ctypes.c_size_t(self._n_rows)
-        cols = [numpy.zeros(n.value, dtype=dt) for dt in ROW_DTYPES]
-        if n.value:
-            _native.check(self.ctx.lib.tdt_clip_rows(self.handle, *[_native.ptr(c) for c in cols], ctypes.byref(n)))
-        return tuple(cols)
-
-    def timing(self):
-        """ms of the last finish: [sort by K2, gather, sort by K1, run lengths + rows, site heads + vote + site rows]"""
-        out = numpy.zeros(5, dtype=numpy.float64)
-        _native.check(self.ctx.lib.tdt_clip_timing(self.handle, _native.ptr(out)))
-        return out
-
-    def reserve_stats(self):
-        """-> (how often the reserve asked the device for the real count, how often the store grew, its capacity now)"""
-        out = numpy.zeros(3, dtype=numpy.uint64)
-        _native.check(self.ctx.lib.tdt_clip_reserve_stats(self.handle, _native.ptr(out)))
-        return tuple(int(v) for v in out)
-
-    def reset(self):
-        _native.check(self.ctx.lib.tdt_clip_reset(self.handle))
-        self._n_rows = 0
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.lib.tdt_clip_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ------------------------------------------------------------------------------------------- the file

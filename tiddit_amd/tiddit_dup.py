@@ -61,6 +61,7 @@ import time
 import numpy
 
 from . import _native, bamio
+from .bamio import _raw_of
 
 DUP_BIAS = 1 << 28
 DUP_HIST_MAX = 1024
@@ -197,10 +198,6 @@ def key_of_read(flag, tid, pos, end, mate_tid, mate_pos, rec_off, raw):
     if not 0 <= ME < E_LIMIT:
         return bad
     return PAIR, k1, PAIR_BIT | mate_tid << 34 | ME << 1 | mrev, marked, 1 if mc is None else 0
-
-
-def _raw_of(b):
-    return b.raw if isinstance(b.raw, (bytes, bytearray)) else memoryview(numpy.ascontiguousarray(b.raw, dtype=numpy.uint8))
 
 
 def keys_of_batch_by_read(b, keys, sn):

@@ -49,13 +49,13 @@ NOT built: an exact per-site depth or reference count in this file (``COV`` is a
 the exact counts), filters near indels or read ends, MNVs (two neighbouring mismatches are two rows), genotypes, a VCF, N ranks
 (refused in ``__main__.run_sv``: a set of equal keys can straddle shards), long-read libraries (the cap of 8).
 """
-import ctypes
 import struct
 import time
 
 import numpy
 
-from . import _native, bamio
+from .bamio import _raw_of
+from .keyed_counter import KeyedCounter
 
 SNV_MAX_PER_READ = 8
 SNV_MAX_CONTIGS = 1 << 24
@@ -155,10 +155,6 @@ def events_of_read(flag, tid, pos, mapq, rec_off, raw, ref, min_mapq=DEFAULT_MAP
     return OK, keys, aligned, low
 
 
-def _raw_of(b):
-    return b.raw if isinstance(b.raw, (bytes, bytearray)) else memoryview(numpy.ascontiguousarray(b.raw, dtype=numpy.uint8))
-
-
 def _count(sn, kind, keys, aligned, low):
     add = lambda k, n: sn.__setitem__(k, sn.get(k, 0) + n) if n else None
     add("records", 1)
@@ -205,83 +201,15 @@ def summarise(keys, sn=None, min_support=DEFAULT_SUPPORT):
 
 
 # ------------------------------------------------------------------------------------------- the device handle
-class SnvCounter:
+class SnvCounter(KeyedCounter):
     """``tdt_snv_*``: the key store and the counters in HBM; one push per batch of the scan, one finish per job.  ``reference``: a
-    refseq.RefSeq on the same context (kept alive by this object)."""
+    refseq.RefSeq on the same context (kept alive by this object until ``close``)."""
+    PREFIX, SIZE, DEFAULT_SUPPORT = "tdt_snv", SIZE, DEFAULT_SUPPORT
 
     def __init__(self, n_contigs, reference, min_mapq=DEFAULT_MAPQ, min_bq=DEFAULT_BQ, capacity=1 << 20, ctx=None):
-        self.ctx = ctx or _native.default_context()
-        assert self.ctx.lib.tdt_snv_sn_size() == SIZE
-        h = ctypes.c_void_p()
-        _native.check(self.ctx.lib.tdt_snv_create(self.ctx.handle, int(n_contigs), int(min_mapq), int(min_bq), int(capacity), reference.handle, ctypes.byref(h)))
-        self.handle = h
+        self._create(ctx, int(n_contigs), int(min_mapq), int(min_bq), int(capacity), reference.handle)
         self.min_mapq, self.min_bq = int(min_mapq), int(min_bq)
-        self._n_rows = 0
         self.reference = reference
-
-    def push_device_batch(self, b):
-        """one DeviceBatch: enqueued on the reader's stream; nothing is waited for unless the reserve must ask or grow (call before the
-        batch's buffers are handed on)"""
-        _native.check(self.ctx.lib.tdt_snv_push_device(self.handle, b.pointer_table(), len(b), b._raw_len))
-
-    def push_host_batch(self, b):
-        """one host-decoded batch (or any object with its columns): uploaded, then the same kernel"""
-        cols, raw = bamio.host_columns(b, ("flag", "tid", "pos", "mapq", "rec_off"))            # (the arguments of tdt_snv_push, in order)
-        _native.check(self.ctx.lib.tdt_snv_push(self.handle, *[_native.ptr(c) for c in cols], len(cols[0]), _native.ptr(raw), len(raw)))
-
-    def keys(self):
-        """-> (K1 uint64[], K2 uint64[]): the store as it lies in HBM (its order is not the file's)"""
-        n = ctypes.c_size_t(0)
-        _native.check(self.ctx.lib.tdt_snv_keys(self.handle, None, None, ctypes.byref(n)))
-        k1, k2 = numpy.zeros(n.value, dtype=numpy.uint64), numpy.zeros(n.value, dtype=numpy.uint64)
-        if n.value:
-            _native.check(self.ctx.lib.tdt_snv_keys(self.handle, _native.ptr(k1), _native.ptr(k2), ctypes.byref(n)))
-        return k1, k2
-
-    def finish(self, min_support=DEFAULT_SUPPORT):
-        """-> uint64[SIZE]: the push counters and, from one sort of the store, the sets (the store is left as it was)"""
-        out = numpy.zeros(SIZE, dtype=numpy.uint64)
-        n = ctypes.c_size_t(0)
-        _native.check(self.ctx.lib.tdt_snv_finish(self.handle, int(min_support), _native.ptr(out), ctypes.byref(n)))
-        self._n_rows = n.value
-        return out
-
-    def rows(self):
-        """-> (K1 uint64[], K2 uint64[] with bit 0 clear, SUPPORT uint32[], REV uint32[]) of the last finish, ascending by key"""
-        n = ctypes.c_size_t(self._n_rows)
-        k1, k2 = numpy.zeros(n.value, dtype=numpy.uint64), numpy.zeros(n.value, dtype=numpy.uint64)
-        sup, rev = numpy.zeros(n.value, dtype=numpy.uint32), numpy.zeros(n.value, dtype=numpy.uint32)
-        if n.value:
-            _native.check(self.ctx.lib.tdt_snv_rows(self.handle, _native.ptr(k1), _native.ptr(k2), _native.ptr(sup), _native.ptr(rev), ctypes.byref(n)))
-        return k1, k2, sup, rev
-
-    def timing(self):
-        """ms of the last finish: [sort by K2, gather, sort by K1, run lengths + rows]"""
-        out = numpy.zeros(4, dtype=numpy.float64)
-        _native.check(self.ctx.lib.tdt_snv_timing(self.handle, _native.ptr(out)))
-        return out
-
-    def reserve_stats(self):
-        """-> (how often the reserve asked the device for the real count, how often the store grew, its capacity now)"""
-        out = numpy.zeros(3, dtype=numpy.uint64)
-        _native.check(self.ctx.lib.tdt_snv_reserve_stats(self.handle, _native.ptr(out)))
-        return tuple(int(v) for v in out)
-
-    def reset(self):
-        _native.check(self.ctx.lib.tdt_snv_reset(self.handle))
-        self._n_rows = 0
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.lib.tdt_snv_destroy(self.handle)
-            self.handle = None
-            self.reference = None                               # (only now: the handle's last kernel is done)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ------------------------------------------------------------------------------------------- the file
