@@ -907,6 +907,36 @@ int tdt_clip_timing(tdt_clip *h, double *ms5);
 int tdt_clip_reserve_stats(tdt_clip *h, uint64_t *out3);
 size_t tdt_clip_sn_size(void);
 
+/* ---- clip-site consensus realigned to the reference (TIDDIT_CLIPS_ALIGN) ---------------------------------- *
+ * For every clip site (K1 = tid << 32 | P, side 0 = L / 1 = R, CLEN, the consensus packed as tdt_clip_rows gives it) the best exact
+ * placement of its CLEN consensus bases on the same contig of a tdt_refseq within W bases of P, on either strand
+ * (csrc/tdt_clip_align.hip); the definition is tiddit_amd/tiddit_clip_align.py's.  Per site five uint32: status (0 short_consensus:
+ * CLEN < K; 1 off_reference: the contig is outside the table or not loaded, or P outside 1 ... len; 2 searched), PARTNER (the best
+ * candidate's Q, 1-based), strand (0 forward, 1 reverse complement), its mismatches, and HITS (the candidates with at most M
+ * mismatches).  The best candidate is the minimum of (mismatches, |Q - P|, strand, Q); a searched site without any candidate, and a
+ * site that is not searched, has PARTNER 0, strand 0, mismatches 0xffffffff and HITS 0.  A CLEN above TDT_CLIP_COLS is taken as
+ * TDT_CLIP_COLS, of the side only bit 0.  tdt_clip_align_sites takes host arrays of n sites, tdt_clip_align_sites_device caller-owned
+ * device arrays; both return when the kernel is done.  tdt_clip_align searches the rows of the handle's last tdt_clip_finish where they
+ * lie in HBM, keeps the five columns on the device for tdt_clip_align_rows (*n in: room of the arrays, out: rows; all five NULL: the
+ * count alone) and fills sn_out[TDT_CLIP_ALIGN_SN_N]:
+ *   [0] sites  [1] short_consensus  [2] off_reference  [3] searched  [4] aligned  [5] ambiguous  [6] unaligned  [7] ref  [8] del
+ *   [9] dup  [10] inv  [11] mated (always 0 here: mates are the host's, rule 5 of the definition)
+ * tdt_clip_align_timing: device milliseconds of the last tdt_clip_align's kernel.  The reference is not owned and must lie on the
+ * context's device.  Refusals: TDT_E_ARG (null pointers, n >= 2^31, a reference of another device, for the handle a reference with
+ * another contig count, tdt_clip_align without a finish since the last push or reset, tdt_clip_align_rows / _timing without a
+ * tdt_clip_align since then), TDT_E_RANGE (W outside 1 ... TDT_CLIP_ALIGN_MAX_WINDOW, K outside 1 ... TDT_CLIP_COLS, M outside
+ * 0 ... TDT_CLIP_COLS - 1, too little room in tdt_clip_align_rows); a refused call leaves its outputs untouched. */
+#define TDT_CLIP_ALIGN_SN_N 12
+#define TDT_CLIP_ALIGN_MAX_WINDOW (1 << 20)
+int tdt_clip_align_sites(tdt_ctx *ctx, tdt_refseq *ref, size_t n, const uint64_t *k1, const uint32_t *side, const uint32_t *clen, const uint64_t *consensus,
+                         int W, int K, int M, uint32_t *status_out, uint32_t *partner_out, uint32_t *strand_out, uint32_t *mm_out, uint32_t *hits_out);
+int tdt_clip_align_sites_device(tdt_ctx *ctx, tdt_refseq *ref, size_t n, const uint64_t *d_k1, const uint32_t *d_side, const uint32_t *d_clen,
+                                const uint64_t *d_consensus, int W, int K, int M, uint32_t *d_status, uint32_t *d_partner, uint32_t *d_strand,
+                                uint32_t *d_mm, uint32_t *d_hits);
+int tdt_clip_align(tdt_clip *h, tdt_refseq *ref, int W, int K, int M, uint64_t *sn_out);
+int tdt_clip_align_rows(tdt_clip *h, uint32_t *status, uint32_t *partner, uint32_t *strand, uint32_t *mm, uint32_t *hits, size_t *n);
+int tdt_clip_align_timing(tdt_clip *h, double *ms);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

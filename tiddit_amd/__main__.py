@@ -72,6 +72,17 @@ the same side, with the support by strand, a consensus of up to 28 clipped bases
 bin (tiddit_amd/tiddit_clips.py has the definition and the file's format), from a key store the scan fills in HBM, one sort and a vote
 per site behind it.  Unset or empty is off; a value that is none of the four forms ends the job with an error before the scan.  One
 process only, refused on N ranks like ``TIDDIT_INDELS``.
+
+``TIDDIT_CLIPS_ALIGN=1`` (window 10000, minimum consensus columns 20, maximum mismatches 2), ``TIDDIT_CLIPS_ALIGN=W``, ``W:K`` or
+``W:K:M`` (valid only together with ``TIDDIT_CLIPS``): ``--sv`` also writes ``{o}.clips.align.tab`` — for every reported clip site whose
+consensus has at least ``K`` columns, the best exact placement of that consensus on the same contig within ``W`` bases of the
+breakpoint, on either strand, with its mismatches (at most ``M`` for an accepted one), the number of acceptable placements, the event
+the junction implies (DEL / DUP / INV and its length, base-pair exact) and the opposite-side site that tells the same event with the
+microhomology between the two (tiddit_amd/tiddit_clip_align.py has the definition and the file's format).  The reference FASTA is packed
+into HBM before the scan (once, shared with ``TIDDIT_INDELS_NORM`` / ``TIDDIT_SNVS``) and one kernel searches it behind the clip stage's
+finish, on the site rows where they lie.  ``{o}.clips.tab`` and every other output are what they are without the switch.  Unset or
+empty is off; the switch without ``TIDDIT_CLIPS``, a value that is none of the four forms, or a contig of the BAM header that the FASTA
+lacks or holds at another length, ends the job with an error before the scan.
 """
 import argparse
 import os
@@ -316,6 +327,13 @@ def run_sv(args, version):
         # (the same)
         print("error, TIDDIT_CLIPS={}: {}".format(os.environ.get("TIDDIT_CLIPS"), e))
         sys.exit(1)
+    try:
+        from . import tiddit_clip_align
+        clips_align = tiddit_clip_align.parse_switch(os.environ.get("TIDDIT_CLIPS_ALIGN"), clips is not None)
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_CLIPS_ALIGN={}: {}".format(os.environ.get("TIDDIT_CLIPS_ALIGN"), e))
+        sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
     if genotype_depth and sites_path is None:
@@ -351,9 +369,9 @@ def run_sv(args, version):
     contig_number = {c: i for i, c in enumerate(contigs)}
     contig_length = {c["SN"]: c["LN"] for c in bam_header["SQ"]}
     prefix = args.o
-    if indels_norm or snvs is not None:
-        # TIDDIT_INDELS_NORM / TIDDIT_SNVS: the contigs of the BAM header are matched to the FASTA's by name now — one that is missing or
-        # has another length ends the job before anything is made
+    if indels_norm or snvs is not None or clips_align is not None:
+        # TIDDIT_INDELS_NORM / TIDDIT_SNVS / TIDDIT_CLIPS_ALIGN: the contigs of the BAM header are matched to the FASTA's by name now — one
+        # that is missing or has another length ends the job before anything is made
         from . import refseq
         norm_fasta = FastaFile(args.ref)
         try:
@@ -361,8 +379,10 @@ def run_sv(args, version):
         except ValueError as e:
             if indels_norm:
                 print("error, TIDDIT_INDELS_NORM=1: {}".format(e))
-            else:
+            elif snvs is not None:
                 print("error, TIDDIT_SNVS={}: {}".format(os.environ.get("TIDDIT_SNVS"), e))
+            else:
+                print("error, TIDDIT_CLIPS_ALIGN={}: {}".format(os.environ.get("TIDDIT_CLIPS_ALIGN"), e))
             sys.exit(1)
     allele_sites = None
     if alleles is not None:
@@ -570,13 +590,14 @@ def run_sv(args, version):
     if indels is not None:
         # TIDDIT_INDELS: ... and a key per small indel of the reads' CIGARs, one launch per batch
         tiddit_signal.INDELS = indels
-    if indels_norm or snvs is not None:
-        # TIDDIT_INDELS_NORM / TIDDIT_SNVS: the reference goes into HBM before the scan (every contig of the BAM header: read, uploaded,
-        # packed to 4-bit codes), ONCE: the indel kernel moves every event as far left as it allows, the SNV kernel compares every
-        # aligned base with it, and both hold the same handle
+    if indels_norm or snvs is not None or clips_align is not None:
+        # TIDDIT_INDELS_NORM / TIDDIT_SNVS / TIDDIT_CLIPS_ALIGN: the reference goes into HBM before the scan (every contig of the BAM
+        # header: read, uploaded, packed to 4-bit codes), ONCE: the indel kernel moves every event as far left as it allows, the SNV
+        # kernel compares every aligned base with it, the clip stage searches it for the sites' consensus, and all hold the same handle
         t_ref = time.time()
         reference, t_read, t_load = refseq.load_for_bam(norm_fasta, chromosomes, [contig_length[c] for c in chromosomes])
-        T["reference into HBM (%s)" % " + ".join(k for k, on in (("TIDDIT_INDELS_NORM", indels_norm), ("TIDDIT_SNVS", snvs is not None)) if on)] = time.time() - t_ref
+        T["reference into HBM (%s)" % " + ".join(k for k, on in (("TIDDIT_INDELS_NORM", indels_norm), ("TIDDIT_SNVS", snvs is not None),
+                                                                  ("TIDDIT_CLIPS_ALIGN", clips_align is not None)) if on)] = time.time() - t_ref
         T["  reference: file read (host)"] = t_read
         T["  reference: upload + ref_pack (returns when packed)"] = t_load
         if indels_norm:
@@ -662,9 +683,16 @@ def run_sv(args, version):
         # (the same)
         counter, tiddit_signal.CLIP_COUNTER = tiddit_signal.CLIP_COUNTER, None
         t = time.time()
-        tiddit_clips.main(counter, prefix, coverage_data, chromosomes, clips[0])
+        try:
+            # TIDDIT_CLIPS_ALIGN: ... and the sites' consensus is searched in the reference, behind the finish, where the rows lie
+            tiddit_clips.main(counter, prefix, coverage_data, chromosomes, clips[0], None if clips_align is None else (reference,) + clips_align)
+        finally:
+            if clips_align is not None and not indels_norm and snvs is None:
+                reference.close()                     # (only this switch loaded it)
         T["clip sites ({o}.clips.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_clips.STAGE_SECONDS.items()})
+        if clips_align is not None:
+            T.update({"  " + k: v for k, v in tiddit_clip_align.STAGE_SECONDS.items()})
         STAGE_NOTES.update(tiddit_clips.STAGE_NOTES)
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,

@@ -32,6 +32,7 @@
 //         key order.
 #include <vector>
 
+#include "tdt_clip_align.h"
 #include "tdt_keystore.h"
 
 typedef unsigned long long ull;
@@ -74,6 +75,11 @@ struct tdt_clip {
     size_t n_rows;
     hipEvent_t ev[2];
     double ms_sites;
+    void *d_align;                            // tdt_clip_align's five columns and counters (grows)
+    size_t align_cap;
+    ca_out align;                             // ... of the last tdt_clip_align (inside d_align), n_rows of them; valid while the rows are
+    bool align_valid;
+    double ms_align;
 };
 
 __global__ __launch_bounds__(CLIP_BLOCK) void clip_keys(ks_cols I, int n, ull raw_len, unsigned min_mapq, unsigned min_clip, ull *__restrict__ k1s,
@@ -267,6 +273,7 @@ static void clip_free(tdt_clip *h) {
     ks_free(&h->S);
     if (h->io.d) (void)hipFree(h->io.d);
     if (h->d_site) (void)hipFree(h->d_site);
+    if (h->d_align) (void)hipFree(h->d_align);
     for (int k = 0; k < 2; k++)
         if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     delete h;
@@ -310,7 +317,7 @@ extern "C" int tdt_clip_create(tdt_ctx *ctx, int n_contigs, int min_mapq, int mi
 extern "C" int tdt_clip_destroy(tdt_clip *h) { return ks_destroy(h, clip_free); }
 
 extern "C" int tdt_clip_reset(tdt_clip *h) {
-    if (h) h->n_rows = 0;
+    if (h) h->n_rows = 0, h->align_valid = false;
     return ks_reset_checked(h ? &h->S : nullptr, "tdt_clip");
 }
 
@@ -322,7 +329,7 @@ static auto clip_launch(tdt_clip *h, size_t n, size_t raw_len) {
             hipLaunchKernelGGL(clip_keys, grid, dim3(CLIP_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, (unsigned)h->min_clip,
                                h->S.k1, h->S.k2, (ull)h->S.cap, h->S.d_state);
         });
-        if (rc == TDT_OK) h->n_rows = 0;
+        if (rc == TDT_OK) h->n_rows = 0, h->align_valid = false;
         return rc;
     };
 }
@@ -357,6 +364,7 @@ static int clip_sites_of_rows(tdt_clip *h, size_t n_, unsigned min_support, ull 
     got[0] = got[1] = 0;
     h->ms_sites = 0;
     h->n_rows = 0;
+    h->align_valid = false;
     if (!n_) return TDT_OK;
     const int n = (int)n_;                                         // (< 2^30: ks_finish refused more)
     const size_t ntiles = (n_ + KS_TILE - 1) / KS_TILE;
@@ -474,3 +482,110 @@ extern "C" int tdt_clip_timing(tdt_clip *h, double *ms5) {
 }
 
 extern "C" int tdt_clip_reserve_stats(tdt_clip *h, uint64_t *out3) { return ks_reserve_stats(h ? &h->S : nullptr, "tdt_clip", out3); }
+
+// ---- the rows of the last finish realigned to the reference (csrc/tdt_clip_align.hip), where they lie: no round trip
+struct clip_align_work {
+    ca_out O;
+    size_t lay(void *base, size_t n) {
+        tdt_carver cv(base);
+        O.status = cv.take<unsigned>(n), O.partner = cv.take<unsigned>(n), O.strand = cv.take<unsigned>(n), O.mm = cv.take<unsigned>(n);
+        O.hits = cv.take<unsigned>(n), O.sn = cv.take<ull>(TDT_CLIP_ALIGN_SN_N);
+        return cv.size;
+    }
+};
+
+// sn_out: uint64[TDT_CLIP_ALIGN_SN_N].  No finish since the last push or reset, or a reference with another contig count: TDT_E_ARG.
+extern "C" int tdt_clip_align(tdt_clip *h, tdt_refseq *ref, int W, int K, int M, uint64_t *sn_out) {
+    if (!h || !ref || !sn_out || ref->ctx->device != h->ctx->device) {
+        tdt_set_error("tdt_clip_align: bad argument");
+        return TDT_E_ARG;
+    }
+    if (!h->S.rows_valid) {
+        tdt_set_error("tdt_clip_align: no finish since the last push or reset");
+        return TDT_E_ARG;
+    }
+    if (ref->n_contigs != h->n_contigs) {
+        tdt_set_error("tdt_clip_align: the reference has %d contigs, the handle was made for %d", ref->n_contigs, h->n_contigs);
+        return TDT_E_ARG;
+    }
+    int rc = ca_check_range("tdt_clip_align", W, K, M);
+    if (rc) return rc;
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    h->align_valid = false;
+    h->ms_align = 0;
+    const size_t n = h->n_rows;
+    clip_align_work A;
+    const size_t bytes = A.lay(nullptr, n);
+    if (bytes > h->align_cap) {
+        if (h->d_align) TDT_HIP(hipFree(h->d_align));
+        h->d_align = nullptr;
+        h->align_cap = 0;
+        if (tdt_dev_malloc(&h->d_align, bytes) != hipSuccess) {
+            tdt_set_error("tdt_clip_align: out of device memory (%zu rows)", n);
+            return TDT_E_NOMEM;
+        }
+        h->align_cap = bytes;
+    }
+    A.lay(h->d_align, n);
+    hipStream_t st = h->ctx->stream;
+    uint64_t res[TDT_CLIP_ALIGN_SN_N] = {};
+    TDT_HIP(hipMemsetAsync(A.O.sn, 0, sizeof res, st));
+    TDT_HIP(hipEventRecord(h->ev[0], st));
+    const clip_sites &R = h->rows;
+    rc = ca_launch(h->ctx, ref, n, ca_sites{R.k1, R.side, R.clen, R.cons}, W, K, M, A.O);
+    if (rc) return rc;
+    TDT_HIP(hipEventRecord(h->ev[1], st));
+    TDT_HIP(hipMemcpyAsync(res, A.O.sn, sizeof res, hipMemcpyDeviceToHost, st));
+    rc = tdt_ctx_sync(h->ctx);
+    if (rc) return rc;
+    float ms = 0;
+    TDT_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    h->ms_align = ms;
+    h->align = A.O;
+    h->align_valid = true;
+    memcpy(sn_out, res, sizeof res);
+    return TDT_OK;
+}
+
+// The five columns of the last tdt_clip_align, in the order of tdt_clip_rows.  *n in: the room of the arrays (ignored when all five are
+// NULL), out: the rows.  Too little room: TDT_E_RANGE, nothing written.
+extern "C" int tdt_clip_align_rows(tdt_clip *h, uint32_t *status, uint32_t *partner, uint32_t *strand, uint32_t *mm, uint32_t *hits, size_t *n) {
+    const bool any = status || partner || strand || mm || hits;
+    if (!h || !n || (any && !(status && partner && strand && mm && hits))) {
+        tdt_set_error("tdt_clip_align_rows: bad argument");
+        return TDT_E_ARG;
+    }
+    if (!h->S.rows_valid || !h->align_valid) {
+        tdt_set_error("tdt_clip_align_rows: no tdt_clip_align since the last push, reset or finish");
+        return TDT_E_ARG;
+    }
+    const size_t have = h->n_rows;
+    if (any) {
+        if (*n < have) {
+            tdt_set_error("tdt_clip_align_rows: room for %zu rows, %zu kept", *n, have);
+            return TDT_E_RANGE;
+        }
+        if (have) {
+            TDT_HIP(hipSetDevice(h->ctx->device));
+            hipStream_t st = h->ctx->stream;
+            const ca_out &O = h->align;
+            TDT_HIP(hipMemcpyAsync(status, O.status, have * 4, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipMemcpyAsync(partner, O.partner, have * 4, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipMemcpyAsync(strand, O.strand, have * 4, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipMemcpyAsync(mm, O.mm, have * 4, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipMemcpyAsync(hits, O.hits, have * 4, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipStreamSynchronize(st));
+        }
+    }
+    *n = have;
+    return TDT_OK;
+}
+
+extern "C" int tdt_clip_align_timing(tdt_clip *h, double *ms) {
+    if (!h || !ms || !h->S.rows_valid || !h->align_valid) {
+        tdt_set_error("tdt_clip_align_timing: bad argument, or no tdt_clip_align since the last push, reset or finish");
+        return TDT_E_ARG;
+    }
+    *ms = h->ms_align;
+    return TDT_OK;
+}

@@ -46,9 +46,12 @@ so the columns of an ``L`` site are reversed, and is ``.`` when ``CLEN`` is 0; `
 ``coverage_data[chrom][(P - 1) // 50]``, ``.`` when the job holds no bins for that contig (or none that far), as
 ``tiddit_snvs.write_file`` writes it.
 
-NOT built: the clip's full length, or more than 28 bases of it; joining the sites to the SV candidates or the VCF; hard clips (``H``
-alone is no clip, and the bases it removed are not in the record); supplementary records (0x800 is not eligible); N ranks (refused in
-``__main__.run_sv``: a site's keys can straddle shards).
+Where the clipped bases come from is tiddit_clip_align.py's (``TIDDIT_CLIPS_ALIGN``): the consensus placed on the same contig, and the
+DEL / DUP / INV the junction implies.
+
+NOT built: the clip's full length, or more than 28 bases of it; joining the sites to the VCF; hard clips (``H`` alone is no clip, and
+the bases it removed are not in the record); supplementary records (0x800 is not eligible); N ranks (refused in ``__main__.run_sv``: a
+site's keys can straddle shards).
 """
 import struct
 import time
@@ -267,8 +270,10 @@ def summary_line(counts):
                                         "malformed")))
 
 
-def main(counter, prefix, coverage_data, names, S):
-    """the stage behind the scan: the sort, the run lengths and the vote on the device, the file and the summary line"""
+def main(counter, prefix, coverage_data, names, S, align=None):
+    """the stage behind the scan: the sort, the run lengths and the vote on the device, the file and the summary line.  ``align``:
+    None, or (reference, W, K, M) of ``TIDDIT_CLIPS_ALIGN`` — the rows are then realigned where they lie, behind the finish and before
+    the counter is closed (tiddit_clip_align.main, which writes ``{o}.clips.align.tab``); the reference is not closed here"""
     STAGE_SECONDS.clear()
     STAGE_NOTES.clear()
     t = time.time()
@@ -277,6 +282,16 @@ def main(counter, prefix, coverage_data, names, S):
     ms = counter.timing()
     asks, grows, cap = counter.reserve_stats()
     min_mapq, min_clip = counter.min_mapq, counter.min_clip
+    align_counts = None
+    if align is not None:
+        from . import tiddit_clip_align
+        t_align = time.time()
+        try:
+            align_counts = tiddit_clip_align.main(counter, rows, align[0], prefix, names, *align[1:])
+        except BaseException:
+            counter.close()
+            raise
+        t += time.time() - t_align                              # (its seconds are its own: tiddit_clip_align.STAGE_SECONDS)
     counter.close()
     STAGE_SECONDS["clip sites (device: two sorts, gather, run lengths, site heads, vote, rows)"] = time.time() - t
     for k, v in zip(("sort by K2", "gather of K1", "sort by K1", "run lengths + rows", "site heads + vote + site rows"), ms.tolist()):
@@ -287,4 +302,6 @@ def main(counter, prefix, coverage_data, names, S):
     write_file(prefix + ".clips.tab", counts, rows, names, coverage_data, S, min_mapq, min_clip)
     STAGE_SECONDS["clip table text (host)"] = time.time() - t
     print(summary_line(counts))
+    if align_counts is not None:
+        print(tiddit_clip_align.summary_line(align_counts))
     return counts
