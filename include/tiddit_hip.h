@@ -937,6 +937,41 @@ int tdt_clip_align(tdt_clip *h, tdt_refseq *ref, int W, int K, int M, uint64_t *
 int tdt_clip_align_rows(tdt_clip *h, uint32_t *status, uint32_t *partner, uint32_t *strand, uint32_t *mm, uint32_t *hits, size_t *n);
 int tdt_clip_align_timing(tdt_clip *h, double *ms);
 
+/* ---- clip-site consensus placed genome-wide by a seeded search (TIDDIT_CLIPS_FAR) -------------------------- *
+ * For every clip site (the four columns of the tdt_clip_align_* entries) the best placement of its CLEN consensus bases on ANY loaded
+ * contig of a tdt_refseq, on either strand, whose first TDT_CLIP_FAR_SEED columns match exactly and whose other columns differ in at
+ * most M places (csrc/tdt_clip_far.hip: the reference streams once against a sorted seed table of the sites); the definition is
+ * tiddit_amd/tiddit_clip_far.py's.  Per site six uint32: status (0 short_consensus: CLEN < K; 1 off_reference: the site's own contig
+ * is outside the table or not loaded, or P outside 1 ... len; 2 searched), the partner's contig, PARTNER (the best candidate's Q,
+ * 1-based), strand (0 forward, 1 reverse complement), its mismatches, and HITS (the candidates with at most M mismatches; it
+ * saturates at 0xffffffff).  The best candidate is the minimum of (mismatches, another contig than the site's, |Q - P| on the site's
+ * own, strand, contig, Q) over those candidates; a searched site without one, and a site that is not searched, has contig 0, PARTNER 0,
+ * strand 0, mismatches 0xffffffff and HITS 0.  A CLEN above TDT_CLIP_COLS is taken as TDT_CLIP_COLS, of the side only bit 0.
+ * tdt_clip_far_sites takes host arrays of n sites, tdt_clip_far_sites_device caller-owned device arrays; both return when the launches
+ * are done.  tdt_clip_far searches the rows of the handle's last tdt_clip_finish where they lie in HBM, keeps the six columns on the
+ * device for tdt_clip_far_rows (*n in: room of the arrays, out: rows; all six NULL: the count alone) and fills
+ * sn_out[TDT_CLIP_FAR_SN_N]:
+ *   [0] sites  [1] short_consensus  [2] off_reference  [3] searched  [4] placed  [5] ambiguous  [6] unplaced  [7] same_contig
+ *   [8] other_contig  [9] reverse  [10] mated (always 0 here: mates are the host's, rule 5 of the definition)
+ * tdt_clip_far_timing: device milliseconds of the last tdt_clip_far: ms4 = seeds and filter, sort, scan, rows.  The reference is not
+ * owned and must lie on the context's device; it and tdt_clip_align share one.  The candidate's 64-bit key holds the contig in 24
+ * bits and a site takes two entries of the sort.  Refusals: TDT_E_ARG (null pointers, n >= 2^31, a reference of another device, for
+ * the handle a reference with another contig count, tdt_clip_far without a finish since the last push or reset, tdt_clip_far_rows /
+ * _timing without a tdt_clip_far since then), TDT_E_RANGE (K outside TDT_CLIP_FAR_SEED ... TDT_CLIP_COLS, M outside
+ * 0 ... TDT_CLIP_COLS - TDT_CLIP_FAR_SEED, a reference of more than 2^24 contigs, 2^29 sites or more, too little room in
+ * tdt_clip_far_rows); a refused call leaves its outputs untouched. */
+#define TDT_CLIP_FAR_SN_N 11
+#define TDT_CLIP_FAR_SEED 16
+int tdt_clip_far_sites(tdt_ctx *ctx, tdt_refseq *ref, size_t n, const uint64_t *k1, const uint32_t *side, const uint32_t *clen, const uint64_t *consensus,
+                       int K, int M, uint32_t *status_out, uint32_t *partner_tid_out, uint32_t *partner_out, uint32_t *strand_out, uint32_t *mm_out,
+                       uint32_t *hits_out);
+int tdt_clip_far_sites_device(tdt_ctx *ctx, tdt_refseq *ref, size_t n, const uint64_t *d_k1, const uint32_t *d_side, const uint32_t *d_clen,
+                              const uint64_t *d_consensus, int K, int M, uint32_t *d_status, uint32_t *d_partner_tid, uint32_t *d_partner,
+                              uint32_t *d_strand, uint32_t *d_mm, uint32_t *d_hits);
+int tdt_clip_far(tdt_clip *h, tdt_refseq *ref, int K, int M, uint64_t *sn_out);
+int tdt_clip_far_rows(tdt_clip *h, uint32_t *status, uint32_t *partner_tid, uint32_t *partner, uint32_t *strand, uint32_t *mm, uint32_t *hits, size_t *n);
+int tdt_clip_far_timing(tdt_clip *h, double *ms4);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

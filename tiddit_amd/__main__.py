@@ -83,6 +83,18 @@ into HBM before the scan (once, shared with ``TIDDIT_INDELS_NORM`` / ``TIDDIT_SN
 finish, on the site rows where they lie.  ``{o}.clips.tab`` and every other output are what they are without the switch.  Unset or
 empty is off; the switch without ``TIDDIT_CLIPS``, a value that is none of the four forms, or a contig of the BAM header that the FASTA
 lacks or holds at another length, ends the job with an error before the scan.
+
+``TIDDIT_CLIPS_FAR=1`` (minimum consensus columns 20, maximum mismatches 2), ``TIDDIT_CLIPS_FAR=K`` or ``K:M`` (valid only together with
+``TIDDIT_CLIPS``; independent of ``TIDDIT_CLIPS_ALIGN``: either, both or neither): ``--sv`` also writes ``{o}.clips.far.tab`` — for every
+reported clip site whose consensus has at least ``K`` columns (16 ... 28), the best placement of that consensus on ANY contig of the
+reference, on either strand, whose first 16 columns match exactly and whose other columns differ in at most ``M`` places (0 ... 12),
+with the number of such placements, the event the junction implies (BND on another contig; REF / DEL / DUP / INV on the site's own) and
+the opposite-side site that tells the same junction with the microhomology between the two (tiddit_amd/tiddit_clip_far.py has the
+definition and the file's format): translocations, dispersed duplications and clips that place many times, which the window of
+``TIDDIT_CLIPS_ALIGN`` cannot reach.  The reference is packed into HBM before the scan (once, shared with the other switches that read
+it) and streams once against a sorted seed table of the sites behind the clip stage's finish.  Every other output is what it is
+without the switch.  Unset or empty is off; the switch without ``TIDDIT_CLIPS``, a value that is none of the three forms, or a contig of
+the BAM header that the FASTA lacks or holds at another length, ends the job with an error before the scan.
 """
 import argparse
 import os
@@ -334,6 +346,13 @@ def run_sv(args, version):
         # (the same)
         print("error, TIDDIT_CLIPS_ALIGN={}: {}".format(os.environ.get("TIDDIT_CLIPS_ALIGN"), e))
         sys.exit(1)
+    try:
+        from . import tiddit_clip_far
+        clips_far = tiddit_clip_far.parse_switch(os.environ.get("TIDDIT_CLIPS_FAR"), clips is not None)
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_CLIPS_FAR={}: {}".format(os.environ.get("TIDDIT_CLIPS_FAR"), e))
+        sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
     if genotype_depth and sites_path is None:
@@ -369,8 +388,8 @@ def run_sv(args, version):
     contig_number = {c: i for i, c in enumerate(contigs)}
     contig_length = {c["SN"]: c["LN"] for c in bam_header["SQ"]}
     prefix = args.o
-    if indels_norm or snvs is not None or clips_align is not None:
-        # TIDDIT_INDELS_NORM / TIDDIT_SNVS / TIDDIT_CLIPS_ALIGN: the contigs of the BAM header are matched to the FASTA's by name now — one
+    if indels_norm or snvs is not None or clips_align is not None or clips_far is not None:
+        # TIDDIT_INDELS_NORM / TIDDIT_SNVS / TIDDIT_CLIPS_ALIGN / TIDDIT_CLIPS_FAR: the contigs of the BAM header are matched to the FASTA's by name now — one
         # that is missing or has another length ends the job before anything is made
         from . import refseq
         norm_fasta = FastaFile(args.ref)
@@ -381,8 +400,10 @@ def run_sv(args, version):
                 print("error, TIDDIT_INDELS_NORM=1: {}".format(e))
             elif snvs is not None:
                 print("error, TIDDIT_SNVS={}: {}".format(os.environ.get("TIDDIT_SNVS"), e))
-            else:
+            elif clips_align is not None:
                 print("error, TIDDIT_CLIPS_ALIGN={}: {}".format(os.environ.get("TIDDIT_CLIPS_ALIGN"), e))
+            else:
+                print("error, TIDDIT_CLIPS_FAR={}: {}".format(os.environ.get("TIDDIT_CLIPS_FAR"), e))
             sys.exit(1)
     allele_sites = None
     if alleles is not None:
@@ -590,14 +611,15 @@ def run_sv(args, version):
     if indels is not None:
         # TIDDIT_INDELS: ... and a key per small indel of the reads' CIGARs, one launch per batch
         tiddit_signal.INDELS = indels
-    if indels_norm or snvs is not None or clips_align is not None:
-        # TIDDIT_INDELS_NORM / TIDDIT_SNVS / TIDDIT_CLIPS_ALIGN: the reference goes into HBM before the scan (every contig of the BAM
+    if indels_norm or snvs is not None or clips_align is not None or clips_far is not None:
+        # TIDDIT_INDELS_NORM / TIDDIT_SNVS / TIDDIT_CLIPS_ALIGN / TIDDIT_CLIPS_FAR: the reference goes into HBM before the scan (every contig of the BAM
         # header: read, uploaded, packed to 4-bit codes), ONCE: the indel kernel moves every event as far left as it allows, the SNV
         # kernel compares every aligned base with it, the clip stage searches it for the sites' consensus, and all hold the same handle
         t_ref = time.time()
         reference, t_read, t_load = refseq.load_for_bam(norm_fasta, chromosomes, [contig_length[c] for c in chromosomes])
         T["reference into HBM (%s)" % " + ".join(k for k, on in (("TIDDIT_INDELS_NORM", indels_norm), ("TIDDIT_SNVS", snvs is not None),
-                                                                  ("TIDDIT_CLIPS_ALIGN", clips_align is not None)) if on)] = time.time() - t_ref
+                                                                  ("TIDDIT_CLIPS_ALIGN", clips_align is not None),
+                                                                  ("TIDDIT_CLIPS_FAR", clips_far is not None)) if on)] = time.time() - t_ref
         T["  reference: file read (host)"] = t_read
         T["  reference: upload + ref_pack (returns when packed)"] = t_load
         if indels_norm:
@@ -685,14 +707,18 @@ def run_sv(args, version):
         t = time.time()
         try:
             # TIDDIT_CLIPS_ALIGN: ... and the sites' consensus is searched in the reference, behind the finish, where the rows lie
-            tiddit_clips.main(counter, prefix, coverage_data, chromosomes, clips[0], None if clips_align is None else (reference,) + clips_align)
+            # TIDDIT_CLIPS_FAR: ... and placed genome-wide by its seed, the same way
+            tiddit_clips.main(counter, prefix, coverage_data, chromosomes, clips[0], None if clips_align is None else (reference,) + clips_align,
+                              far=None if clips_far is None else (reference,) + clips_far)
         finally:
-            if clips_align is not None and not indels_norm and snvs is None:
-                reference.close()                     # (only this switch loaded it)
+            if (clips_align is not None or clips_far is not None) and not indels_norm and snvs is None:
+                reference.close()                     # (only these switches loaded it)
         T["clip sites ({o}.clips.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_clips.STAGE_SECONDS.items()})
         if clips_align is not None:
             T.update({"  " + k: v for k, v in tiddit_clip_align.STAGE_SECONDS.items()})
+        if clips_far is not None:
+            T.update({"  " + k: v for k, v in tiddit_clip_far.STAGE_SECONDS.items()})
         STAGE_NOTES.update(tiddit_clips.STAGE_NOTES)
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,

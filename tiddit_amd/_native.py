@@ -196,6 +196,11 @@ SYMBOLS = {
     "tdt_clip_align": (_i, [_P, _P, _i, _i, _i, _P]),
     "tdt_clip_align_rows": (_i, [_P] * 6 + [ctypes.POINTER(_sz)]),
     "tdt_clip_align_timing": (_i, [_P, ctypes.POINTER(_dbl)]),
+    "tdt_clip_far_sites": (_i, [_P, _P, _sz] + [_P] * 4 + [_i, _i] + [_P] * 6),
+    "tdt_clip_far_sites_device": (_i, [_P, _P, _sz] + [_P] * 4 + [_i, _i] + [_P] * 6),
+    "tdt_clip_far": (_i, [_P, _P, _i, _i, _P]),
+    "tdt_clip_far_rows": (_i, [_P] * 7 + [ctypes.POINTER(_sz)]),
+    "tdt_clip_far_timing": (_i, [_P, _P]),
     "tdt_refseq_create": (_i, [_P, _i, _P, _PP]),
     "tdt_refseq_destroy": (_i, [_P]),
     "tdt_refseq_load_fasta": (_i, [_P, _i, _P, _i64, _i64, _i, _i]),

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "tdt_clip_align.h"
+#include "tdt_clip_far.h"
 #include "tdt_keystore.h"
 
 typedef unsigned long long ull;
@@ -80,6 +81,12 @@ struct tdt_clip {
     ca_out align;                             // ... of the last tdt_clip_align (inside d_align), n_rows of them; valid while the rows are
     bool align_valid;
     double ms_align;
+    void *d_far;                              // tdt_clip_far's six columns, counters and workspace (grows)
+    size_t far_cap;
+    far_out far;                              // ... of the last tdt_clip_far (inside d_far), n_rows of them; valid while the rows are
+    bool far_valid;
+    double ms_far[4];
+    hipEvent_t ev_far[5];                     // made by the first tdt_clip_far
 };
 
 __global__ __launch_bounds__(CLIP_BLOCK) void clip_keys(ks_cols I, int n, ull raw_len, unsigned min_mapq, unsigned min_clip, ull *__restrict__ k1s,
@@ -274,6 +281,9 @@ static void clip_free(tdt_clip *h) {
     if (h->io.d) (void)hipFree(h->io.d);
     if (h->d_site) (void)hipFree(h->d_site);
     if (h->d_align) (void)hipFree(h->d_align);
+    if (h->d_far) (void)hipFree(h->d_far);
+    for (int k = 0; k < 5; k++)
+        if (h->ev_far[k]) (void)hipEventDestroy(h->ev_far[k]);
     for (int k = 0; k < 2; k++)
         if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     delete h;
@@ -317,7 +327,7 @@ extern "C" int tdt_clip_create(tdt_ctx *ctx, int n_contigs, int min_mapq, int mi
 extern "C" int tdt_clip_destroy(tdt_clip *h) { return ks_destroy(h, clip_free); }
 
 extern "C" int tdt_clip_reset(tdt_clip *h) {
-    if (h) h->n_rows = 0, h->align_valid = false;
+    if (h) h->n_rows = 0, h->align_valid = h->far_valid = false;
     return ks_reset_checked(h ? &h->S : nullptr, "tdt_clip");
 }
 
@@ -329,7 +339,7 @@ static auto clip_launch(tdt_clip *h, size_t n, size_t raw_len) {
             hipLaunchKernelGGL(clip_keys, grid, dim3(CLIP_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, (unsigned)h->min_clip,
                                h->S.k1, h->S.k2, (ull)h->S.cap, h->S.d_state);
         });
-        if (rc == TDT_OK) h->n_rows = 0, h->align_valid = false;
+        if (rc == TDT_OK) h->n_rows = 0, h->align_valid = h->far_valid = false;
         return rc;
     };
 }
@@ -364,7 +374,7 @@ static int clip_sites_of_rows(tdt_clip *h, size_t n_, unsigned min_support, ull 
     got[0] = got[1] = 0;
     h->ms_sites = 0;
     h->n_rows = 0;
-    h->align_valid = false;
+    h->align_valid = h->far_valid = false;
     if (!n_) return TDT_OK;
     const int n = (int)n_;                                         // (< 2^30: ks_finish refused more)
     const size_t ntiles = (n_ + KS_TILE - 1) / KS_TILE;
@@ -587,5 +597,118 @@ extern "C" int tdt_clip_align_timing(tdt_clip *h, double *ms) {
         return TDT_E_ARG;
     }
     *ms = h->ms_align;
+    return TDT_OK;
+}
+
+// ---- the rows of the last finish placed genome-wide (csrc/tdt_clip_far.hip), where they lie: no round trip
+struct clip_far_work {
+    far_out O;
+    far_work Wk;
+    size_t lay(void *base, size_t n) {
+        tdt_carver cv(base);
+        O.status = cv.take<unsigned>(n), O.ptid = cv.take<unsigned>(n), O.partner = cv.take<unsigned>(n), O.strand = cv.take<unsigned>(n);
+        O.mm = cv.take<unsigned>(n), O.hits = cv.take<unsigned>(n), O.sn = cv.take<ull>(TDT_CLIP_FAR_SN_N);
+        const size_t head = cv.size;
+        return head + Wk.lay(base ? (char *)base + head : nullptr, n);
+    }
+};
+
+// sn_out: uint64[TDT_CLIP_FAR_SN_N].  No finish since the last push or reset, or a reference with another contig count: TDT_E_ARG.
+extern "C" int tdt_clip_far(tdt_clip *h, tdt_refseq *ref, int K, int M, uint64_t *sn_out) {
+    if (!h || !ref || !sn_out || ref->ctx->device != h->ctx->device) {
+        tdt_set_error("tdt_clip_far: bad argument");
+        return TDT_E_ARG;
+    }
+    if (!h->S.rows_valid) {
+        tdt_set_error("tdt_clip_far: no finish since the last push or reset");
+        return TDT_E_ARG;
+    }
+    if (ref->n_contigs != h->n_contigs) {
+        tdt_set_error("tdt_clip_far: the reference has %d contigs, the handle was made for %d", ref->n_contigs, h->n_contigs);
+        return TDT_E_ARG;
+    }
+    const size_t n = h->n_rows;
+    int rc = far_check_range("tdt_clip_far", ref, n, K, M);
+    if (rc) return rc;
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    h->far_valid = false;
+    for (int k = 0; k < 4; k++) h->ms_far[k] = 0;
+    for (int k = 0; k < 5; k++)
+        if (!h->ev_far[k]) TDT_HIP(hipEventCreate(&h->ev_far[k]));
+    clip_far_work A;
+    const size_t bytes = A.lay(nullptr, n);
+    if (bytes > h->far_cap) {
+        if (h->d_far) TDT_HIP(hipFree(h->d_far));
+        h->d_far = nullptr;
+        h->far_cap = 0;
+        if (tdt_dev_malloc(&h->d_far, bytes) != hipSuccess) {
+            tdt_set_error("tdt_clip_far: out of device memory (%zu rows)", n);
+            return TDT_E_NOMEM;
+        }
+        h->far_cap = bytes;
+    }
+    A.lay(h->d_far, n);
+    hipStream_t st = h->ctx->stream;
+    uint64_t res[TDT_CLIP_FAR_SN_N] = {};
+    TDT_HIP(hipMemsetAsync(A.O.sn, 0, sizeof res, st));
+    const clip_sites &R = h->rows;
+    rc = far_launch(h->ctx, ref, n, ca_sites{R.k1, R.side, R.clen, R.cons}, K, M, A.O, A.Wk, h->ev_far);
+    if (rc) {
+        (void)tdt_ctx_sync(h->ctx);
+        return rc;
+    }
+    TDT_HIP(hipMemcpyAsync(res, A.O.sn, sizeof res, hipMemcpyDeviceToHost, st));
+    rc = tdt_ctx_sync(h->ctx);
+    if (rc) return rc;
+    for (int k = 0; k < 4; k++) {
+        float ms = 0;
+        TDT_HIP(hipEventElapsedTime(&ms, h->ev_far[k], h->ev_far[k + 1]));
+        h->ms_far[k] = ms;
+    }
+    h->far = A.O;
+    h->far_valid = true;
+    memcpy(sn_out, res, sizeof res);
+    return TDT_OK;
+}
+
+// The six columns of the last tdt_clip_far, in the order of tdt_clip_rows.  *n in: the room of the arrays (ignored when all six are
+// NULL), out: the rows.  Too little room: TDT_E_RANGE, nothing written.
+extern "C" int tdt_clip_far_rows(tdt_clip *h, uint32_t *status, uint32_t *partner_tid, uint32_t *partner, uint32_t *strand, uint32_t *mm, uint32_t *hits,
+                                 size_t *n) {
+    const bool any = status || partner_tid || partner || strand || mm || hits;
+    if (!h || !n || (any && !(status && partner_tid && partner && strand && mm && hits))) {
+        tdt_set_error("tdt_clip_far_rows: bad argument");
+        return TDT_E_ARG;
+    }
+    if (!h->S.rows_valid || !h->far_valid) {
+        tdt_set_error("tdt_clip_far_rows: no tdt_clip_far since the last push, reset or finish");
+        return TDT_E_ARG;
+    }
+    const size_t have = h->n_rows;
+    if (any) {
+        if (*n < have) {
+            tdt_set_error("tdt_clip_far_rows: room for %zu rows, %zu kept", *n, have);
+            return TDT_E_RANGE;
+        }
+        if (have) {
+            TDT_HIP(hipSetDevice(h->ctx->device));
+            hipStream_t st = h->ctx->stream;
+            const far_out &O = h->far;
+            uint32_t *dst[6] = {status, partner_tid, partner, strand, mm, hits};
+            const unsigned *src[6] = {O.status, O.ptid, O.partner, O.strand, O.mm, O.hits};
+            for (int k = 0; k < 6; k++) TDT_HIP(hipMemcpyAsync(dst[k], src[k], have * 4, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipStreamSynchronize(st));
+        }
+    }
+    *n = have;
+    return TDT_OK;
+}
+
+extern "C" int tdt_clip_far_timing(tdt_clip *h, double *ms4) {
+    if (!h || !ms4 || !h->S.rows_valid || !h->far_valid) {
+        tdt_set_error("tdt_clip_far_timing: bad argument, or no tdt_clip_far since the last push, reset or finish");
+        return TDT_E_ARG;
+    }
+    for (int k = 0; k < 4; k++) ms4[k] = h->ms_far[k];
     return TDT_OK;
 }

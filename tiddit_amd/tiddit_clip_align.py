@@ -40,7 +40,9 @@ site, in the order of ``{o}.clips.tab``, all tab-separated.  ``PARTNER`` / ``STR
 candidate (also of an unaligned site), ``.`` when there is none; ``TYPE`` / ``LEN`` are ``.`` for an unaligned site; ``MATE`` is the
 mate's ``POS`` and ``HOM`` the homology, or ``.``.
 
-NOT built: other contigs (translocations), gapped placements, more than the 28 consensus columns, mates of INV rows, joining the rows
+Other contigs (translocations) and placements beyond the window are tiddit_clip_far.py's (``TIDDIT_CLIPS_FAR``), by an exact seed.
+
+NOT built: gapped placements, more than the 28 consensus columns, mates of INV rows, joining the rows
 to the SV candidates or the VCF.
 """
 import ctypes

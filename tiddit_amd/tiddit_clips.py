@@ -47,7 +47,7 @@ so the columns of an ``L`` site are reversed, and is ``.`` when ``CLEN`` is 0; `
 ``tiddit_snvs.write_file`` writes it.
 
 Where the clipped bases come from is tiddit_clip_align.py's (``TIDDIT_CLIPS_ALIGN``): the consensus placed on the same contig, and the
-DEL / DUP / INV the junction implies.
+DEL / DUP / INV the junction implies; and tiddit_clip_far.py's (``TIDDIT_CLIPS_FAR``): the consensus placed on any contig by its seed.
 
 NOT built: the clip's full length, or more than 28 bases of it; joining the sites to the VCF; hard clips (``H`` alone is no clip, and
 the bases it removed are not in the record); supplementary records (0x800 is not eligible); N ranks (refused in ``__main__.run_sv``: a
@@ -270,10 +270,12 @@ def summary_line(counts):
                                         "malformed")))
 
 
-def main(counter, prefix, coverage_data, names, S, align=None):
+def main(counter, prefix, coverage_data, names, S, align=None, far=None):
     """the stage behind the scan: the sort, the run lengths and the vote on the device, the file and the summary line.  ``align``:
     None, or (reference, W, K, M) of ``TIDDIT_CLIPS_ALIGN`` — the rows are then realigned where they lie, behind the finish and before
-    the counter is closed (tiddit_clip_align.main, which writes ``{o}.clips.align.tab``); the reference is not closed here"""
+    the counter is closed (tiddit_clip_align.main, which writes ``{o}.clips.align.tab``); ``far``: None, or (reference, K, M) of
+    ``TIDDIT_CLIPS_FAR`` — the rows are placed genome-wide the same way (tiddit_clip_far.main, ``{o}.clips.far.tab``); the reference is not
+    closed here"""
     STAGE_SECONDS.clear()
     STAGE_NOTES.clear()
     t = time.time()
@@ -292,6 +294,16 @@ def main(counter, prefix, coverage_data, names, S, align=None):
             counter.close()
             raise
         t += time.time() - t_align                              # (its seconds are its own: tiddit_clip_align.STAGE_SECONDS)
+    far_counts = None
+    if far is not None:
+        from . import tiddit_clip_far
+        t_far = time.time()
+        try:
+            far_counts = tiddit_clip_far.main(counter, rows, far[0], prefix, names, *far[1:])
+        except BaseException:
+            counter.close()
+            raise
+        t += time.time() - t_far                                # (the same: tiddit_clip_far.STAGE_SECONDS)
     counter.close()
     STAGE_SECONDS["clip sites (device: two sorts, gather, run lengths, site heads, vote, rows)"] = time.time() - t
     for k, v in zip(("sort by K2", "gather of K1", "sort by K1", "run lengths + rows", "site heads + vote + site rows"), ms.tolist()):
@@ -304,4 +316,6 @@ def main(counter, prefix, coverage_data, names, S, align=None):
     print(summary_line(counts))
     if align_counts is not None:
         print(tiddit_clip_align.summary_line(align_counts))
+    if far_counts is not None:
+        print(tiddit_clip_far.summary_line(far_counts))
     return counts

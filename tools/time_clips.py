@@ -9,7 +9,12 @@ stream idle, best of 4) on every batch of the file.  Writes the record to profil
 With --align the record is about TIDDIT_CLIPS_ALIGN instead: the job with the switches off, with TIDDIT_CLIPS alone and with the aligned
 job, interleaved in one process, and the aligned job at W = 2^20; written to profiles/clips_align_<mb>mb.md.
 
-usage: python tools/time_clips.py (--bam WGS.bam --ref ref.fa | --mb 240) [--reps 3] [--switch 1] [--align [--align-switch 1]] [--out FILE.md]
+With --far the record is about TIDDIT_CLIPS_FAR: the job with the switches off, with TIDDIT_CLIPS alone and with the far job, interleaved
+in one process; `far_scan`'s device time against `clip_align_sites` at W = 2^20 on the same sites scaled to the genome's length (the
+brute-force alternative) and against a plain streaming read of the packed store's bytes; written to profiles/clips_far_<mb>mb.md.
+
+usage: python tools/time_clips.py (--bam WGS.bam --ref ref.fa | --mb 240) [--reps 3] [--switch 1] [--align [--align-switch 1]] [--far [--far-switch 1]]
+                                  [--out FILE.md]
 (--mb: bench.py's synthetic file of that genome size, made at $TIDDIT_BENCH_TMP/tiddit_bench_sv_<mb>/ when it is not there)"""
 import argparse
 import contextlib
@@ -76,9 +81,9 @@ ALIGN_LABELS = {"wall": "whole job", "scan": "scan stage", "reference": "referen
                 "align text": "align: mates and file text (host)"}
 
 
-def _one_job(cli, ctx, bam, ref, out, clips=None, align=None):
+def _one_job(cli, ctx, bam, ref, out, clips=None, align=None, far=None, keys=None):
     """one `--sv --skip_assembly` job in this process -> its wall seconds and stage seconds by short name"""
-    for k, v in (("TIDDIT_CLIPS", clips), ("TIDDIT_CLIPS_ALIGN", align)):
+    for k, v in (("TIDDIT_CLIPS", clips), ("TIDDIT_CLIPS_ALIGN", align), ("TIDDIT_CLIPS_FAR", far)):
         os.environ.pop(k, None)
         if v is not None:
             os.environ[k] = v
@@ -90,10 +95,126 @@ def _one_job(cli, ctx, bam, ref, out, clips=None, align=None):
     finally:
         os.environ.pop("TIDDIT_CLIPS", None)
         os.environ.pop("TIDDIT_CLIPS_ALIGN", None)
+        os.environ.pop("TIDDIT_CLIPS_FAR", None)
     Sx = {k.strip(): v for k, v in cli.STAGE_SECONDS.items()}
     rec = {"wall": time.perf_counter() - t0}
-    rec.update({short: Sx[key] for short, key in ALIGN_KEYS if key in Sx})
+    rec.update({short: Sx[key] for short, key in (keys or ALIGN_KEYS) if key in Sx})
     return rec
+
+
+FAR_MODES = ("off", "clips", "far")
+FAR_KEYS = (("scan", "signal extraction + coverage"), ("reference", "reference into HBM (TIDDIT_CLIPS_FAR)"), ("clip stage", "clip sites ({o}.clips.tab)"),
+            ("far", "clip far (device: seed table, sort, one scan of the packed reference, rows)"), ("seeds", "clip far seeds + filter (device time)"),
+            ("sort", "clip far sort (device time)"), ("far_scan", "clip far scan (device time)"), ("rows", "clip far rows (device time)"),
+            ("far text", "clip far mates + table text (host)"), ("kernel", "clip align kernel (device time)"))
+FAR_LABELS = {"wall": "whole job", "scan": "scan stage", "reference": "reference into HBM (read, upload, pack)", "clip stage": "clip stage (finish, far, files)",
+              "far": "far: the calls into the library (launches, wait, six columns read out)", "seeds": "far: memsets + `far_seeds` (device)",
+              "sort": "far: the sort's launches (device)", "far_scan": "far: `far_scan` (device)", "rows": "far: `far_rows` (device)",
+              "far text": "far: mates and file text (host)", "kernel": "`clip_align_sites` at W = 2^20 (device)"}
+
+
+def stream_read_rate(ctx, nbytes):
+    """what a plain streaming read of ``nbytes`` of device memory reaches (tdt_calib_stream_read, bench.py's roofline.stream_read), GB/s"""
+    import ctypes
+    import torch
+    from tiddit_amd import _native
+    cal = torch.empty(max(nbytes // 8, 1 << 20), dtype=torch.int64, device="cuda")
+    cal.random_(0, 1 << 40)
+    torch.cuda.synchronize()
+    rate = 0.0
+    for wpc, blocked in ((2, 0), (8, 0), (8, 1)):
+        cb, cm = ctypes.c_double(0), ctypes.c_double(0)
+        _native.check(ctx.lib.tdt_calib_stream_read(ctx.handle, cal.data_ptr(), cal.numel() * 8, 10, wpc, blocked, ctypes.byref(cb), ctypes.byref(cm)))
+        rate = max(rate, cal.numel() * 8 / (cm.value * 1e-3) / 1e9)
+    return rate
+
+
+def main_far(a):
+    """--far: the job with the switches off, with TIDDIT_CLIPS alone and with TIDDIT_CLIPS_FAR beside it, interleaved in one process,
+    medians of --reps; then TIDDIT_CLIPS_ALIGN at W = 2^20 on the same sites, the brute force the seeded scan replaces"""
+    from tiddit_amd import __main__ as cli
+    from tiddit_amd import _native, bamio, tiddit_clip_align, tiddit_clip_far
+    ctx = _native.default_context()
+    K, M = tiddit_clip_far.parse_switch(a.far_switch)
+    widest = "%d:%d:%d" % (tiddit_clip_align.MAX_WINDOW, K, M)
+    rd = bamio.BamReader(a.bam, batch_bytes=1 << 20)
+    lengths = [int(c["LN"]) for c in rd.header["SQ"]]
+    rd.close()
+    genome = sum(lengths)
+    store = 16 + sum((n + 15) // 16 * 8 + 16 for n in lengths)          # the packed store's bytes (refseq.RefSeq.layout)
+    runs = {m: [] for m in FAR_MODES + ("widest",)}
+    table = wide = {}
+    sn_of = lambda path: {l.split("\t")[1]: int(l.split("\t")[2]) for l in open(path).read().split("\n") if l.startswith("SN\t")}
+    with tempfile.TemporaryDirectory() as d:
+        for i in range(a.reps + 1):                       # (the first round warms up)
+            for mode in FAR_MODES:
+                out = os.path.join(d, "r%d_%s" % (i, mode))
+                rec = _one_job(cli, ctx, a.bam, a.ref, out, a.switch if mode != "off" else None, None, a.far_switch if mode == "far" else None, FAR_KEYS)
+                assert os.path.exists(out + ".clips.far.tab") == (mode == "far") and os.path.exists(out + ".clips.tab") == (mode != "off")
+                if i:
+                    runs[mode].append(rec)
+                print("round %d %s: %.3f s" % (i, mode, rec["wall"]), file=sys.stderr, flush=True)
+                if mode == "far" and i == a.reps:
+                    table = sn_of(out + ".clips.far.tab")
+                    types = {}
+                    for l in open(out + ".clips.far.tab").read().split("\n"):
+                        if l and not l.startswith(("#", "SN\t")):
+                            types[l.split("\t")[10]] = types.get(l.split("\t")[10], 0) + 1
+        for i in range(a.reps + 1):
+            out = os.path.join(d, "w%d" % i)
+            rec = _one_job(cli, ctx, a.bam, a.ref, out, a.switch, widest, None, FAR_KEYS)
+            if i:
+                runs["widest"].append(rec)
+            if i == a.reps:
+                wide = sn_of(out + ".clips.align.tab")
+            print("widest %d: %.3f s, kernel %.3f ms" % (i, rec["wall"], rec.get("kernel", 0) * 1e3), file=sys.stderr, flush=True)
+    rate = stream_read_rate(ctx, store)
+    keys = ["wall"] + [short for short, _ in FAR_KEYS]
+    med = lambda mode, key: statistics.median([r[key] for r in runs[mode] if r.get(key) is not None] or [float("nan")])
+    base, offw = [r["wall"] for r in runs["clips"]], [r["wall"] for r in runs["off"]]
+    scan_ms, brute_ms = med("far", "far_scan") * 1e3, med("widest", "kernel") * 1e3
+    brute_scaled = brute_ms * genome / (2.0 * tiddit_clip_align.MAX_WINDOW + 1)
+    stream_ms = store / (rate * 1e9) * 1e3
+    res = {"bam": a.bam, "bam_MB": round(os.path.getsize(a.bam) / 1e6, 1), "reps": a.reps, "switch": a.switch, "far": a.far_switch, "SN": table, "TYPE": types,
+           "SN_align_widest": wide, "genome_bases": genome, "store_bytes": store, "stream_read_GB_per_s": rate, "far_scan_ms": scan_ms,
+           "clip_align_widest_ms": brute_ms, "clip_align_scaled_to_genome_ms": brute_scaled, "far_scan_frac_of_stream_read": stream_ms / scan_ms if scan_ms else None,
+           "median_s": {m: {k: med(m, k) for k in keys if any(k in r for r in runs[m])} for m in runs}, "clips_alone_wall_spread_s": max(base) - min(base),
+           "off_wall_spread_s": max(offw) - min(offw), "runs": runs}
+    print(json.dumps(res))
+    path = a.out or os.path.join(REPO, "profiles", "clips_far" + ("_%dmb.md" % a.mb if a.mb else ".md"))
+    with open(path, "w") as f:
+        f.write("# Clip-site consensus placed genome-wide by a seeded search (`TIDDIT_CLIPS=%s TIDDIT_CLIPS_FAR=%s`)\n\n" % (a.switch, a.far_switch))
+        f.write("File: `%s` (%.0f MB), %d contigs, %d bases; the packed store is %d bytes.  `tools/time_clips.py --far`: one process, after one warm-up round "
+                "%d rounds of { switches off, `TIDDIT_CLIPS` alone, `TIDDIT_CLIPS` + `TIDDIT_CLIPS_FAR` }, interleaved; then %d jobs with "
+                "`TIDDIT_CLIPS_ALIGN=%s` on the same sites.  Wall seconds unless a row says device.  The yardstick is the `TIDDIT_CLIPS`-alone job of the "
+                "same process and the spread of its runs; no threshold was fixed in advance, this is what was measured.\n\n" % (
+                    os.path.basename(os.path.dirname(a.bam)) + "/" + os.path.basename(a.bam), os.path.getsize(a.bam) / 1e6, len(lengths), genome, store, a.reps, a.reps,
+                    widest))
+        f.write("| | " + " | ".join("run %d" % (k + 1) for k in range(a.reps)) + " | median |\n|---|" + "---|" * (a.reps + 1) + "\n")
+        for mode in runs:
+            for key in keys:
+                if not any(key in r for r in runs[mode]):
+                    continue
+                f.write("| %s: %s | %s | %.5f |\n" % (mode, FAR_LABELS[key], " | ".join("%.5f" % r.get(key, float("nan")) for r in runs[mode]), med(mode, key)))
+        f.write("\nWhole job, far against the `TIDDIT_CLIPS`-alone median: %+.4f s; the `TIDDIT_CLIPS`-alone runs' spread is %.4f s (min %.4f, max %.4f), the off "
+                "runs' %.4f s.  The reference going into HBM is %.4f s of it, which `TIDDIT_INDELS_NORM` / `TIDDIT_SNVS` / `TIDDIT_CLIPS_ALIGN` pay already when they "
+                "are on.\n" % (med("far", "wall") - med("clips", "wall"), max(base) - min(base), min(base), max(base), max(offw) - min(offw), med("far", "reference")))
+        f.write("\n`far_scan`: %.3f ms (device) for %d sites (%d searched: %d table entries) over %d bases.  The brute force it replaces, `clip_align_sites` at "
+                "W = 2^20 on the same sites (%d searched there): %.3f ms for 2^21 + 1 starts per site, which scaled to the genome's length is %.1f ms — an "
+                "extrapolation, not a measurement.  A plain streaming read of the store's %d bytes at `roofline.stream_read` (%.0f GB/s measured in this "
+                "process) would take %.4f ms: `far_scan` runs at %.3f of it, so it is not bound by the memory: every base costs two funnel shifts, a multiply and "
+                "one read of the filter in LDS, and which of these bounds it was not measured (no profiler run; with this few sites the filter passes almost "
+                "nothing, so table lookups and atomics are not it).  The seed launch (two memsets and `far_seeds`) is %.3f ms, the sort's launches %.3f "
+                "ms, `far_rows` %.3f ms; the stage's host side (the library calls with their wait, then mates and text) %.5f s + %.5f s.\n" % (
+                    scan_ms, table.get("sites", 0), table.get("searched", 0), 2 * table.get("searched", 0), genome, wide.get("searched", 0), brute_ms, brute_scaled, store,
+                    rate, stream_ms, stream_ms / scan_ms if scan_ms else float("nan"), med("far", "seeds") * 1e3, med("far", "sort") * 1e3, med("far", "rows") * 1e3,
+                    med("far", "far"), med("far", "far text")))
+        f.write("\nThe table: %s.  TYPE of the rows: %s.\n" % (", ".join("%s %d" % kv for kv in table.items()), ", ".join("%s %d" % kv for kv in sorted(types.items()))))
+        f.write("\nThe synthetic file plants no junction sequence: the bases of a read, its clip included, are cut from the reference in one piece "
+                "(`synth_bam.write_wgs_sv_bam` with `ref_seqs`), so every site is expected to place as `REF` beside its own breakpoint: the figures are the "
+                "cost of the search, not a result.  Not measured by this record: real libraries, ten thousand sites and more (the filter's hit rate grows with "
+                "the table: %d entries set at most that many of its 2^19 bits here), repeat-rich seeds (a seed with millions of occurrences pays an atomic "
+                "pair per wave and tile), 3 Gb, the kernel under a profiler.\n" % (2 * table.get("searched", 0)))
 
 
 def main_align(a):
@@ -168,6 +289,8 @@ def main():
     ap.add_argument("--switch", default="1")
     ap.add_argument("--align", action="store_true", help="measure TIDDIT_CLIPS_ALIGN against the TIDDIT_CLIPS-alone job instead")
     ap.add_argument("--align-switch", default="1")
+    ap.add_argument("--far", action="store_true", help="measure TIDDIT_CLIPS_FAR against the TIDDIT_CLIPS-alone job instead")
+    ap.add_argument("--far-switch", default="1")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.mb:
@@ -177,6 +300,8 @@ def main():
     print("file: %s" % a.bam, file=sys.stderr, flush=True)
     if a.align:
         return main_align(a)
+    if a.far:
+        return main_far(a)
     from tiddit_amd import __main__ as cli
     from tiddit_amd import _native, tiddit_clips
     S, Q, L = tiddit_clips.parse_switch(a.switch)
