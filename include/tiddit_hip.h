@@ -972,6 +972,57 @@ int tdt_clip_far(tdt_clip *h, tdt_refseq *ref, int K, int M, uint64_t *sn_out);
 int tdt_clip_far_rows(tdt_clip *h, uint32_t *status, uint32_t *partner_tid, uint32_t *partner, uint32_t *strand, uint32_t *mm, uint32_t *hits, size_t *n);
 int tdt_clip_far_timing(tdt_clip *h, double *ms4);
 
+/* ---- insertion candidates from facing clip sites (TIDDIT_CLIPS_INS) --------------------------------------- *
+ * The clipped bases of a clip site beyond TDT_CLIP_COLS columns, up to TDT_CLIP_EXT_COLS, and the insertion that an R site and an L
+ * site facing each other close where their extended consensus overlap (csrc/tdt_clip_ins.hip, the extension keys in
+ * csrc/tdt_clip.hip); the definition is tiddit_amd/tiddit_clip_ins.py's.  tdt_clip_ext_enable gives a tdt_clip handle a SECOND key
+ * store of `capacity` keys, before its first push: every push then also stores, per clip of which more than 28 bases are kept, one key
+ * per further chunk c = 1 ... 4 of 28 columns, K1 = c << 56 | tid << 32 | P and K2 in the layout of the first store (at most
+ * TDT_CLIP_EXT_MAX_PER_READ keys per read; the store reserves and grows as the first does).  tdt_clip_ext_keys reads that store out in
+ * the convention of tdt_clip_keys.  tdt_clip_ins runs on the rows of the handle's last tdt_clip_finish where they lie in HBM, with that
+ * finish's minimum support S: the second store is finished as the first was (a chunk's row has SUPPORT >= S), the chunks are gathered
+ * onto the rows (ECLEN, and TDT_CLIP_EXT_WORDS words of 56 bits per row: columns 28 w ... 28 w + 27 in word w), and every R row with
+ * ECLEN >= K is paired with every L row with ECLEN >= K on its contig at P_R + 1 - d, 0 <= d <= TDT_CLIP_INS_MAX_TSD.  Per pair, for
+ * l in O ... a + b - O (a, b the two ECLEN): the overlap o = min(a, l) - max(0, l - b) and its mismatches; an l with o >= O and at most
+ * M mismatches is a closure, the best one the minimum of (mismatches, l).  It fills sn_out[TDT_CLIP_INS_SN_N]:
+ *   [0] ext_left_events  [1] ext_right_events  [2] ext_keys  [3] cut_beyond_28  [4] sites_extended  [5] left_sites  [6] right_sites
+ *   [7] pairs  [8] closed  [9] open  [10] closed_multi
+ * tdt_clip_ext_rows reads ECLEN and the words of every row out, in the order of tdt_clip_rows; tdt_clip_ins_rows the pairs, ascending
+ * by (contig, P_R, P_L): the two rows' indices, TSD = d, status (1 closed, 0 open), LEN, MISMATCH and CLOSURES (LEN and MISMATCH 0
+ * for an open pair) and TDT_CLIP_INS_SEQ_WORDS words of 56 bits of the closed sequence (zero for an open pair); for both *n in: the room
+ * of the arrays, out: the rows; every array NULL: the count alone.  tdt_clip_ins_timing: device milliseconds of the last tdt_clip_ins:
+ * ms3 = the second store's finish, the gather, the pair launches.  tdt_clip_ins_sites takes host arrays of n sites (k1, side, eclen,
+ * cons5) that ascend strictly by (K1, side), tdt_clip_ins_sites_device caller-owned device arrays (outputs and sn_out on the device
+ * too; their order is the caller's to keep); *n_pairs in: the room of the eight pair arrays, out: the pairs; all eight NULL: the pair
+ * count and the counters [4] ... [7] alone.  An ECLEN above TDT_CLIP_EXT_COLS is taken as TDT_CLIP_EXT_COLS, of the side only bit 0.
+ * Refusals: TDT_E_ARG (null pointers, some but not all output arrays, host sites that do not ascend, tdt_clip_ext_enable twice or
+ * behind a push, tdt_clip_ext_keys / tdt_clip_ins without tdt_clip_ext_enable, tdt_clip_ins without a finish since the last push or
+ * reset, the read-outs and the timing without a tdt_clip_ins since then), TDT_E_RANGE (K outside TDT_CLIP_INS_MIN_COLS ...
+ * TDT_CLIP_EXT_COLS, O outside TDT_CLIP_INS_MIN_OVERLAP ... TDT_CLIP_EXT_COLS, M outside 0 ... TDT_CLIP_INS_MAX_MISMATCH, too little
+ * room); a refused call leaves its outputs untouched. */
+#define TDT_CLIP_EXT_COLS 140
+#define TDT_CLIP_EXT_WORDS 5
+#define TDT_CLIP_EXT_MAX_PER_READ 8
+#define TDT_CLIP_INS_SN_N 11
+#define TDT_CLIP_INS_MAX_TSD 32
+#define TDT_CLIP_INS_SEQ_WORDS 10
+#define TDT_CLIP_INS_MIN_COLS 10
+#define TDT_CLIP_INS_MIN_OVERLAP 8
+#define TDT_CLIP_INS_MAX_MISMATCH 8
+int tdt_clip_ext_enable(tdt_clip *h, size_t capacity);
+int tdt_clip_ext_keys(tdt_clip *h, uint64_t *k1, uint64_t *k2, size_t *n);
+int tdt_clip_ins(tdt_clip *h, int K, int O, int M, uint64_t *sn_out);
+int tdt_clip_ext_rows(tdt_clip *h, uint32_t *eclen, uint64_t *cons5, size_t *n);
+int tdt_clip_ins_rows(tdt_clip *h, uint32_t *r_row, uint32_t *l_row, uint32_t *tsd, uint32_t *status, uint32_t *len, uint32_t *mm, uint32_t *closures,
+                      uint64_t *seq10, size_t *n);
+int tdt_clip_ins_timing(tdt_clip *h, double *ms3);
+int tdt_clip_ins_sites(tdt_ctx *ctx, size_t n, const uint64_t *k1, const uint32_t *side, const uint32_t *eclen, const uint64_t *cons5, int K, int O, int M,
+                       uint64_t *sn_out, uint32_t *r_row, uint32_t *l_row, uint32_t *tsd, uint32_t *status, uint32_t *len, uint32_t *mm, uint32_t *closures,
+                       uint64_t *seq10, size_t *n_pairs);
+int tdt_clip_ins_sites_device(tdt_ctx *ctx, size_t n, const uint64_t *d_k1, const uint32_t *d_side, const uint32_t *d_eclen, const uint64_t *d_cons5, int K,
+                              int O, int M, uint64_t *d_sn_out, uint32_t *d_r_row, uint32_t *d_l_row, uint32_t *d_tsd, uint32_t *d_status, uint32_t *d_len,
+                              uint32_t *d_mm, uint32_t *d_closures, uint64_t *d_seq10, size_t *n_pairs);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

@@ -95,6 +95,17 @@ definition and the file's format): translocations, dispersed duplications and cl
 it) and streams once against a sorted seed table of the sites behind the clip stage's finish.  Every other output is what it is
 without the switch.  Unset or empty is off; the switch without ``TIDDIT_CLIPS``, a value that is none of the three forms, or a contig of
 the BAM header that the FASTA lacks or holds at another length, ends the job with an error before the scan.
+
+``TIDDIT_CLIPS_INS=1`` (minimum extended-consensus columns 20, minimum overlap 12, maximum mismatches 1), ``TIDDIT_CLIPS_INS=K``, ``K:O``
+or ``K:O:M`` (valid only together with ``TIDDIT_CLIPS``; independent of ``TIDDIT_CLIPS_ALIGN`` and ``TIDDIT_CLIPS_FAR``, and no FASTA goes
+into HBM for it): ``--sv`` also writes ``{o}.clips.ins.tab`` — insertion candidates from clip sites that face each other.  The vote over
+the clipped bases of a site is carried from 28 to 140 columns (a second key store beside the first, one more launch per batch), every
+``R`` site with at least ``K`` (10 ... 140) columns is paired with every such ``L`` site at ``P_R + 1`` or up to 32 bases to its left (a
+target-site duplication), and the pair is ``CLOSED`` where the two extended consensus overlap by ``O`` (8 ... 140) bases or more with at
+most ``M`` (0 ... 8) mismatches, with the inserted sequence (up to 2 x 140 - ``O`` bases); otherwise it is ``OPEN`` and the two flanks
+are what is known of a longer insertion (tiddit_amd/tiddit_clip_ins.py has the definition and the file's format).  Every other output is
+what it is without the switch.  Unset or empty is off; the switch without ``TIDDIT_CLIPS``, or a value that is none of the four forms,
+ends the job with an error before the scan.  N ranks are refused with ``TIDDIT_CLIPS``.
 """
 import argparse
 import os
@@ -352,6 +363,13 @@ def run_sv(args, version):
     except ValueError as e:
         # (the same)
         print("error, TIDDIT_CLIPS_FAR={}: {}".format(os.environ.get("TIDDIT_CLIPS_FAR"), e))
+        sys.exit(1)
+    try:
+        from . import tiddit_clip_ins
+        clips_ins = tiddit_clip_ins.parse_switch(os.environ.get("TIDDIT_CLIPS_INS"), clips is not None)
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_CLIPS_INS={}: {}".format(os.environ.get("TIDDIT_CLIPS_INS"), e))
         sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
@@ -631,6 +649,8 @@ def run_sv(args, version):
     if clips is not None:
         # TIDDIT_CLIPS: ... and a key per soft clip of the reads, one launch per batch
         tiddit_signal.CLIPS = clips
+        # TIDDIT_CLIPS_INS: ... and a key per further chunk of 28 clipped bases, one more launch per batch
+        tiddit_signal.CLIPS_INS = clips_ins is not None
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -651,6 +671,7 @@ def run_sv(args, version):
             tiddit_signal.SNVS = None
             tiddit_signal.SNV_REFERENCE = None        # (the same)
             tiddit_signal.CLIPS = None
+            tiddit_signal.CLIPS_INS = False
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:
@@ -708,8 +729,9 @@ def run_sv(args, version):
         try:
             # TIDDIT_CLIPS_ALIGN: ... and the sites' consensus is searched in the reference, behind the finish, where the rows lie
             # TIDDIT_CLIPS_FAR: ... and placed genome-wide by its seed, the same way
+            # TIDDIT_CLIPS_INS: ... and the rows are extended from the second store, paired and closed, the same way
             tiddit_clips.main(counter, prefix, coverage_data, chromosomes, clips[0], None if clips_align is None else (reference,) + clips_align,
-                              far=None if clips_far is None else (reference,) + clips_far)
+                              far=None if clips_far is None else (reference,) + clips_far, ins=clips_ins)
         finally:
             if (clips_align is not None or clips_far is not None) and not indels_norm and snvs is None:
                 reference.close()                     # (only these switches loaded it)
@@ -719,6 +741,8 @@ def run_sv(args, version):
             T.update({"  " + k: v for k, v in tiddit_clip_align.STAGE_SECONDS.items()})
         if clips_far is not None:
             T.update({"  " + k: v for k, v in tiddit_clip_far.STAGE_SECONDS.items()})
+        if clips_ins is not None:
+            T.update({"  " + k: v for k, v in tiddit_clip_ins.STAGE_SECONDS.items()})
         STAGE_NOTES.update(tiddit_clips.STAGE_NOTES)
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,

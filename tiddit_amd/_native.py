@@ -201,6 +201,14 @@ SYMBOLS = {
     "tdt_clip_far": (_i, [_P, _P, _i, _i, _P]),
     "tdt_clip_far_rows": (_i, [_P] * 7 + [ctypes.POINTER(_sz)]),
     "tdt_clip_far_timing": (_i, [_P, _P]),
+    "tdt_clip_ext_enable": (_i, [_P, _sz]),
+    "tdt_clip_ext_keys": (_i, [_P, _P, _P, ctypes.POINTER(_sz)]),
+    "tdt_clip_ins": (_i, [_P, _i, _i, _i, _P]),
+    "tdt_clip_ext_rows": (_i, [_P, _P, _P, ctypes.POINTER(_sz)]),
+    "tdt_clip_ins_rows": (_i, [_P] * 9 + [ctypes.POINTER(_sz)]),
+    "tdt_clip_ins_timing": (_i, [_P, _P]),
+    "tdt_clip_ins_sites": (_i, [_P, _sz] + [_P] * 4 + [_i, _i, _i] + [_P] * 9 + [ctypes.POINTER(_sz)]),
+    "tdt_clip_ins_sites_device": (_i, [_P, _sz] + [_P] * 4 + [_i, _i, _i] + [_P] * 9 + [ctypes.POINTER(_sz)]),
     "tdt_refseq_create": (_i, [_P, _i, _P, _PP]),
     "tdt_refseq_destroy": (_i, [_P]),
     "tdt_refseq_load_fasta": (_i, [_P, _i, _P, _i64, _i64, _i, _i]),

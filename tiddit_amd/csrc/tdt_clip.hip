@@ -30,10 +30,23 @@
 //         packed consensus an OR, AGREE and TOTAL sums over the wave.  A site of tens of thousands of rows costs its rows / 64 steps;
 //       - clip_keep<false> counts per tile the sites with SUPPORT >= S, ks_carry_sum again, clip_keep<true> writes them as rows in
 //         key order.
+//   * clip_ext_keys — ONE more launch per batch, only on a handle with tdt_clip_ext_enable (TIDDIT_CLIPS_INS), enqueued beside clip_keys
+//     and waiting for nothing: the same gate, open and CIGAR pass; for a clip of which more than 28 bases are kept it emits one key per
+//     further chunk c = 1 ... 4 of 28 columns, K1 = c << 56 | tid << 32 | P (the tid has 24 bits, the top byte is free) and K2 in
+//     clip_keys' layout, into a SECOND key store of the handle, whose reserve, growth and ask-the-device policy are the first one's.
+//     At most TDT_CLIP_EXT_MAX_PER_READ = 8 keys per read, staged in LDS: 256 reads x 8 keys x 16 B = 32 KB (34 056 B with the gate's
+//     and the flush's words).  That is four workgroups (16 waves) per CU by LDS, half of clip_keys'; a tile of 128 reads would halve
+//     the LDS and double the workgroups and their flush atomics for the same waves per CU, and most lanes of this kernel leave at
+//     the clip-length test before a base is read, so the tile stays one round of 256.  Malformed, no-sequence and no-alignment reads emit nothing here and are not counted again.
+//     With the chunk in K1 a "site" of that store is a (chunk, site), and the finish above — ks_finish with support 1, clip_heads,
+//     clip_vote, clip_keep with S — gives each chunk's SUPPORT, CLEN and packed consensus with no new vote kernel
+//     (clip_sites_of_rows takes the store and the buffers as arguments).  The gather of the chunks into an extended consensus, the
+//     pairing of facing sites and the closure are csrc/tdt_clip_ins.hip's.
 #include <vector>
 
 #include "tdt_clip_align.h"
 #include "tdt_clip_far.h"
+#include "tdt_clip_ins.h"
 #include "tdt_keystore.h"
 
 typedef unsigned long long ull;
@@ -47,6 +60,7 @@ static_assert(CLIP_K_TILE == CLIP_BLOCK, "one round per workgroup");
 static_assert(TDT_CLIP_MAX_PER_READ == 2, "a leading and a trailing clip");
 static_assert(TDT_CLIP_COLS == 28 && TDT_CLIP_COLS <= CLIP_VOTE_BLOCK, "56 bits of bases in K2; a lane per column");
 static_assert(CLIP_VOTE_BLOCK == 64, "clip_vote's workgroup is one wavefront");
+static_assert(TDT_CLIP_EXT_COLS == 5 * TDT_CLIP_COLS && TDT_CLIP_EXT_MAX_PER_READ == 2 * 4, "four further chunks of 28 columns per clip");
 
 // the SN rows, in the order of the file; the first ten are the push's
 enum { SN_RECORDS = 0, SN_ELIGIBLE, SN_MALFORMED, SN_NO_SEQUENCE, SN_NO_ALIGNMENT, SN_SHORT_CLIPS, SN_LEFT_CLIPS, SN_RIGHT_CLIPS, SN_CLIPPED_READS,
@@ -54,6 +68,8 @@ enum { SN_RECORDS = 0, SN_ELIGIBLE, SN_MALFORMED, SN_NO_SEQUENCE, SN_NO_ALIGNMEN
 static_assert(SN_N == TDT_CLIP_SN_N, "SN rows");
 enum { ST_OR1 = SN_PUSH_N };                  // OR1, NAND1, OR2, NAND2 behind the push counters; KS_N, KS_OVERFLOW: tdt_keystore.h
 static_assert(ST_OR1 + 4 <= KS_N, "state layout");
+// the push counters of the extension store: the events with a key by side, the clips cut at another base at or beyond column 28
+enum { XN_LEFT = 0, XN_RIGHT, XN_CUT, XN_PUSH_N, XT_OR1 = XN_PUSH_N };
 
 struct clip_sites {                           // per site (n entries each): what clip_vote writes / what clip_keep<true> keeps
     ull *k1, *cons, *agree, *total;
@@ -87,6 +103,26 @@ struct tdt_clip {
     bool far_valid;
     double ms_far[4];
     hipEvent_t ev_far[5];                     // made by the first tdt_clip_far
+    // ---- TIDDIT_CLIPS_INS: nothing below is allocated without tdt_clip_ext_enable
+    bool ext;
+    tdt_keystore X;                           // the extension keys (chunk << 56 | K1, K2)
+    void *d_xsite;                            // the site launches' buffers over X's rows (grows)
+    size_t xsite_cap;
+    clip_sites xrows;                         // the (chunk, site) rows of the last tdt_clip_ins (inside d_xsite), n_xrows of them
+    size_t n_xrows;
+    double ms_xsites;
+    unsigned last_support;                    // the minimum support of the last tdt_clip_finish
+    void *d_ins;                              // ECLEN and the five words per row, the pair stage's workspace and counters (grows)
+    size_t ins_cap;
+    unsigned *ext_eclen;                      // ... of the last tdt_clip_ins (inside d_ins), n_rows of them; valid while the rows are
+    ull *ext_cons5;
+    void *d_pairs;                            // the pair rows (grows)
+    size_t pairs_cap;
+    ins_out pairs;                            // ... of the last tdt_clip_ins (inside d_pairs), n_pairs of them
+    size_t n_pairs;
+    bool ins_valid;
+    double ms_ins[3];
+    hipEvent_t ev_ins[4];                     // made by tdt_clip_ext_enable
 };
 
 __global__ __launch_bounds__(CLIP_BLOCK) void clip_keys(ks_cols I, int n, ull raw_len, unsigned min_mapq, unsigned min_clip, ull *__restrict__ k1s,
@@ -170,6 +206,89 @@ __global__ __launch_bounds__(CLIP_BLOCK) void clip_keys(ks_cols I, int n, ull ra
         }
     }
     ks_flush<CLIP_BLOCK, SN_PUSH_N>(cnt, M, nk, s_k1, s_k2, k1s, k2s, cap, st);
+}
+
+// The extension keys of a batch (see the head of this file).  The gate counts nothing here (records and eligible are clip_keys'), and
+// a read that clip_keys calls malformed, without sequence or without alignment is passed over.
+__global__ __launch_bounds__(CLIP_BLOCK) void clip_ext_keys(ks_cols I, int n, ull raw_len, unsigned min_mapq, unsigned min_clip, ull *__restrict__ k1s,
+                                                            ull *__restrict__ k2s, ull cap, ull *__restrict__ st) {
+    __shared__ ull s_k1[CLIP_K_TILE * TDT_CLIP_EXT_MAX_PER_READ], s_k2[CLIP_K_TILE * TDT_CLIP_EXT_MAX_PER_READ];      // 2 x 16 KB
+    const long long lo = (long long)blockIdx.x * CLIP_K_TILE, hi = lo + CLIP_K_TILE < n ? lo + CLIP_K_TILE : n;
+    ull cnt[XN_PUSH_N] = {0, 0, 0};
+    ull records = 0, eligible = 0;                                 // (not counted again)
+    const ks_gated G = ks_read_gate<CLIP_BLOCK>(I, lo, hi, min_mapq, records, eligible);
+    const bool live = (int)threadIdx.x < G.live;
+    unsigned ncut = 0;
+    int nE[2] = {0, 0};                                            // the chunks 1 ... nE[side] of a clip have a key
+    ull eK1[2] = {0, 0}, eK2[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    ks_read A{};
+    const uint8_t *__restrict__ raw = I.raw;
+    if (live && KS_OPEN(A, I, G.read, raw_len)) {
+        const tdt_rec &R = A.R;
+        const int pos = A.pos, l_seq = R.l_seq;
+        const unsigned nc = R.n_cig;
+        const tdt_cig_span C = tdt_cig_span_of<true>(raw + R.cig(), nc);
+        const unsigned w0 = C.w0, w1 = C.w1, wy = C.wy, wz = C.wz;
+        const ull rl = C.ref_len;
+        if (!C.malformed(pos, l_seq, nc) && nc != 0 && l_seq != 0 && rl != 0) {
+            const ull seq = R.seq();
+            const bool lead = (w0 & 0xfu) == 4u || ((w0 & 0xfu) == 5u && nc >= 2 && (w1 & 0xfu) == 4u);
+            const bool trail = (wz & 0xfu) == 4u || ((wz & 0xfu) == 5u && nc >= 2 && (wy & 0xfu) == 4u);
+            const unsigned llen = ((w0 & 0xfu) == 4u ? w0 : w1) >> 4, tlen = ((wz & 0xfu) == 4u ? wz : wy) >> 4;
+#pragma unroll
+            for (int side = 0; side < 2; side++) {
+                const bool has = side ? trail : lead;
+                const unsigned clen = side ? tlen : llen;
+                if (!has || clen < min_clip || clen <= (unsigned)TDT_CLIP_COLS) continue;       // (no column beyond the 28 of clip_keys)
+                const unsigned want = clen < (unsigned)TDT_CLIP_EXT_COLS ? clen : (unsigned)TDT_CLIP_EXT_COLS;
+                const ull q0 = side ? (ull)l_seq - clen : (ull)clen - 1ull;      // column j: q0 + j (R), q0 - j (L), as in clip_keys
+                unsigned nb = 0;                                   // the columns kept so far
+                while (nb < (unsigned)TDT_CLIP_COLS && __popc(tdt_rec_base(raw, seq, side ? q0 + nb : q0 - nb)) == 1) nb++;
+                bool full = nb == (unsigned)TDT_CLIP_COLS;         // the chunk in front was full
+#pragma unroll
+                for (int c = 1; c <= 4; c++) {
+                    if (!full) break;
+                    const unsigned at = (unsigned)(TDT_CLIP_COLS * c), lim = want > at ? (want - at < (unsigned)TDT_CLIP_COLS ? want - at : (unsigned)TDT_CLIP_COLS) : 0u;
+                    unsigned k = 0;
+                    ull bases = 0;
+                    while (k < lim) {
+                        const unsigned code = tdt_rec_base(raw, seq, side ? q0 + at + k : q0 - at - k);
+                        if (__popc(code) != 1) break;
+                        bases |= (ull)__builtin_ctz(code) << (2u * k);
+                        k++;
+                    }
+                    nb += k;
+                    full = k == (unsigned)TDT_CLIP_COLS;
+                    if (k) {
+                        eK2[side][c - 1] = ((ull)side << 63) | ((ull)k << 58) | (bases << 2) | (ull)A.rev;
+                        nE[side] = c;
+                    }
+                }
+                ncut += nb >= (unsigned)TDT_CLIP_COLS && nb < want;
+                eK1[side] = ((ull)(unsigned)A.tid << 32) | (side ? (ull)pos + rl : (ull)pos + 1ull);
+            }
+        }
+    }
+    cnt[XN_LEFT] = (ull)__popcll(__ballot(nE[0] > 0));
+    cnt[XN_RIGHT] = (ull)__popcll(__ballot(nE[1] > 0));
+    cnt[XN_CUT] = tdt_wave_reduce<tdt_sum>((ull)ncut);
+    int nk;                                                        // the keys of the tile (uniform over the workgroup)
+    int slot = ks_stage<CLIP_BLOCK>(nE[0] + nE[1], &nk);           // (+ mine <= nk <= 8 x the reads of the tile)
+    ks_masks M;
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+#pragma unroll
+        for (int c = 1; c <= 4; c++) {
+            if (c <= nE[side]) {
+                const ull k1 = ((ull)c << 56) | eK1[side];
+                M.add(k1, eK2[side][c - 1]);
+                s_k1[slot] = k1;
+                s_k2[slot] = eK2[side][c - 1];
+                slot++;
+            }
+        }
+    }
+    ks_flush<CLIP_BLOCK, XN_PUSH_N>(cnt, M, nk, s_k1, s_k2, k1s, k2s, cap, st);
 }
 
 // ---- the sites of the finish's rows (a = K1, b = K2 with bit 0 clear, ascending by (K1, K2); n rows)
@@ -282,6 +401,12 @@ static void clip_free(tdt_clip *h) {
     if (h->d_site) (void)hipFree(h->d_site);
     if (h->d_align) (void)hipFree(h->d_align);
     if (h->d_far) (void)hipFree(h->d_far);
+    if (h->ext) ks_free(&h->X);
+    if (h->d_xsite) (void)hipFree(h->d_xsite);
+    if (h->d_ins) (void)hipFree(h->d_ins);
+    if (h->d_pairs) (void)hipFree(h->d_pairs);
+    for (int k = 0; k < 4; k++)
+        if (h->ev_ins[k]) (void)hipEventDestroy(h->ev_ins[k]);
     for (int k = 0; k < 5; k++)
         if (h->ev_far[k]) (void)hipEventDestroy(h->ev_far[k]);
     for (int k = 0; k < 2; k++)
@@ -327,7 +452,11 @@ extern "C" int tdt_clip_create(tdt_ctx *ctx, int n_contigs, int min_mapq, int mi
 extern "C" int tdt_clip_destroy(tdt_clip *h) { return ks_destroy(h, clip_free); }
 
 extern "C" int tdt_clip_reset(tdt_clip *h) {
-    if (h) h->n_rows = 0, h->align_valid = h->far_valid = false;
+    if (h) h->n_rows = 0, h->align_valid = h->far_valid = h->ins_valid = false;
+    if (h && h->ext) {
+        const int rc = ks_reset(&h->X);
+        if (rc) return rc;
+    }
     return ks_reset_checked(h ? &h->S : nullptr, "tdt_clip");
 }
 
@@ -339,8 +468,14 @@ static auto clip_launch(tdt_clip *h, size_t n, size_t raw_len) {
             hipLaunchKernelGGL(clip_keys, grid, dim3(CLIP_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, (unsigned)h->min_clip,
                                h->S.k1, h->S.k2, (ull)h->S.cap, h->S.d_state);
         });
-        if (rc == TDT_OK) h->n_rows = 0, h->align_valid = h->far_valid = false;
-        return rc;
+        if (rc == TDT_OK) h->n_rows = 0, h->align_valid = h->far_valid = h->ins_valid = false;
+        if (rc || !h->ext) return rc;
+        // TIDDIT_CLIPS_INS: the extension keys of the same batch into the second store, TDT_CLIP_EXT_MAX_PER_READ slots per read
+        return ks_launch(&h->X, n * TDT_CLIP_EXT_MAX_PER_READ, [&] {
+            const dim3 grid((unsigned)((n + CLIP_K_TILE - 1) / CLIP_K_TILE));
+            hipLaunchKernelGGL(clip_ext_keys, grid, dim3(CLIP_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, (unsigned)h->min_clip,
+                               h->X.k1, h->X.k2, (ull)h->X.cap, h->X.d_state);
+        });
     };
 }
 
@@ -368,42 +503,51 @@ struct clip_work {
     }
 };
 
-// the site launches over the n rows of the keystore's last finish -> got[0] = the sites, got[1] = those with SUPPORT >= min_support
-static int clip_sites_of_rows(tdt_clip *h, size_t n_, unsigned min_support, ull *got) {
-    tdt_ctx *ctx = h->ctx;
+// where the site launches of one key store leave their rows: the handle's fields for that store (the buffer grows)
+struct clip_site_bufs {
+    void *&d_site;
+    size_t &site_cap;
+    clip_sites &rows;
+    size_t &n_rows;
+    double &ms_sites;
+    hipEvent_t *ev;                               // two
+};
+
+// the site launches over the n rows of the last finish of the key store S -> got[0] = the sites, got[1] = those with SUPPORT >=
+// min_support, which become B.rows.  The handle's two stores each bring their own buffers.
+static int clip_sites_of_rows(tdt_ctx *ctx, const tdt_keystore &S, size_t n_, unsigned min_support, clip_site_bufs B, ull *got) {
     got[0] = got[1] = 0;
-    h->ms_sites = 0;
-    h->n_rows = 0;
-    h->align_valid = h->far_valid = false;
+    B.ms_sites = 0;
+    B.n_rows = 0;
     if (!n_) return TDT_OK;
     const int n = (int)n_;                                         // (< 2^30: ks_finish refused more)
     const size_t ntiles = (n_ + KS_TILE - 1) / KS_TILE;
     clip_work K;
     const size_t bytes = K.lay(nullptr, n_, ntiles);
-    if (bytes > h->site_cap) {
-        if (h->d_site) TDT_HIP(hipFree(h->d_site));
-        h->d_site = nullptr;
-        h->site_cap = 0;
-        if (tdt_dev_malloc(&h->d_site, bytes) != hipSuccess) {
+    if (bytes > B.site_cap) {
+        if (B.d_site) TDT_HIP(hipFree(B.d_site));
+        B.d_site = nullptr;
+        B.site_cap = 0;
+        if (tdt_dev_malloc(&B.d_site, bytes) != hipSuccess) {
             tdt_set_error("tdt_clip_finish: out of device memory (%zu rows)", n_);
             return TDT_E_NOMEM;
         }
-        h->site_cap = bytes;
+        B.site_cap = bytes;
     }
-    K.lay(h->d_site, n_, ntiles);
+    K.lay(B.d_site, n_, ntiles);
     hipStream_t st = ctx->stream;
-    const ull *a = h->S.r_k1, *b = h->S.r_k2;
+    const ull *a = S.r_k1, *b = S.r_k2;
     const int nt = (int)ntiles;
     const unsigned vgrid = n_ < CLIP_VOTE_GRID ? (unsigned)n_ : CLIP_VOTE_GRID;
     TDT_HIP(hipMemsetAsync(K.d_out, 0, 2 * 8, st));
-    TDT_HIP(hipEventRecord(h->ev[0], st));
+    TDT_HIP(hipEventRecord(B.ev[0], st));
     hipLaunchKernelGGL(clip_heads<false>, dim3((unsigned)ntiles), dim3(KS_BLOCK), 0, st, a, b, n, K.tile_heads, K.d_out, K.start);
     TDT_CHECK_LAUNCH();
     hipLaunchKernelGGL(ks_carry_sum, dim3(1), dim3(KS_BLOCK), 0, st, K.tile_heads, nt);
     TDT_CHECK_LAUNCH();
     hipLaunchKernelGGL(clip_heads<true>, dim3((unsigned)ntiles), dim3(KS_BLOCK), 0, st, a, b, n, K.tile_heads, K.d_out, K.start);
     TDT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(clip_vote, dim3(vgrid), dim3(CLIP_VOTE_BLOCK), 0, st, a, b, (const unsigned *)h->S.r_sup, (const unsigned *)h->S.r_rev, n,
+    hipLaunchKernelGGL(clip_vote, dim3(vgrid), dim3(CLIP_VOTE_BLOCK), 0, st, a, b, (const unsigned *)S.r_sup, (const unsigned *)S.r_rev, n,
                        (const int *)K.start, (const ull *)K.d_out, min_support, K.V);
     TDT_CHECK_LAUNCH();
     hipLaunchKernelGGL(clip_keep<false>, dim3((unsigned)ntiles), dim3(KS_BLOCK), 0, st, K.V, (const ull *)K.d_out, min_support, K.tile_kept, K.d_out, K.W);
@@ -412,15 +556,15 @@ static int clip_sites_of_rows(tdt_clip *h, size_t n_, unsigned min_support, ull 
     TDT_CHECK_LAUNCH();
     hipLaunchKernelGGL(clip_keep<true>, dim3((unsigned)ntiles), dim3(KS_BLOCK), 0, st, K.V, (const ull *)K.d_out, min_support, K.tile_kept, K.d_out, K.W);
     TDT_CHECK_LAUNCH();
-    TDT_HIP(hipEventRecord(h->ev[1], st));
+    TDT_HIP(hipEventRecord(B.ev[1], st));
     TDT_HIP(hipMemcpyAsync(got, K.d_out, 2 * 8, hipMemcpyDeviceToHost, st));
     const int rc = tdt_ctx_sync(ctx);
     if (rc) return rc;
     float ms = 0;
-    TDT_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->ms_sites = ms;
-    h->rows = K.W;
-    h->n_rows = (size_t)got[1];
+    TDT_HIP(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
+    B.ms_sites = ms;
+    B.rows = K.W;
+    B.n_rows = (size_t)got[1];
     return TDT_OK;
 }
 
@@ -432,7 +576,9 @@ extern "C" int tdt_clip_finish(tdt_clip *h, uint64_t min_support, uint64_t *sn_o
     // (a minimum support of 1 for the runs: every distinct sequence is a row)
     int rc = ks_finish_counted(h ? &h->S : nullptr, "tdt_clip", h && sn_out && n_rows, min_support, TDT_CLIP_MAX_SUPPORT, 1, SN_PUSH_N, res, seqs);
     if (rc) return rc;
-    rc = clip_sites_of_rows(h, h->S.n_rows, (unsigned)min_support, sites);
+    h->align_valid = h->far_valid = h->ins_valid = false;
+    h->last_support = (unsigned)min_support;
+    rc = clip_sites_of_rows(h->ctx, h->S, h->S.n_rows, (unsigned)min_support, clip_site_bufs{h->d_site, h->site_cap, h->rows, h->n_rows, h->ms_sites, h->ev}, sites);
     if (rc) {
         h->S.rows_valid = false;
         return rc;
@@ -710,5 +856,215 @@ extern "C" int tdt_clip_far_timing(tdt_clip *h, double *ms4) {
         return TDT_E_ARG;
     }
     for (int k = 0; k < 4; k++) ms4[k] = h->ms_far[k];
+    return TDT_OK;
+}
+
+// ---- TIDDIT_CLIPS_INS: the second store, and the rows of the last finish extended, paired and closed where they lie (csrc/tdt_clip_ins.hip)
+// The store of the extension keys, of `capacity` keys.  Before the first push only (the two stores hold the same reads): a handle that
+// has it already, or that has been pushed to, is refused with TDT_E_ARG.
+extern "C" int tdt_clip_ext_enable(tdt_clip *h, size_t capacity) {
+    if (!h || h->ext || h->S.upper) {
+        tdt_set_error("tdt_clip_ext_enable: bad argument, enabled already, or pushed to already");
+        return TDT_E_ARG;
+    }
+    if (capacity >= (1ull << 40)) {
+        tdt_set_error("tdt_clip_ext_enable: capacity %zu", capacity);
+        return TDT_E_RANGE;
+    }
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    int rc = ks_init(&h->X, h->ctx, "tdt_clip_ext", XT_OR1, capacity);
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4 && rc == TDT_OK && e == hipSuccess; k++) e = hipEventCreate(&h->ev_ins[k]);
+    if (rc == TDT_OK && e != hipSuccess) {
+        tdt_set_error("tdt_clip_ext_enable: %s", hipGetErrorString(e));
+        rc = TDT_E_HIP;
+    }
+    if (rc) {
+        ks_free(&h->X);
+        for (int k = 0; k < 4; k++) {
+            if (h->ev_ins[k]) (void)hipEventDestroy(h->ev_ins[k]);
+            h->ev_ins[k] = nullptr;
+        }
+        h->X = tdt_keystore{};
+        return rc;
+    }
+    h->ext = true;
+    return TDT_OK;
+}
+
+extern "C" int tdt_clip_ext_keys(tdt_clip *h, uint64_t *k1, uint64_t *k2, size_t *n) {
+    return ks_keys(h && h->ext ? &h->X : nullptr, "tdt_clip_ext", k1, k2, n);
+}
+
+struct clip_ins_bufs {
+    unsigned *eclen;
+    ull *cons5, *sn;
+    ins_work Wk;
+    size_t lay(void *base, size_t n) {
+        tdt_carver cv(base);
+        eclen = cv.take<unsigned>(n), cons5 = cv.take<ull>(n * TDT_CLIP_EXT_WORDS), sn = cv.take<ull>(TDT_CLIP_INS_SN_N);
+        const size_t head = cv.size;
+        return head + Wk.lay(base ? (char *)base + head : nullptr, n);
+    }
+};
+
+// a buffer of the handle that only grows
+static int clip_grow(const char *fn, void **d, size_t *cap, size_t bytes) {
+    if (bytes <= *cap) return TDT_OK;
+    if (*d) TDT_HIP(hipFree(*d));
+    *d = nullptr;
+    *cap = 0;
+    if (tdt_dev_malloc(d, bytes) != hipSuccess) {
+        tdt_set_error("%s: out of device memory (%zu bytes)", fn, bytes);
+        return TDT_E_NOMEM;
+    }
+    *cap = bytes;
+    return TDT_OK;
+}
+
+// sn_out: uint64[TDT_CLIP_INS_SN_N].  The extension store is finished with the minimum support of the last tdt_clip_finish, its
+// chunks are gathered onto that finish's rows, and the rows are paired and closed.  No finish since the last push or reset, or no
+// tdt_clip_ext_enable: TDT_E_ARG.
+extern "C" int tdt_clip_ins(tdt_clip *h, int K, int O, int M, uint64_t *sn_out) {
+    if (!h || !sn_out) {
+        tdt_set_error("tdt_clip_ins: bad argument");
+        return TDT_E_ARG;
+    }
+    if (!h->ext || !h->S.rows_valid) {
+        tdt_set_error("tdt_clip_ins: %s", h->ext ? "no finish since the last push or reset" : "no tdt_clip_ext_enable");
+        return TDT_E_ARG;
+    }
+    int rc = ins_check_range("tdt_clip_ins", K, O, M);
+    if (rc) return rc;
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    h->ins_valid = false;
+    h->n_pairs = 0;
+    for (int k = 0; k < 3; k++) h->ms_ins[k] = 0;
+    hipStream_t st = h->ctx->stream;
+    // ---- the extension store's (chunk, site) rows: the finish of the first store, on the second
+    ull state[KS_WORDS], runs[2], sites[2];
+    rc = ks_stored(&h->X, state);
+    if (rc) return rc;
+    TDT_HIP(hipEventRecord(h->ev_ins[0], st));
+    rc = ks_finish(&h->X, state, 1, runs);
+    if (rc == TDT_OK)
+        rc = clip_sites_of_rows(h->ctx, h->X, h->X.n_rows, h->last_support, clip_site_bufs{h->d_xsite, h->xsite_cap, h->xrows, h->n_xrows, h->ms_xsites, h->ev}, sites);
+    if (rc) return rc;
+    // ---- the gather onto the base rows, then the pairs
+    const size_t n = h->n_rows;
+    clip_ins_bufs A;
+    rc = clip_grow("tdt_clip_ins", &h->d_ins, &h->ins_cap, A.lay(nullptr, n));
+    if (rc) return rc;
+    A.lay(h->d_ins, n);
+    uint64_t res[TDT_CLIP_INS_SN_N] = {};
+    const clip_sites &R = h->rows, &X = h->xrows;
+    TDT_HIP(hipMemsetAsync(A.sn, 0, sizeof res, st));
+    TDT_HIP(hipEventRecord(h->ev_ins[1], st));
+    rc = ins_gather_launch(h->ctx, n, R.k1, R.side, R.clen, R.cons, h->n_xrows, ins_chunks{X.k1, X.side, X.clen, X.cons}, A.eclen, A.cons5);
+    if (rc) return rc;
+    TDT_HIP(hipEventRecord(h->ev_ins[2], st));
+    const ins_sites S{R.k1, R.side, A.eclen, A.cons5};
+    rc = ins_count_launch(h->ctx, n, S, K, A.Wk, A.sn);
+    if (rc) return rc;
+    TDT_HIP(hipMemcpyAsync(res, A.sn, sizeof res, hipMemcpyDeviceToHost, st));
+    rc = tdt_ctx_sync(h->ctx);
+    if (rc) return rc;
+    const size_t np = (size_t)res[IN_PAIRS];                              // (the pairs: rows for them are made now)
+    ins_out P{};
+    rc = clip_grow("tdt_clip_ins", &h->d_pairs, &h->pairs_cap, P.lay(nullptr, np));
+    if (rc) return rc;
+    P.lay(h->d_pairs, np);
+    rc = ins_pairs_launch(h->ctx, n, S, K, O, M, A.Wk, np, P, A.sn);
+    if (rc) return rc;
+    TDT_HIP(hipEventRecord(h->ev_ins[3], st));
+    TDT_HIP(hipMemcpyAsync(res, A.sn, sizeof res, hipMemcpyDeviceToHost, st));
+    rc = tdt_ctx_sync(h->ctx);
+    if (rc) return rc;
+    for (int k = 0; k < 3; k++) {
+        float ms = 0;
+        TDT_HIP(hipEventElapsedTime(&ms, h->ev_ins[k], h->ev_ins[k + 1]));
+        h->ms_ins[k] = ms;
+    }
+    res[IN_EXT_LEFT] = state[XN_LEFT], res[IN_EXT_RIGHT] = state[XN_RIGHT], res[IN_EXT_KEYS] = state[KS_N], res[IN_CUT] = state[XN_CUT];
+    h->ext_eclen = A.eclen, h->ext_cons5 = A.cons5;
+    h->pairs = P;
+    h->n_pairs = np;
+    h->ins_valid = true;
+    memcpy(sn_out, res, sizeof res);
+    return TDT_OK;
+}
+
+// ECLEN and the five words of every row of the last finish, as the last tdt_clip_ins gathered them, in the order of tdt_clip_rows.
+// *n in: the room of the arrays (ignored when both are NULL), out: the rows.  Too little room: TDT_E_RANGE, nothing written.
+extern "C" int tdt_clip_ext_rows(tdt_clip *h, uint32_t *eclen, uint64_t *cons5, size_t *n) {
+    if (!h || !n || ((eclen || cons5) && !(eclen && cons5))) {
+        tdt_set_error("tdt_clip_ext_rows: bad argument");
+        return TDT_E_ARG;
+    }
+    if (!h->S.rows_valid || !h->ins_valid) {
+        tdt_set_error("tdt_clip_ext_rows: no tdt_clip_ins since the last push, reset or finish");
+        return TDT_E_ARG;
+    }
+    const size_t have = h->n_rows;
+    if (eclen) {
+        if (*n < have) {
+            tdt_set_error("tdt_clip_ext_rows: room for %zu rows, %zu kept", *n, have);
+            return TDT_E_RANGE;
+        }
+        if (have) {
+            TDT_HIP(hipSetDevice(h->ctx->device));
+            hipStream_t st = h->ctx->stream;
+            TDT_HIP(hipMemcpyAsync(eclen, h->ext_eclen, have * 4, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipMemcpyAsync(cons5, h->ext_cons5, have * TDT_CLIP_EXT_WORDS * 8, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipStreamSynchronize(st));
+        }
+    }
+    *n = have;
+    return TDT_OK;
+}
+
+// The pairs of the last tdt_clip_ins, ascending by (t, P_R, P_L): the two rows' indices into tdt_clip_rows, TSD, status (1 closed),
+// LEN, MISMATCH, CLOSURES and TDT_CLIP_INS_SEQ_WORDS words of SEQ.  *n in: the room of the arrays (ignored when all eight are NULL),
+// out: the pairs.  Too little room: TDT_E_RANGE, nothing written.
+extern "C" int tdt_clip_ins_rows(tdt_clip *h, uint32_t *r_row, uint32_t *l_row, uint32_t *tsd, uint32_t *status, uint32_t *len, uint32_t *mm, uint32_t *closures,
+                                 uint64_t *seq10, size_t *n) {
+    const bool any = r_row || l_row || tsd || status || len || mm || closures || seq10;
+    if (!h || !n || (any && !(r_row && l_row && tsd && status && len && mm && closures && seq10))) {
+        tdt_set_error("tdt_clip_ins_rows: bad argument");
+        return TDT_E_ARG;
+    }
+    if (!h->S.rows_valid || !h->ins_valid) {
+        tdt_set_error("tdt_clip_ins_rows: no tdt_clip_ins since the last push, reset or finish");
+        return TDT_E_ARG;
+    }
+    const size_t have = h->n_pairs;
+    if (any) {
+        if (*n < have) {
+            tdt_set_error("tdt_clip_ins_rows: room for %zu pairs, %zu kept", *n, have);
+            return TDT_E_RANGE;
+        }
+        if (have) {
+            TDT_HIP(hipSetDevice(h->ctx->device));
+            hipStream_t st = h->ctx->stream;
+            const ins_out &P = h->pairs;
+            uint32_t *dst[7] = {r_row, l_row, tsd, status, len, mm, closures};
+            const unsigned *src[7] = {P.r_row, P.l_row, P.tsd, P.status, P.len, P.mm, P.closures};
+            for (int k = 0; k < 7; k++) TDT_HIP(hipMemcpyAsync(dst[k], src[k], have * 4, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipMemcpyAsync(seq10, P.seq10, have * INS_SEQ_WORDS * 8, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipStreamSynchronize(st));
+        }
+    }
+    *n = have;
+    return TDT_OK;
+}
+
+// device milliseconds of the last tdt_clip_ins: ms3 = the extension store's finish (sort, run lengths, site launches), the gather,
+// the pair launches (count, offsets, rows, closure)
+extern "C" int tdt_clip_ins_timing(tdt_clip *h, double *ms3) {
+    if (!h || !ms3 || !h->S.rows_valid || !h->ins_valid) {
+        tdt_set_error("tdt_clip_ins_timing: bad argument, or no tdt_clip_ins since the last push, reset or finish");
+        return TDT_E_ARG;
+    }
+    for (int k = 0; k < 3; k++) ms3[k] = h->ms_ins[k];
     return TDT_OK;
 }

@@ -18,14 +18,13 @@
 #include "tdt_batch.h"
 #include "tdt_bam_record.h"
 
-namespace {
-
-typedef unsigned long long ks_ull;
-
 #define KS_BLOCK 256
 #define KS_TILE 4096                          // keys of a run-length workgroup: KS_BLOCK lanes, KS_TILE / KS_BLOCK rounds
+#include "tdt_keyscan.h"                      // ks_block_scan, ks_carry_sum: in a header of their own, for launches that have no store
+
+namespace {
+
 enum { KS_N = 16, KS_OVERFLOW, KS_WORDS = 32 };
-static_assert(KS_TILE % KS_BLOCK == 0, "whole rounds");
 static_assert(KS_N * 8 % 128 == 0, "the store-slot atomic has a cache line of its own");
 
 struct tdt_keystore {
@@ -54,29 +53,6 @@ __global__ __launch_bounds__(KS_BLOCK) void ks_iota(unsigned *__restrict__ v, in
 __global__ __launch_bounds__(KS_BLOCK) void ks_gather(ks_ull *__restrict__ dst, const ks_ull *__restrict__ src, const unsigned *__restrict__ perm, int n) {
     const int i = blockIdx.x * KS_BLOCK + threadIdx.x;
     if (i < n) dst[i] = src[perm[i]];
-}
-
-// inclusive scan over the workgroup's 256 threads, in thread order (Op: tdt_max or tdt_sum; `none` its neutral element);
-// *total = the reduction of all (s: KS_BLOCK / 64 words)
-template <class Op> __device__ __forceinline__ int ks_block_scan(int v, int none, int *s, int t, int *total) {
-    const int lane = t & 63, wave = t >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o);
-        if (lane >= o) v = Op::of(v, u);
-    }
-    if (lane == 63) s[wave] = v;
-    __syncthreads();
-    int all = none;
-#pragma unroll
-    for (int w = 0; w < KS_BLOCK / 64; w++) {
-        const int c = s[w];
-        if (w < wave) v = Op::of(v, c);
-        all = Op::of(all, c);
-    }
-    __syncthreads();
-    *total = all;
-    return v;
 }
 
 // ---- the push side: what every *_keys kernel does in front of and behind its own walk of a record
@@ -256,21 +232,6 @@ __global__ __launch_bounds__(KS_BLOCK) void ks_carry(int *__restrict__ tile_last
             if (k < ntiles) v_[k] = v;
             running = all > running ? all : running;
         }
-    }
-}
-
-// ONE workgroup: tile_kept[k] = the kept runs of the tiles in front of tile k (an exclusive sum; the total is below 2^30)
-__global__ __launch_bounds__(KS_BLOCK) void ks_carry_sum(int *__restrict__ tile_kept, int ntiles) {
-    __shared__ int s[KS_BLOCK / 64];
-    const int t = threadIdx.x;
-    int running = 0;
-    for (int c = 0; c < ntiles; c += KS_BLOCK) {                   // (uniform)
-        const int k = c + t;
-        const int mine = k < ntiles ? tile_kept[k] : 0;
-        int all;
-        const int v = ks_block_scan<tdt_sum>(mine, 0, s, t, &all);
-        if (k < ntiles) tile_kept[k] = running + v - mine;
-        running += all;
     }
 }
 

@@ -42,8 +42,10 @@ mate's ``POS`` and ``HOM`` the homology, or ``.``.
 
 Other contigs (translocations) and placements beyond the window are tiddit_clip_far.py's (``TIDDIT_CLIPS_FAR``), by an exact seed.
 
-NOT built: gapped placements, more than the 28 consensus columns, mates of INV rows, joining the rows
-to the SV candidates or the VCF.
+Sites that place nowhere and face each other are tiddit_clip_ins.py's (``TIDDIT_CLIPS_INS``): insertions, closed from up to 140 columns.
+
+NOT built: gapped placements, searching with more than the 28 consensus columns (the 140 of ``TIDDIT_CLIPS_INS`` are not searched), mates
+of INV rows, joining the rows to the SV candidates or the VCF.
 """
 import ctypes
 import time

@@ -39,8 +39,11 @@ at 1-based ``q`` (refseq.CODES); a code that is not A, C, G or T equals no conse
 order of ``SN``, then ``#CHROM POS SIDE SUPPORT CLEN PCHROM PARTNER STRAND MISMATCH HITS TYPE LEN MATE_CHROM MATE HOM`` and one row per
 SEARCHED site, in the order of ``{o}.clips.tab``, all tab-separated, ``.`` where there is nothing (an unplaced site has no partner).
 
-NOT built: mismatches inside the seed (spaced or multiple seeds), gapped placements, more than the 28 consensus columns, mates of
-reverse-strand rows, joining the rows to the SV candidates or the VCF, N ranks.
+A site whose consensus places nowhere is sequence the reference does not hold: two such sites that face each other are an insertion,
+which tiddit_clip_ins.py (``TIDDIT_CLIPS_INS``) pairs and closes from up to 140 clipped columns per side.
+
+NOT built: mismatches inside the seed (spaced or multiple seeds), gapped placements, searching with more than the 28 consensus columns
+(the 140 of ``TIDDIT_CLIPS_INS`` are not searched), mates of reverse-strand rows, joining the rows to the SV candidates or the VCF, N ranks.
 """
 import ctypes
 import time

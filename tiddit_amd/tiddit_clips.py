@@ -49,15 +49,20 @@ so the columns of an ``L`` site are reversed, and is ``.`` when ``CLEN`` is 0; `
 Where the clipped bases come from is tiddit_clip_align.py's (``TIDDIT_CLIPS_ALIGN``): the consensus placed on the same contig, and the
 DEL / DUP / INV the junction implies; and tiddit_clip_far.py's (``TIDDIT_CLIPS_FAR``): the consensus placed on any contig by its seed.
 
-NOT built: the clip's full length, or more than 28 bases of it; joining the sites to the VCF; hard clips (``H`` alone is no clip, and
+Clipped bases beyond the 28 columns, up to 140, and the insertions that two facing sites close are tiddit_clip_ins.py's
+(``TIDDIT_CLIPS_INS``), from a second key store beside this one (:meth:`ClipCounter.enable_ext`).
+
+NOT built: more than 140 clipped bases of a clip; joining the sites to the VCF; hard clips (``H`` alone is no clip, and
 the bases it removed are not in the record); supplementary records (0x800 is not eligible); N ranks (refused in ``__main__.run_sv``: a
 site's keys can straddle shards).
 """
+import ctypes
 import struct
 import time
 
 import numpy
 
+from . import _native
 from .bamio import _raw_of
 from .keyed_counter import KeyedCounter
 
@@ -103,13 +108,13 @@ def parse_switch(value):
 
 
 # ------------------------------------------------------------------------------------------- the definition
-def events_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq=DEFAULT_MAPQ, min_clip=DEFAULT_CLIP):
-    """THE DEFINITION, one read -> (kind, keys, short_clips, cut): ``keys`` the read's [(K1, K2)] (at most two, the leading clip's
-    first) when kind is OK, else []; the two counts are what the read adds to ``SN short_clips`` / ``SN cut_at_other_base``.  ``raw``:
-    the batch's record bytes (bytes-like), the other arguments the read's entries of the batch's columns."""
+def clips_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq=DEFAULT_MAPQ, min_clip=DEFAULT_CLIP):
+    """rules 1 to 4, one read -> (kind, clips, short_clips, base): ``clips`` the read's events before their bases are taken,
+    [(side, P, cliplen, q0)] (the leading clip's first) when kind is OK, else []; column ``j`` of a clip is the query base at index
+    ``q0 - j`` (L) or ``q0 + j`` (R), and ``base(qi)`` gives a query base's 4-bit code (None unless kind is OK)"""
     if flag & 0xF04 or tid < 0 or mapq < min_mapq:
-        return NOT_ELIGIBLE, [], 0, 0
-    bad = (MALFORMED, [], 0, 0)
+        return NOT_ELIGIBLE, [], 0, None
+    bad = (MALFORMED, [], 0, None)
     raw_len = len(raw)
     if tid >= CLIP_MAX_CONTIGS or pos < 0 or rec_off + 36 > raw_len:
         return bad
@@ -129,17 +134,16 @@ def events_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq=DEFAULT_MAPQ, mi
     if pos + ref_len > END_LIMIT or (L >= 1 and n_cig >= 1 and query_len != L):
         return bad
     if n_cig == 0 or L == 0:
-        return NO_SEQUENCE, [], 0, 0
+        return NO_SEQUENCE, [], 0, None
     if ref_len == 0:
-        return NO_ALIGNMENT, [], 0, 0
+        return NO_ALIGNMENT, [], 0, None
     seq = cig + 4 * n_cig
-    rev = (flag >> 4) & 1
     ops = [(w & 0xf, w >> 4) for w in words]
     lead = 0 if ops[0][0] == 4 else 1 if ops[0][0] == 5 and n_cig >= 2 and ops[1][0] == 4 else None
     trail = n_cig - 1 if ops[-1][0] == 4 else n_cig - 2 if ops[-1][0] == 5 and n_cig >= 2 and ops[-2][0] == 4 else None
     assert lead is None or lead != trail
     base = lambda qi: (raw[seq + (qi >> 1)] >> (0 if qi & 1 else 4)) & 0xf
-    keys, short, cut = [], 0, 0
+    clips, short = [], 0
     for side, at in ((0, lead), (1, trail)):
         if at is None:
             continue
@@ -147,17 +151,34 @@ def events_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq=DEFAULT_MAPQ, mi
         if cliplen < min_clip:
             short += 1
             continue
-        n, bases = 0, 0
-        while n < min(cliplen, CLIP_COLS):
-            c = base(cliplen - 1 - n if side == 0 else L - cliplen + n)
-            if c not in _CODE:
-                break
-            bases |= _CODE[c] << (2 * n)
-            n += 1
+        clips.append((side, pos + 1 if side == 0 else pos + ref_len, cliplen, cliplen - 1 if side == 0 else L - cliplen))
+    return OK, clips, short, base
+
+
+def kept_bases(side, cliplen, q0, base, cols):
+    """rule 5 up to ``cols`` columns -> the kept codes (0 ... 3) outward from the breakpoint, cut at the first other base"""
+    out = []
+    while len(out) < min(cliplen, cols):
+        c = base(q0 - len(out) if side == 0 else q0 + len(out))
+        if c not in _CODE:
+            break
+        out.append(_CODE[c])
+    return out
+
+
+def events_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq=DEFAULT_MAPQ, min_clip=DEFAULT_CLIP):
+    """THE DEFINITION, one read -> (kind, keys, short_clips, cut): ``keys`` the read's [(K1, K2)] (at most two, the leading clip's
+    first) when kind is OK, else []; the two counts are what the read adds to ``SN short_clips`` / ``SN cut_at_other_base``.  ``raw``:
+    the batch's record bytes (bytes-like), the other arguments the read's entries of the batch's columns."""
+    kind, clips, short, base = clips_of_read(flag, tid, pos, mapq, rec_off, raw, min_mapq, min_clip)
+    rev = (flag >> 4) & 1
+    keys, cut = [], 0
+    for side, P, cliplen, q0 in clips:
+        kept = kept_bases(side, cliplen, q0, base, CLIP_COLS)
+        n, bases = len(kept), sum(c << (2 * j) for j, c in enumerate(kept))
         cut += int(n < min(cliplen, CLIP_COLS))
-        P = pos + 1 if side == 0 else pos + ref_len
         keys.append((tid << 32 | P, side << 63 | n << 58 | bases << 2 | rev))
-    return OK, keys, short, cut
+    return kind, keys, short, cut
 
 
 def _count(sn, kind, keys, short, cut):
@@ -242,6 +263,48 @@ class ClipCounter(KeyedCounter):
         self._create(ctx, int(n_contigs), int(min_mapq), int(min_clip), int(capacity))
         self.min_mapq, self.min_clip = int(min_mapq), int(min_clip)
 
+    # ---- TIDDIT_CLIPS_INS (tiddit_clip_ins.py): a second store for the clipped bases beyond column 28, filled by every later push
+    def enable_ext(self, capacity=1 << 20):
+        """``tdt_clip_ext_enable``: before the first push"""
+        _native.check(self._c("ext_enable")(self.handle, int(capacity)))
+
+    def ext_keys(self):
+        """-> (K1 uint64[], K2 uint64[]): the extension store as it lies in HBM"""
+        n = ctypes.c_size_t(0)
+        _native.check(self._c("ext_keys")(self.handle, None, None, ctypes.byref(n)))
+        k1, k2 = numpy.zeros(n.value, dtype=numpy.uint64), numpy.zeros(n.value, dtype=numpy.uint64)
+        if n.value:
+            _native.check(self._c("ext_keys")(self.handle, _native.ptr(k1), _native.ptr(k2), ctypes.byref(n)))
+        return k1, k2
+
+    def ins(self, K, O, M):
+        """``tdt_clip_ins`` on the rows of the last finish, where they lie -> uint64[tiddit_clip_ins.SIZE]"""
+        from . import tiddit_clip_ins
+        sn = numpy.zeros(tiddit_clip_ins.SIZE, dtype=numpy.uint64)
+        _native.check(self._c("ins")(self.handle, int(K), int(O), int(M), _native.ptr(sn)))
+        self._n_pairs = int(sn[tiddit_clip_ins.SN_INDEX["pairs"]])
+        return sn
+
+    def ext_rows(self):
+        """-> (ECLEN uint32[], cons5 uint64[n][5]) of the last ``ins``, in the order of ``rows()``"""
+        n = ctypes.c_size_t(self._n_rows)
+        eclen, cons5 = numpy.zeros(n.value, dtype=numpy.uint32), numpy.zeros((n.value, 5), dtype=numpy.uint64)
+        if n.value:
+            _native.check(self._c("ext_rows")(self.handle, _native.ptr(eclen), _native.ptr(cons5), ctypes.byref(n)))
+        return eclen, cons5
+
+    def ins_rows(self):
+        """-> ((R row, L row, TSD, status, LEN, MISMATCH, CLOSURES) uint32[], seq10 uint64[n][10]) of the last ``ins``"""
+        n = ctypes.c_size_t(getattr(self, "_n_pairs", 0))
+        cols, seq10 = [numpy.zeros(n.value, dtype=numpy.uint32) for _ in range(7)], numpy.zeros((n.value, 10), dtype=numpy.uint64)
+        if n.value:
+            _native.check(self._c("ins_rows")(self.handle, *[_native.ptr(c) for c in cols], _native.ptr(seq10), ctypes.byref(n)))
+        return tuple(cols), seq10
+
+    def ins_timing(self):
+        """ms of the last ``ins``: [the extension store's finish, the gather, the pair launches]"""
+        return self._out("ins_timing", 3, numpy.float64)
+
 
 # ------------------------------------------------------------------------------------------- the file
 def write_file(path, counts, rows, names, coverage_data, min_support, min_mapq, min_clip):
@@ -270,12 +333,13 @@ def summary_line(counts):
                                         "malformed")))
 
 
-def main(counter, prefix, coverage_data, names, S, align=None, far=None):
+def main(counter, prefix, coverage_data, names, S, align=None, far=None, ins=None):
     """the stage behind the scan: the sort, the run lengths and the vote on the device, the file and the summary line.  ``align``:
     None, or (reference, W, K, M) of ``TIDDIT_CLIPS_ALIGN`` — the rows are then realigned where they lie, behind the finish and before
     the counter is closed (tiddit_clip_align.main, which writes ``{o}.clips.align.tab``); ``far``: None, or (reference, K, M) of
     ``TIDDIT_CLIPS_FAR`` — the rows are placed genome-wide the same way (tiddit_clip_far.main, ``{o}.clips.far.tab``); the reference is not
-    closed here"""
+    closed here; ``ins``: None, or (K, O, M) of ``TIDDIT_CLIPS_INS`` — the counter has its extension store (``enable_ext``), and the rows are
+    extended, paired and closed where they lie (tiddit_clip_ins.main, ``{o}.clips.ins.tab``)"""
     STAGE_SECONDS.clear()
     STAGE_NOTES.clear()
     t = time.time()
@@ -304,6 +368,16 @@ def main(counter, prefix, coverage_data, names, S, align=None, far=None):
             counter.close()
             raise
         t += time.time() - t_far                                # (the same: tiddit_clip_far.STAGE_SECONDS)
+    ins_counts = None
+    if ins is not None:
+        from . import tiddit_clip_ins
+        t_ins = time.time()
+        try:
+            ins_counts = tiddit_clip_ins.main(counter, rows, prefix, names, *ins)
+        except BaseException:
+            counter.close()
+            raise
+        t += time.time() - t_ins                                # (the same: tiddit_clip_ins.STAGE_SECONDS)
     counter.close()
     STAGE_SECONDS["clip sites (device: two sorts, gather, run lengths, site heads, vote, rows)"] = time.time() - t
     for k, v in zip(("sort by K2", "gather of K1", "sort by K1", "run lengths + rows", "site heads + vote + site rows"), ms.tolist()):
@@ -318,4 +392,6 @@ def main(counter, prefix, coverage_data, names, S, align=None, far=None):
         print(tiddit_clip_align.summary_line(align_counts))
     if far_counts is not None:
         print(tiddit_clip_far.summary_line(far_counts))
+    if ins_counts is not None:
+        print(tiddit_clip_ins.summary_line(ins_counts))
     return counts

@@ -410,6 +410,10 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         #  file's bound; the store grows 1.5x when a batch does not fit)
         clipc = tiddit_clips.ClipCounter(len(names), CLIPS[1], CLIPS[2], capacity=min(max(os.path.getsize(bam_file_name) // 32, 1 << 16), 1 << 26),
                                          ctx=getattr(reader, "ctx", None))
+        if CLIPS_INS:
+            # TIDDIT_CLIPS_INS: a second store for the clipped bases beyond column 28, one more launch per batch inside the same push
+            # (room for 8 keys per read is reserved before each launch, behind which a reserve asks the device for the real count)
+            clipc.enable_ext(capacity=min(max(os.path.getsize(bam_file_name) // 16, 1 << 16), 1 << 26))
         T["clip keys (push)"] = 0.0
     tables = data = splits = clips = None
     if isinstance(reader, DeviceBamReader):
@@ -699,6 +703,7 @@ SNVS = None                 # (min_support, min_mapq, min_bq): the scan also sto
 SNV_REFERENCE = None        # a refseq.RefSeq: the reference the SNV counter compares with (TIDDIT_SNVS; the same handle as INDEL_REFERENCE when both are set)
 SNV_COUNTER = None          # that counter after the last scan that had SNVS set (the caller runs its finish and closes it), else None
 CLIPS = None                # (min_support, min_mapq, min_clip): the scan also stores a key per soft clip of the reads (tiddit_clips.ClipCounter), one launch per batch
+CLIPS_INS = False           # with CLIPS: the counter also stores the clipped bases beyond column 28 (ClipCounter.enable_ext; tiddit_clip_ins.py)
 CLIP_COUNTER = None         # that counter after the last scan that had CLIPS set (the caller runs its finish and closes it), else None
 INDEL_COUNTER = None        # that counter after the last scan that had INDELS set (the caller runs its finish and closes it), else None
 KEEP_EVIDENCE = False       # the scan packs every placed record into an evidence store for the variant stage (tiddit_variant.LIVE_STORE)

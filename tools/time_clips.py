@@ -13,8 +13,12 @@ With --far the record is about TIDDIT_CLIPS_FAR: the job with the switches off, 
 in one process; `far_scan`'s device time against `clip_align_sites` at W = 2^20 on the same sites scaled to the genome's length (the
 brute-force alternative) and against a plain streaming read of the packed store's bytes; written to profiles/clips_far_<mb>mb.md.
 
+With --ins the record is about TIDDIT_CLIPS_INS: the job with the switches off, with TIDDIT_CLIPS alone and with the extension store and
+the pair stage, interleaved in one process; the push of every batch with and without `clip_ext_keys` beside `clip_keys` (the stream idle,
+best of 4); the device events of the extension finish, the gather and the pair launches; written to profiles/clips_ins_<mb>mb.md.
+
 usage: python tools/time_clips.py (--bam WGS.bam --ref ref.fa | --mb 240) [--reps 3] [--switch 1] [--align [--align-switch 1]] [--far [--far-switch 1]]
-                                  [--out FILE.md]
+                                  [--ins [--ins-switch 1]] [--out FILE.md]
 (--mb: bench.py's synthetic file of that genome size, made at $TIDDIT_BENCH_TMP/tiddit_bench_sv_<mb>/ when it is not there)"""
 import argparse
 import contextlib
@@ -44,8 +48,9 @@ LABELS = {"wall": "whole job", "scan": "scan stage", "push": "new stage timer (p
 NOTES = ("clip store: reserves that asked the device", "clip store: growths", "clip store: capacity (keys)", "clip store: keys")
 
 
-def keys_alone(bam, min_mapq, min_clip):
-    """every batch of the file through tdt_clip_push_device with the stream idle around it -> per batch (reads, raw bytes, ms of the launch)"""
+def keys_alone(bam, min_mapq, min_clip, ext=False):
+    """every batch of the file through tdt_clip_push_device with the stream idle around it -> per batch (reads, raw bytes, ms of the launch);
+    ``ext``: on a handle with the extension store, so the push is `clip_keys` and `clip_ext_keys`"""
     from tiddit_amd import bamio, tiddit_clips
     rd = bamio.DeviceBamReader(bam)
     h = None
@@ -54,6 +59,8 @@ def keys_alone(bam, min_mapq, min_clip):
         for b in rd.batches():
             if h is None:                                # (room for the largest batch's bound: no reserve asks or grows inside the timing)
                 h = tiddit_clips.ClipCounter(len(rd.references), min_mapq, min_clip, capacity=2 * len(b) + 4096, ctx=rd.ctx)
+                if ext:
+                    h.enable_ext(8 * len(b) + 4096)
             rd.ctx.sync()
             best = None
             for _ in range(4):                           # (the first one warms up)
@@ -81,9 +88,9 @@ ALIGN_LABELS = {"wall": "whole job", "scan": "scan stage", "reference": "referen
                 "align text": "align: mates and file text (host)"}
 
 
-def _one_job(cli, ctx, bam, ref, out, clips=None, align=None, far=None, keys=None):
+def _one_job(cli, ctx, bam, ref, out, clips=None, align=None, far=None, keys=None, ins=None):
     """one `--sv --skip_assembly` job in this process -> its wall seconds and stage seconds by short name"""
-    for k, v in (("TIDDIT_CLIPS", clips), ("TIDDIT_CLIPS_ALIGN", align), ("TIDDIT_CLIPS_FAR", far)):
+    for k, v in (("TIDDIT_CLIPS", clips), ("TIDDIT_CLIPS_ALIGN", align), ("TIDDIT_CLIPS_FAR", far), ("TIDDIT_CLIPS_INS", ins)):
         os.environ.pop(k, None)
         if v is not None:
             os.environ[k] = v
@@ -96,10 +103,112 @@ def _one_job(cli, ctx, bam, ref, out, clips=None, align=None, far=None, keys=Non
         os.environ.pop("TIDDIT_CLIPS", None)
         os.environ.pop("TIDDIT_CLIPS_ALIGN", None)
         os.environ.pop("TIDDIT_CLIPS_FAR", None)
+        os.environ.pop("TIDDIT_CLIPS_INS", None)
     Sx = {k.strip(): v for k, v in cli.STAGE_SECONDS.items()}
     rec = {"wall": time.perf_counter() - t0}
     rec.update({short: Sx[key] for short, key in (keys or ALIGN_KEYS) if key in Sx})
     return rec
+
+
+INS_MODES = ("off", "clips", "ins")
+INS_KEYS = (("scan", "signal extraction + coverage"), ("push", "clip keys (push)"), ("ingest wait", "ingest (inflate + decode, device)"),
+            ("clip stage", "clip sites ({o}.clips.tab)"), ("ins", "clip ins (device: extension finish, gather, pairs)"),
+            ("ext finish", "clip ins extension finish (sort, run lengths, vote) (device time)"), ("gather", "clip ins gather of the extended consensus (device time)"),
+            ("pairs", "clip ins pair count + closure (device time)"), ("ins text", "clip ins table text (host)"))
+INS_LABELS = {"wall": "whole job", "scan": "scan stage", "push": "stage timer of the pushes (host side, reserve waits included)",
+              "ingest wait": "scan: waited for the ingest", "clip stage": "clip stage (finish, ins, files)",
+              "ins": "ins: the calls into the library (launches, waits, columns read out)",
+              "ext finish": "ins: the extension store's finish, between its events (device, with the host's waits between the launches)",
+              "gather": "ins: `clip_ext_gather` (device)", "pairs": "ins: `clip_ins_count` x 2, `ks_carry_sum`, `clip_ins_pairs` (device, with the host's wait for the count)",
+              "ins text": "ins: file text (host)"}
+
+
+def main_ins(a):
+    """--ins: the job with the switches off, with TIDDIT_CLIPS alone and with TIDDIT_CLIPS_INS beside it, interleaved in one process,
+    medians of --reps; then every batch's push with and without the extension kernel, the stream idle"""
+    from tiddit_amd import __main__ as cli
+    from tiddit_amd import _native, tiddit_clips
+    ctx = _native.default_context()
+    S, Q, L = tiddit_clips.parse_switch(a.switch)
+    runs = {m: [] for m in INS_MODES}
+    table = {}
+    n_rows = 0
+    with tempfile.TemporaryDirectory() as d:
+        for i in range(a.reps + 1):                       # (the first round warms up)
+            for mode in INS_MODES:
+                out = os.path.join(d, "r%d_%s" % (i, mode))
+                rec = _one_job(cli, ctx, a.bam, a.ref, out, a.switch if mode != "off" else None, None, None, INS_KEYS, a.ins_switch if mode == "ins" else None)
+                assert os.path.exists(out + ".clips.ins.tab") == (mode == "ins") and os.path.exists(out + ".clips.tab") == (mode != "off")
+                if i:
+                    runs[mode].append(rec)
+                print("round %d %s: %.3f s" % (i, mode, rec["wall"]), file=sys.stderr, flush=True)
+                if mode == "ins" and i == a.reps:
+                    lines = open(out + ".clips.ins.tab").read().split("\n")
+                    table = {l.split("\t")[1]: int(l.split("\t")[2]) for l in lines if l.startswith("SN\t")}
+                    n_rows = sum(1 for l in lines if l and not l.startswith(("#", "SN\t")))
+    alone, both = keys_alone(a.bam, Q, L), keys_alone(a.bam, Q, L, ext=True)
+    keys = ["wall"] + [short for short, _ in INS_KEYS]
+    med = lambda mode, key: statistics.median([r[key] for r in runs[mode] if r.get(key) is not None] or [float("nan")])
+    sp = lambda mode, key: (lambda v: (max(v) - min(v), min(v), max(v)))([r[key] for r in runs[mode]])
+    res = {"bam": a.bam, "bam_MB": round(os.path.getsize(a.bam) / 1e6, 1), "reps": a.reps, "switch": a.switch, "ins": a.ins_switch, "SN": table, "rows": n_rows,
+           "median_s": {m: {k: med(m, k) for k in keys if any(k in r for r in runs[m])} for m in runs}, "clips_alone_wall_spread_s": sp("clips", "wall")[0],
+           "clips_alone_scan_spread_s": sp("clips", "scan")[0], "runs": runs, "clip_keys_alone": alone, "clip_keys_and_ext_keys": both}
+    print(json.dumps(res))
+    write_ins_record(res, a.out or os.path.join(REPO, "profiles", "clips_ins" + ("_%dmb.md" % a.mb if a.mb else ".md")))
+
+
+def write_ins_record(res, path):
+    """the record of --ins from its result line (also: --render FILE.json, which writes the record of a saved line again)"""
+    runs, table, n_rows, alone, both = res["runs"], res["SN"], res["rows"], res["clip_keys_alone"], res["clip_keys_and_ext_keys"]
+    keys = ["wall"] + [short for short, _ in INS_KEYS]
+    med = lambda mode, key: statistics.median([r[key] for r in runs[mode] if r.get(key) is not None] or [float("nan")])
+    sp = lambda mode, key: (lambda v: (max(v) - min(v), min(v), max(v)))([r[key] for r in runs[mode]])
+
+    class a:
+        bam, reps, switch, ins_switch = res["bam"], res["reps"], res["switch"], res["ins"]
+    size = res["bam_MB"] * 1e6
+    with open(path, "w") as f:
+        f.write("# Insertion candidates from facing clip sites (`TIDDIT_CLIPS=%s TIDDIT_CLIPS_INS=%s`)\n\n" % (a.switch, a.ins_switch))
+        f.write("File: `%s` (%.0f MB).  `tools/time_clips.py --ins`: one process, after one warm-up round %d rounds of { switches off, `TIDDIT_CLIPS` alone, "
+                "`TIDDIT_CLIPS` + `TIDDIT_CLIPS_INS` }, interleaved.  Wall seconds unless a row says device.  The yardstick is the `TIDDIT_CLIPS`-alone job of the "
+                "same process and the spread of its runs; no budget was fixed in advance, this is what was measured.\n\n" % (
+                    os.path.basename(os.path.dirname(a.bam)) + "/" + os.path.basename(a.bam), size / 1e6, a.reps))
+        f.write("| | " + " | ".join("run %d" % (k + 1) for k in range(a.reps)) + " | median |\n|---|" + "---|" * (a.reps + 1) + "\n")
+        for mode in runs:
+            for key in keys:
+                if not any(key in r for r in runs[mode]):
+                    continue
+                f.write("| %s: %s | %s | %.5f |\n" % (mode, INS_LABELS[key], " | ".join("%.5f" % r.get(key, float("nan")) for r in runs[mode]), med(mode, key)))
+        f.write("\nScan stage, ins against the `TIDDIT_CLIPS`-alone median: %+.4f s; the `TIDDIT_CLIPS`-alone runs' spread is %.4f s (min %.4f, max %.4f).  Whole job: "
+                "%+.4f s; spread %.4f s (min %.4f, max %.4f).  The off runs' whole-job spread is %.4f s.\n" % (
+                    (med("ins", "scan") - med("clips", "scan"),) + sp("clips", "scan") + (med("ins", "wall") - med("clips", "wall"),) + sp("clips", "wall") +
+                    (sp("off", "wall")[0],)))
+        f.write("\nThe expectation was that the push hides under the next span's inflate, as `clip_keys` does.  The scan stage's difference above against the "
+                "spread beside it is the answer this file gives: a difference inside the spread confirms it for this file, one outside it refutes it.\n")
+        cap = min(max(int(size) // 16, 1 << 16), 1 << 26)
+        room = 8 * max(r["reads"] for r in both)
+        f.write("\nThe pushes' stage timer (host side) is %.2f ms with `TIDDIT_CLIPS` alone and %.2f ms here.  It holds the waits of a reserve that has to ask "
+                "the device: room for 8 keys per read is reserved before each launch, %d slots for the largest batch of this file, and the extension store is "
+                "made for %d keys (file size / 16, at most 2^26), so %s.  An ask drains the stream, the batch's ingest included.  (Derived from the "
+                "policy, not counted: the handle reports the first store's reserve only.)\n" % (
+                    med("clips", "push") * 1e3, med("ins", "push") * 1e3, room, cap,
+                    "a second batch's bound never fits behind the first's and the reserve asks the device for the real count before nearly every launch" if 2 * room > cap
+                    else "the bounds of %d batches fit before the reserve asks the device for the real count" % (cap // room)))
+        f.write("\nOn the device: the extension store's finish %.3f ms (%d keys; the figure is between two events round two sorts, the run-length and the site "
+                "launches and holds the host's waits between them), `clip_ext_gather` %.3f ms over %d reported sites, the pair launches %.3f ms (%d pairs; "
+                "the host's wait for the pair count lies inside).  The text of the file: %.3f ms on the host.\n" % (
+                    med("ins", "ext finish") * 1e3, table.get("ext_keys", 0), med("ins", "gather") * 1e3,
+                    table.get("left_sites", 0) + table.get("right_sites", 0), med("ins", "pairs") * 1e3, table.get("pairs", 0), med("ins", "ins text") * 1e3))
+        f.write("\nThe table: %s; %d rows.\n" % (", ".join("%s %d" % kv for kv in table.items()), n_rows))
+        f.write("\nThe push of one batch, the stream idle around it, best of 4, host clock around launch and sync (the launch latency is in it): `clip_keys` "
+                "alone, and `clip_keys` + `clip_ext_keys` on a handle with the extension store.  The difference is what `clip_ext_keys` adds when nothing "
+                "overlaps it; the `TIDDIT_CLIPS`-alone runs' scan-stage spread beside these figures is %.1f ms:\n\n| batch | reads | raw MB | clip_keys ms | both ms | "
+                "difference ms |\n|---|---|---|---|---|---|\n" % (sp("clips", "scan")[0] * 1e3))
+        for k, (r, q) in enumerate(zip(alone, both)):
+            f.write("| %d | %d | %.1f | %.3f | %.3f | %+.3f |\n" % (k, r["reads"], r["raw_bytes"] / 1e6, r["ms"], q["ms"], q["ms"] - r["ms"]))
+        f.write("\nThe synthetic file's reads are cut from the reference in one piece (`synth_bam.write_wgs_sv_bam` with `ref_seqs`), a clip included, so no "
+                "insertion is planted and few pairs or none are expected: the figures are the cost of the stage, not a result.  Unmeasured until someone has "
+                "real libraries: their clip density, sites with thousands of events, long reads (the cap of 140 columns).\n")
 
 
 FAR_MODES = ("off", "clips", "far")
@@ -291,8 +400,13 @@ def main():
     ap.add_argument("--align-switch", default="1")
     ap.add_argument("--far", action="store_true", help="measure TIDDIT_CLIPS_FAR against the TIDDIT_CLIPS-alone job instead")
     ap.add_argument("--far-switch", default="1")
+    ap.add_argument("--ins", action="store_true", help="measure TIDDIT_CLIPS_INS against the TIDDIT_CLIPS-alone job instead")
+    ap.add_argument("--ins-switch", default="1")
+    ap.add_argument("--render", help="write the --ins record of a saved result line (FILE.json) again; needs --out")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.render:
+        return write_ins_record(json.loads(open(a.render).read().strip().split("\n")[-1]), a.out)
     if a.mb:
         a.bam, a.ref = bench_file(a.mb)
     if not a.bam or not a.ref:
@@ -302,6 +416,8 @@ def main():
         return main_align(a)
     if a.far:
         return main_far(a)
+    if a.ins:
+        return main_ins(a)
     from tiddit_amd import __main__ as cli
     from tiddit_amd import _native, tiddit_clips
     S, Q, L = tiddit_clips.parse_switch(a.switch)
