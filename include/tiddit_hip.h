@@ -393,6 +393,27 @@ int tdt_region_counts_packed_device(tdt_ctx *ctx, tdt_evstore *s, const int64_t 
  * output untouched; n_contigs == 0 returns TDT_OK.  The context's stream is synchronised before the return. */
 int tdt_depth_dist(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, int cap, int64_t *out);
 
+/* ---- reference support at clip-site junctions from the evidence store (TIDDIT_CLIPS_VCF) ------------------------ *
+ * For every boundary b (0-based: b bases lie left of the cut) of a contig of LN bases and the flank F, over the contig's records with
+ * e = min(end, LN) and end > start: left = the records with start <= b - F < e (0 when b - F < 0), right = those with
+ * start <= b + F - 1 < e (0 when b + F > LN), span = those with both — each over the records with none of TDT_EV_UNMAPPED,
+ * TDT_EV_DUPLICATE, TDT_EV_LOW_Q — and span_lowq = the records with both whose only one of those bits is TDT_EV_LOW_Q.  b outside
+ * 0 ... LN is legal and follows the same rule.  All arithmetic is 64-bit.  contigs = int64[n_contigs][5] (offset, n, max span, tid,
+ * contig length), the table of tdt_region_counts_packed, validated the same way; boundaries = int32[nb][2] (contig row, b), 8-byte
+ * aligned; out = int64[nb][4] (left, right, span, span_lowq).  Host arrays.  One launch over all boundaries, one wavefront per
+ * boundary (csrc/tdt_junction.hip).  TDT_E_ARG for a null or misaligned pointer or F outside 1 ... 1000, TDT_E_RANGE for a row
+ * outside the store, a negative length or a boundary that names no row — all before anything is launched, the output untouched;
+ * nb == 0 returns TDT_OK.  The context's stream is synchronised before the return. */
+int tdt_junction_support(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *boundaries, size_t nb, int F,
+                         int64_t *out);
+/* The same counts with the boundaries and the output in HBM (d_boundaries 8-byte aligned; d_out int64[nb][4]); contigs = the host
+ * table as above, validated on the host.  The kernel checks every boundary's row: a boundary naming no row gets zeros, and the call
+ * returns TDT_E_RANGE naming the first such boundary.  The context's stream is synchronised before the return. */
+int tdt_junction_support_device(tdt_ctx *ctx, tdt_evstore *s, const int64_t *contigs, int n_contigs, const int32_t *d_boundaries, size_t nb,
+                                int F, int64_t *d_out);
+/* the device milliseconds of the last of the two calls above that launched over this store (the kernel alone, between two events) */
+int tdt_junction_timing(tdt_evstore *s, double *ms);
+
 /* ---- order statistics for the depth fold-changes of genotyped sites (TIDDIT_GENOTYPE_DEPTH) ------------ *
  * cov / gc are the concatenated float64 coverage bins / int8 GC bins (n of them, n < 2^31 - 1; coverage is non-negative, -0.0 reads
  * as +0.0).  Radix select on the bit patterns (csrc/tdt_depth.hip): lower / upper are the two middle order statistics (equal for an

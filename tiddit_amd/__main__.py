@@ -106,6 +106,16 @@ most ``M`` (0 ... 8) mismatches, with the inserted sequence (up to 2 x 140 - ``O
 are what is known of a longer insertion (tiddit_amd/tiddit_clip_ins.py has the definition and the file's format).  Every other output is
 what it is without the switch.  Unset or empty is off; the switch without ``TIDDIT_CLIPS``, or a value that is none of the four forms,
 ends the job with an error before the scan.  N ranks are refused with ``TIDDIT_CLIPS``.
+
+``TIDDIT_CLIPS_VCF=1`` (flank 10) or ``TIDDIT_CLIPS_VCF=F`` (2 ... 1000; valid only together with ``TIDDIT_CLIPS`` and at least one of
+``TIDDIT_CLIPS_ALIGN`` / ``TIDDIT_CLIPS_FAR`` / ``TIDDIT_CLIPS_INS``): ``--sv`` also writes ``{o}.clips.vcf`` — the mated DEL / DUP / BND rows of
+the two placement stages as one record per junction (a BND two), left-aligned through the microhomology, and the insertion pairs that
+no junction explains, each with a genotype from the clipped reads at its two sites against the reads that cross either breakpoint
+intact with ``F`` aligned bases on both sides (tiddit_amd/tiddit_clip_vcf.py has the definition and the file's format).  The scan keeps
+its evidence store as for ``TIDDIT_DEPTH_DIST``, and one launch behind the clip stages counts all breakpoints over it where it lies; the
+store is neither taken nor freed.  Every other output is what it is without the switch.  A bare ``1`` means the default, so a flank of
+1 cannot be asked for.  Unset or empty is off; the switch without its partners, or any other value, ends the job with an error before
+the scan.  N ranks are refused with ``TIDDIT_CLIPS``.
 """
 import argparse
 import os
@@ -371,6 +381,14 @@ def run_sv(args, version):
         # (the same)
         print("error, TIDDIT_CLIPS_INS={}: {}".format(os.environ.get("TIDDIT_CLIPS_INS"), e))
         sys.exit(1)
+    try:
+        from . import tiddit_clip_vcf
+        clips_vcf = tiddit_clip_vcf.parse_switch(os.environ.get("TIDDIT_CLIPS_VCF"), clips is not None,
+                                                 clips_align is not None or clips_far is not None or clips_ins is not None)
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_CLIPS_VCF={}: {}".format(os.environ.get("TIDDIT_CLIPS_VCF"), e))
+        sys.exit(1)
     sites_path = os.environ.get("TIDDIT_GENOTYPE") or None
     genotype_depth = os.environ.get("TIDDIT_GENOTYPE_DEPTH") == "1"
     if genotype_depth and sites_path is None:
@@ -612,8 +630,8 @@ def run_sv(args, version):
     # TIDDIT_VARIANTS=1: the scan also packs every placed record into the evidence store the native variant stage reads (on N ranks:
     # every rank the records of its own shard)
     # TIDDIT_GENOTYPE needs the same store, with or without the variant stage
-    # ... and so does TIDDIT_DEPTH_DIST
-    tiddit_signal.KEEP_EVIDENCE = os.environ.get("TIDDIT_VARIANTS") == "1" or genotype_job is not None or depth_dist
+    # ... and so do TIDDIT_DEPTH_DIST and TIDDIT_CLIPS_VCF
+    tiddit_signal.KEEP_EVIDENCE = os.environ.get("TIDDIT_VARIANTS") == "1" or genotype_job is not None or depth_dist or clips_vcf is not None
     if track is not None:
         # TIDDIT_COV_TRACK: the scan fills a second histogram — every contig, the track's bin size and mapq cut — from the same batches
         tiddit_signal.COV_TRACK = (track[0], track[1])
@@ -726,12 +744,13 @@ def run_sv(args, version):
         # (the same)
         counter, tiddit_signal.CLIP_COUNTER = tiddit_signal.CLIP_COUNTER, None
         t = time.time()
+        clip_stage_rows = None if clips_vcf is None else {}
         try:
             # TIDDIT_CLIPS_ALIGN: ... and the sites' consensus is searched in the reference, behind the finish, where the rows lie
             # TIDDIT_CLIPS_FAR: ... and placed genome-wide by its seed, the same way
             # TIDDIT_CLIPS_INS: ... and the rows are extended from the second store, paired and closed, the same way
             tiddit_clips.main(counter, prefix, coverage_data, chromosomes, clips[0], None if clips_align is None else (reference,) + clips_align,
-                              far=None if clips_far is None else (reference,) + clips_far, ins=clips_ins)
+                              far=None if clips_far is None else (reference,) + clips_far, ins=clips_ins, keep=clip_stage_rows)
         finally:
             if (clips_align is not None or clips_far is not None) and not indels_norm and snvs is None:
                 reference.close()                     # (only these switches loaded it)
@@ -744,6 +763,19 @@ def run_sv(args, version):
         if clips_ins is not None:
             T.update({"  " + k: v for k, v in tiddit_clip_ins.STAGE_SECONDS.items()})
         STAGE_NOTES.update(tiddit_clips.STAGE_NOTES)
+        if clips_vcf is not None:
+            # TIDDIT_CLIPS_VCF: the stages' rows become junctions, and one launch counts the reads that cross every breakpoint intact over
+            # the store the scan left, which stays where it is for the stages below
+            from . import tiddit_variant
+            if tiddit_variant.LIVE_STORE is None:
+                raise RuntimeError("TIDDIT_CLIPS_VCF: the scan left no evidence store")
+            t = time.time()
+            vcf_counts = tiddit_clip_vcf.main(tiddit_variant.LIVE_STORE, prefix, chromosomes, clips_vcf,
+                                              tiddit_clip_vcf.header_parts(bam_header, sample_id, version),
+                                              clip_stage_rows.get("align"), clip_stage_rows.get("far"), clip_stage_rows.get("ins"))
+            print(tiddit_clip_vcf.summary_line(vcf_counts))
+            T["clip junction vcf ({o}.clips.vcf)"] = time.time() - t
+            T.update({"  " + k: v for k, v in tiddit_clip_vcf.STAGE_SECONDS.items()})
     try:
         _after_scan(args, prefix, rank, multi, T, gc_job, start_gc if gc_job is not None else None, chromosomes, contigs, contig_length, samples,
                     library, coverage_data, bam_header, max_ins_len, min_mapq, sample_id, version, contig_number, own_group if multi else False,

@@ -128,6 +128,9 @@ SYMBOLS = {
     "tdt_region_counts_packed": (_i, [_P, _P, _P, _i, _P, _sz, _i, _i64, _P]),
     "tdt_region_counts_packed_device": (_i, [_P, _P, _P, _i, _P, _sz, _i, _i64, _P]),
     "tdt_depth_dist": (_i, [_P, _P, _P, _i, _i, _P]),
+    "tdt_junction_support": (_i, [_P, _P, _P, _i, _P, _sz, _i, _P]),
+    "tdt_junction_support_device": (_i, [_P, _P, _P, _i, _P, _sz, _i, _P]),
+    "tdt_junction_timing": (_i, [_P, ctypes.POINTER(_dbl)]),
     "tdt_links_create": (_i, [_P, _P, _P, _P, _P, _i, _PP]),
     "tdt_links_destroy": (_i, [_P]),
     "tdt_links_count": (_i, [_P, _P, _sz, _P]),

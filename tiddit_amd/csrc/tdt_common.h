@@ -110,6 +110,7 @@ struct tdt_evstore {
     int4 *rec;
     size_t n, cap;
     int *d_span;      // per contig: max(end - start) over its records (atomicMax in the pack kernel)
+    double junction_ms = 0;   // tdt_junction.hip: the device time of the last junction_support launch over this store
 };
 // every row {offset, n, max span, tid, contig length} of a contig table lies inside the store, else TDT_E_RANGE naming `fn`
 int tdt_evstore_check_rows(const char *fn, const tdt_evstore *s, const int64_t *contigs, int n_contigs);

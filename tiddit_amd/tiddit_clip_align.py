@@ -45,7 +45,8 @@ Other contigs (translocations) and placements beyond the window are tiddit_clip_
 Sites that place nowhere and face each other are tiddit_clip_ins.py's (``TIDDIT_CLIPS_INS``): insertions, closed from up to 140 columns.
 
 NOT built: gapped placements, searching with more than the 28 consensus columns (the 140 of ``TIDDIT_CLIPS_INS`` are not searched), mates
-of INV rows, joining the rows to the SV candidates or the VCF.
+of INV rows, joining the rows to the SV candidates of ``{o}.vcf`` (tiddit_clip_vcf.py, ``TIDDIT_CLIPS_VCF``, writes the mated DEL / DUP rows as
+genotyped records of their own file, ``{o}.clips.vcf``).
 """
 import ctypes
 import time
@@ -233,9 +234,10 @@ def summary_line(counts):
         *(int(c[SN_INDEX[k]]) for k in ("sites", "searched", "aligned", "ambiguous", "unaligned", "ref", "del", "dup", "inv", "mated")))
 
 
-def main(counter, clip_rows, reference, prefix, names, W, K, M):
+def main(counter, clip_rows, reference, prefix, names, W, K, M, rows_out=None):
     """the stage behind the clip counter's finish and in front of its close: the search on the device over the rows where they lie,
-    rule 5 on the host and the file -> the counters (:func:`summary_line`); ``clip_rows``: the columns ``counter.rows()`` gave"""
+    rule 5 on the host and the file -> the counters (:func:`summary_line`); ``clip_rows``: the columns ``counter.rows()`` gave;
+    ``rows_out``: None, or a list that receives the rows of :func:`summarise` (tiddit_clip_vcf.py joins them)"""
     STAGE_SECONDS.clear()
     t = time.time()
     sn, placed, ms = align_counter(counter, reference, W, K, M)
@@ -247,5 +249,7 @@ def main(counter, clip_rows, reference, prefix, names, W, K, M):
     if not numpy.array_equal(counts[:SN_INDEX["mated"]], sn[:SN_INDEX["mated"]]):
         raise RuntimeError("tdt_clip_align: the device's counters {} differ from the rows' {}".format(sn.tolist(), counts.tolist()))
     write_file(prefix + ".clips.align.tab", counts, rows, names, W, K, M)
+    if rows_out is not None:
+        rows_out.extend(rows)
     STAGE_SECONDS["clip align mates + table text (host)"] = time.time() - t
     return counts

@@ -43,7 +43,8 @@ A site whose consensus places nowhere is sequence the reference does not hold: t
 which tiddit_clip_ins.py (``TIDDIT_CLIPS_INS``) pairs and closes from up to 140 clipped columns per side.
 
 NOT built: mismatches inside the seed (spaced or multiple seeds), gapped placements, searching with more than the 28 consensus columns
-(the 140 of ``TIDDIT_CLIPS_INS`` are not searched), mates of reverse-strand rows, joining the rows to the SV candidates or the VCF, N ranks.
+(the 140 of ``TIDDIT_CLIPS_INS`` are not searched), mates of reverse-strand rows, joining the rows to the SV candidates of ``{o}.vcf`` (tiddit_clip_vcf.py,
+``TIDDIT_CLIPS_VCF``, writes the mated BND / DEL / DUP rows as genotyped records of their own file, ``{o}.clips.vcf``), N ranks.
 """
 import ctypes
 import time
@@ -232,9 +233,10 @@ def summary_line(counts):
         *(int(c[SN_INDEX[k]]) for k in ("sites", "searched", "placed", "ambiguous", "unplaced", "same_contig", "other_contig", "reverse", "mated")))
 
 
-def main(counter, clip_rows, reference, prefix, names, K, M):
+def main(counter, clip_rows, reference, prefix, names, K, M, rows_out=None):
     """the stage behind the clip counter's finish and in front of its close: the search on the device over the rows where they lie,
-    rule 5 on the host and the file -> the counters (:func:`summary_line`); ``clip_rows``: the columns ``counter.rows()`` gave"""
+    rule 5 on the host and the file -> the counters (:func:`summary_line`); ``clip_rows``: the columns ``counter.rows()`` gave;
+    ``rows_out``: None, or a list that receives the rows of :func:`summarise` (tiddit_clip_vcf.py joins them)"""
     STAGE_SECONDS.clear()
     t = time.time()
     sn, placed, ms = far_counter(counter, reference, K, M)
@@ -247,5 +249,7 @@ def main(counter, clip_rows, reference, prefix, names, K, M):
     if not numpy.array_equal(counts[:SN_INDEX["mated"]], sn[:SN_INDEX["mated"]]):
         raise RuntimeError("tdt_clip_far: the device's counters {} differ from the rows' {}".format(sn.tolist(), counts.tolist()))
     write_file(prefix + ".clips.far.tab", counts, rows, names, K, M)
+    if rows_out is not None:
+        rows_out.extend(rows)
     STAGE_SECONDS["clip far mates + table text (host)"] = time.time() - t
     return counts

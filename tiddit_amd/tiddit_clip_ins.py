@@ -47,7 +47,8 @@ for the eleven counters in the order of ``SN``, then ``#CHROM POS END TSD R_SUPP
 CLOSURES SEQ LEFT_SEQ RIGHT_SEQ`` and one row per pair, all tab-separated.  ``POS = P_R``, ``END = P_L``.
 
 NOT built: insertions with a deleted stretch (``P_L > P_R + 1``); one-sided sites; checking the consensus tails against the
-reference; more than 140 columns; naming mobile-element families; joining the rows to the VCF; N ranks (refused with ``TIDDIT_CLIPS``).
+reference; more than 140 columns; naming mobile-element families; joining the rows to ``{o}.vcf`` (tiddit_clip_vcf.py, ``TIDDIT_CLIPS_VCF``, writes them as genotyped
+records of their own file, ``{o}.clips.vcf``); N ranks (refused with ``TIDDIT_CLIPS``).
 """
 import ctypes
 import time
@@ -339,10 +340,10 @@ def summary_line(counts):
         *(int(c[SN_INDEX[k]]) for k in ("ext_keys", "sites_extended", "left_sites", "right_sites", "pairs", "closed", "closed_multi", "open")))
 
 
-def main(counter, clip_rows, prefix, names, K, O, M):
+def main(counter, clip_rows, prefix, names, K, O, M, rows_out=None):
     """the stage behind the clip counter's finish and in front of its close: the extension store's finish, the gather and the pair
     launches on the device over the rows where they lie, and the file -> the counters (:func:`summary_line`); ``clip_rows``: the
-    columns ``counter.rows()`` gave"""
+    columns ``counter.rows()`` gave; ``rows_out``: None, or a list that receives the rows of :func:`file_rows` (tiddit_clip_vcf.py joins them)"""
     STAGE_SECONDS.clear()
     t = time.time()
     sn = counter.ins(K, O, M)
@@ -353,6 +354,9 @@ def main(counter, clip_rows, prefix, names, K, O, M):
     for k, v in zip(("extension finish (sort, run lengths, vote)", "gather of the extended consensus", "pair count + closure"), ms.tolist()):
         STAGE_SECONDS["  clip ins " + k + " (device time)"] = v * 1e-3
     t = time.time()
-    write_file(prefix + ".clips.ins.tab", sn, file_rows(clip_rows[0], clip_rows[2], eclen, cons5, cols, seq10), names, K, O, M)
+    rows = file_rows(clip_rows[0], clip_rows[2], eclen, cons5, cols, seq10)
+    write_file(prefix + ".clips.ins.tab", sn, rows, names, K, O, M)
+    if rows_out is not None:
+        rows_out.extend(rows)
     STAGE_SECONDS["clip ins table text (host)"] = time.time() - t
     return sn

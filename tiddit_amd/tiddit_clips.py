@@ -333,13 +333,14 @@ def summary_line(counts):
                                         "malformed")))
 
 
-def main(counter, prefix, coverage_data, names, S, align=None, far=None, ins=None):
+def main(counter, prefix, coverage_data, names, S, align=None, far=None, ins=None, keep=None):
     """the stage behind the scan: the sort, the run lengths and the vote on the device, the file and the summary line.  ``align``:
     None, or (reference, W, K, M) of ``TIDDIT_CLIPS_ALIGN`` — the rows are then realigned where they lie, behind the finish and before
     the counter is closed (tiddit_clip_align.main, which writes ``{o}.clips.align.tab``); ``far``: None, or (reference, K, M) of
     ``TIDDIT_CLIPS_FAR`` — the rows are placed genome-wide the same way (tiddit_clip_far.main, ``{o}.clips.far.tab``); the reference is not
     closed here; ``ins``: None, or (K, O, M) of ``TIDDIT_CLIPS_INS`` — the counter has its extension store (``enable_ext``), and the rows are
-    extended, paired and closed where they lie (tiddit_clip_ins.main, ``{o}.clips.ins.tab``)"""
+    extended, paired and closed where they lie (tiddit_clip_ins.main, ``{o}.clips.ins.tab``); ``keep``: None, or a dict that receives the rows of
+    the stages that ran under ``"align"`` / ``"far"`` / ``"ins"`` (``TIDDIT_CLIPS_VCF``, tiddit_clip_vcf.py, joins them behind this stage)"""
     STAGE_SECONDS.clear()
     STAGE_NOTES.clear()
     t = time.time()
@@ -353,7 +354,7 @@ def main(counter, prefix, coverage_data, names, S, align=None, far=None, ins=Non
         from . import tiddit_clip_align
         t_align = time.time()
         try:
-            align_counts = tiddit_clip_align.main(counter, rows, align[0], prefix, names, *align[1:])
+            align_counts = tiddit_clip_align.main(counter, rows, align[0], prefix, names, *align[1:], rows_out=None if keep is None else keep.setdefault("align", []))
         except BaseException:
             counter.close()
             raise
@@ -363,7 +364,7 @@ def main(counter, prefix, coverage_data, names, S, align=None, far=None, ins=Non
         from . import tiddit_clip_far
         t_far = time.time()
         try:
-            far_counts = tiddit_clip_far.main(counter, rows, far[0], prefix, names, *far[1:])
+            far_counts = tiddit_clip_far.main(counter, rows, far[0], prefix, names, *far[1:], rows_out=None if keep is None else keep.setdefault("far", []))
         except BaseException:
             counter.close()
             raise
@@ -373,7 +374,7 @@ def main(counter, prefix, coverage_data, names, S, align=None, far=None, ins=Non
         from . import tiddit_clip_ins
         t_ins = time.time()
         try:
-            ins_counts = tiddit_clip_ins.main(counter, rows, prefix, names, *ins)
+            ins_counts = tiddit_clip_ins.main(counter, rows, prefix, names, *ins, rows_out=None if keep is None else keep.setdefault("ins", []))
         except BaseException:
             counter.close()
             raise

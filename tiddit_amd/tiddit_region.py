@@ -288,6 +288,25 @@ class EvidenceStore:
         _native.check(ctx.lib.tdt_depth_dist(ctx.handle, self.handle, _native.ptr(tab), len(tab), DD_CAP, _native.ptr(out)))
         return out
 
+    def junction_support(self, boundaries, F, table=None, ctx=None):
+        """boundaries: (contig row, b) rows, b 0-based = the bases left of the cut -> int64[nb, 4] (left, right, span, span_lowq): the
+        kept records that hold base b - F, base b + F - 1, both, and the low-MAPQ ones with both — the reads that cross a breakpoint
+        intact with ``F`` (1 ... 1000) aligned bases on either side, all boundaries in ONE launch (tiddit_clip_vcf.py rule 4 has the
+        definition)."""
+        ctx = ctx or self.ctx
+        q = numpy.ascontiguousarray(numpy.asarray(boundaries, dtype=numpy.int32).reshape(-1, 2))
+        tab = numpy.ascontiguousarray(self.contig_table() if table is None else table, dtype=numpy.int64).reshape(-1, 5)
+        out = numpy.zeros((len(q), 4), dtype=numpy.int64)
+        _native.check(ctx.lib.tdt_junction_support(ctx.handle, self.handle, _native.ptr(tab), len(tab), _native.ptr(q), len(q), int(F), _native.ptr(out)))
+        return out
+
+    def junction_ms(self):
+        """the device milliseconds of the last junction_support launch over this store"""
+        import ctypes
+        ms = ctypes.c_double(0)
+        _native.check(self.ctx.lib.tdt_junction_timing(self.handle, ctypes.byref(ms)))
+        return ms.value
+
     def close(self):
         if getattr(self, "handle", None):
             self.ctx.lib.tdt_evstore_destroy(self.handle)

@@ -43,15 +43,24 @@ def cmd_line():
     return '##TIDDITcmd="' + " ".join(sys.argv) + '"'
 
 
+def contig_lines(bam_header):
+    """the ``##contig`` lines, one per ``@SQ`` of the BAM header"""
+    return ["##contig=<ID={},length={}>".format(c["SN"], c["LN"]) for c in bam_header["SQ"]]
+
+
+def column_line(sample_id):
+    return "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + sample_id
+
+
 def main(bam_header, library, sample_id, version):
     lines = ["##fileformat=VCFv4.1", "##source=TIDDIT-" + version]
     lines += ['##ALT=<ID={},Description="{}">'.format(i, d) for i, d in _ALT]
-    lines += ["##contig=<ID={},length={}>".format(c["SN"], c["LN"]) for c in bam_header["SQ"]]
+    lines += contig_lines(bam_header)
     lines += ['##INFO=<ID={},Number={},Type={},Description="{}">'.format(*row) for row in _INFO]
     lines += ['##FILTER=<ID={},Description="{}">'.format(*row) for row in _FILTER]
     lines += ['##FORMAT=<ID={},Number={},Type={},Description="{}">'.format(*row) for row in _FORMAT]
     lines.append("##LibraryStats=TIDDIT-{} Coverage={}  ReadLength={} MeanInsertSize={} STDInsertSize={} Reverse_Forward={}".format(
         version, library["avg_coverage"], library["avg_read_length"], library["avg_insert_size"], library["std_insert_size"], library["mp"]))
     lines.append(cmd_line())
-    lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + sample_id)
+    lines.append(column_line(sample_id))
     return "\n".join(lines)

@@ -17,8 +17,13 @@ With --ins the record is about TIDDIT_CLIPS_INS: the job with the switches off, 
 the pair stage, interleaved in one process; the push of every batch with and without `clip_ext_keys` beside `clip_keys` (the stream idle,
 best of 4); the device events of the extension finish, the gather and the pair launches; written to profiles/clips_ins_<mb>mb.md.
 
+With --vcf the record is about TIDDIT_CLIPS_VCF: the job with the switches off, with the four clip switches and with the junction VCF
+beside them, interleaved in one process — the yardstick is the four-switch job and its own run-to-run spread; the stage's host parts and
+`junction_support`'s device time; then the kernel alone on one boundary per 10 kb over a store built from the file; written to
+profiles/clips_vcf_<mb>mb.md.
+
 usage: python tools/time_clips.py (--bam WGS.bam --ref ref.fa | --mb 240) [--reps 3] [--switch 1] [--align [--align-switch 1]] [--far [--far-switch 1]]
-                                  [--ins [--ins-switch 1]] [--out FILE.md]
+                                  [--ins [--ins-switch 1]] [--vcf [--vcf-switch 1]] [--out FILE.md]
 (--mb: bench.py's synthetic file of that genome size, made at $TIDDIT_BENCH_TMP/tiddit_bench_sv_<mb>/ when it is not there)"""
 import argparse
 import contextlib
@@ -88,9 +93,9 @@ ALIGN_LABELS = {"wall": "whole job", "scan": "scan stage", "reference": "referen
                 "align text": "align: mates and file text (host)"}
 
 
-def _one_job(cli, ctx, bam, ref, out, clips=None, align=None, far=None, keys=None, ins=None):
+def _one_job(cli, ctx, bam, ref, out, clips=None, align=None, far=None, keys=None, ins=None, vcf=None):
     """one `--sv --skip_assembly` job in this process -> its wall seconds and stage seconds by short name"""
-    for k, v in (("TIDDIT_CLIPS", clips), ("TIDDIT_CLIPS_ALIGN", align), ("TIDDIT_CLIPS_FAR", far), ("TIDDIT_CLIPS_INS", ins)):
+    for k, v in (("TIDDIT_CLIPS", clips), ("TIDDIT_CLIPS_ALIGN", align), ("TIDDIT_CLIPS_FAR", far), ("TIDDIT_CLIPS_INS", ins), ("TIDDIT_CLIPS_VCF", vcf)):
         os.environ.pop(k, None)
         if v is not None:
             os.environ[k] = v
@@ -104,10 +109,106 @@ def _one_job(cli, ctx, bam, ref, out, clips=None, align=None, far=None, keys=Non
         os.environ.pop("TIDDIT_CLIPS_ALIGN", None)
         os.environ.pop("TIDDIT_CLIPS_FAR", None)
         os.environ.pop("TIDDIT_CLIPS_INS", None)
+        os.environ.pop("TIDDIT_CLIPS_VCF", None)
     Sx = {k.strip(): v for k, v in cli.STAGE_SECONDS.items()}
     rec = {"wall": time.perf_counter() - t0}
     rec.update({short: Sx[key] for short, key in (keys or ALIGN_KEYS) if key in Sx})
     return rec
+
+
+VCF_MODES = ("off", "four", "vcf")
+VCF_KEYS = (("scan", "signal extraction + coverage"), ("clip stage", "clip sites ({o}.clips.tab)"), ("vcf", "clip junction vcf ({o}.clips.vcf)"),
+            ("junctions", "clip vcf junctions (host)"), ("support", "clip vcf support (device: one wavefront per boundary over the evidence store)"),
+            ("kernel", "clip vcf junction_support kernel (device time)"), ("vcf text", "clip vcf text (host)"))
+VCF_LABELS = {"wall": "whole job", "scan": "scan stage", "clip stage": "clip stage (finish, align, far, ins, files)", "vcf": "vcf stage (junctions, support, file)",
+              "junctions": "vcf: rows to junctions (host)", "support": "vcf: the call into the library (table, upload, launch, wait)",
+              "kernel": "vcf: `junction_support` (device)", "vcf text": "vcf: records and file text (host)"}
+
+
+def main_vcf(a):
+    """--vcf: the job with the switches off, with the four clip switches and with TIDDIT_CLIPS_VCF beside them, interleaved in one process,
+    medians of --reps; then `junction_support` alone on a synthetic boundary list, one boundary per 10 kb, over a store built from the file"""
+    from tiddit_amd import __main__ as cli
+    from tiddit_amd import _native, tiddit_clip_vcf, tiddit_region
+    ctx = _native.default_context()
+    F = tiddit_clip_vcf.parse_switch(a.vcf_switch)
+    runs = {m: [] for m in VCF_MODES}
+    header = {}
+    with tempfile.TemporaryDirectory() as d:
+        for i in range(a.reps + 1):                       # (the first round warms up)
+            for mode in VCF_MODES:
+                out = os.path.join(d, "r%d_%s" % (i, mode))
+                on = mode != "off"
+                rec = _one_job(cli, ctx, a.bam, a.ref, out, a.switch if on else None, a.align_switch if on else None, a.far_switch if on else None, VCF_KEYS,
+                               a.ins_switch if on else None, a.vcf_switch if mode == "vcf" else None)
+                assert os.path.exists(out + ".clips.vcf") == (mode == "vcf") and os.path.exists(out + ".clips.ins.tab") == on
+                if i:
+                    runs[mode].append(rec)
+                print("round %d %s: %.3f s" % (i, mode, rec["wall"]), file=sys.stderr, flush=True)
+                if mode == "vcf" and i == a.reps:
+                    header = {l[len("##clips_vcf_"):].split("=")[0]: int(l.split("=")[1]) for l in open(out + ".clips.vcf").read().split("\n") if l.startswith("##clips_vcf_")}
+    # the kernel alone, on real work: one boundary per 10 kb of every contig over the file's store
+    store = tiddit_region.build_store(a.bam, 5, 100000)
+    try:
+        bounds = [(t, b) for t, ln in enumerate(store.lengths) for b in range(5000, ln, 10000)]
+        table = store.contig_table()
+        alone = []
+        for _ in range(5):                                # (the first one warms up)
+            t0 = time.perf_counter()
+            counts = store.junction_support(bounds, F, table=table)
+            alone.append({"call_ms": (time.perf_counter() - t0) * 1e3, "kernel_ms": store.junction_ms()})
+        alone = alone[1:]
+        n_records, max_span = int(store.n), int(table[:, 2].max()) if len(table) else 0
+        crossed = int(counts[:, 2].sum())
+    finally:
+        store.close()
+    keys = ["wall"] + [short for short, _ in VCF_KEYS]
+    med = lambda mode, key: statistics.median([r[key] for r in runs[mode] if r.get(key) is not None] or [float("nan")])
+    sp = lambda mode, key: (lambda v: (max(v) - min(v), min(v), max(v)))([r[key] for r in runs[mode]])
+    res = {"bam": a.bam, "bam_MB": round(os.path.getsize(a.bam) / 1e6, 1), "reps": a.reps, "switches": [a.switch, a.align_switch, a.far_switch, a.ins_switch, a.vcf_switch],
+           "flank": F, "header": header, "median_s": {m: {k: med(m, k) for k in keys if any(k in r for r in runs[m])} for m in runs},
+           "four_wall_spread_s": sp("four", "wall")[0], "four_scan_spread_s": sp("four", "scan")[0], "runs": runs,
+           "alone": {"boundaries": len(bounds), "records": n_records, "max_span": max_span, "span_sum": crossed, "calls": alone}}
+    print(json.dumps(res))
+    path = a.out or os.path.join(REPO, "profiles", "clips_vcf" + ("_%dmb.md" % a.mb if a.mb else ".md"))
+    with open(path, "w") as f:
+        f.write("# Genotyped VCF of the clip-site junctions (`TIDDIT_CLIPS=%s TIDDIT_CLIPS_ALIGN=%s TIDDIT_CLIPS_FAR=%s TIDDIT_CLIPS_INS=%s TIDDIT_CLIPS_VCF=%s`)\n\n"
+                % (a.switch, a.align_switch, a.far_switch, a.ins_switch, a.vcf_switch))
+        f.write("File: `%s` (%.0f MB).  `tools/time_clips.py --vcf`: one process, after one warm-up round %d rounds of { switches off, the four clip switches, the "
+                "four and `TIDDIT_CLIPS_VCF` }, interleaved.  Wall seconds unless a row says device.  The yardstick is the four-switch job of the same process — "
+                "the job as it was before this switch existed — and the spread of its runs; no number was fixed in advance, this is what was measured.\n\n" % (
+                    os.path.basename(os.path.dirname(a.bam)) + "/" + os.path.basename(a.bam), os.path.getsize(a.bam) / 1e6, a.reps))
+        f.write("| | " + " | ".join("run %d" % (k + 1) for k in range(a.reps)) + " | median |\n|---|" + "---|" * (a.reps + 1) + "\n")
+        for mode in runs:
+            for key in keys:
+                if not any(key in r for r in runs[mode]):
+                    continue
+                f.write("| %s: %s | %s | %.5f |\n" % (mode, VCF_LABELS[key], " | ".join("%.5f" % r.get(key, float("nan")) for r in runs[mode]), med(mode, key)))
+        f.write("\nScan stage, vcf against the four-switch median: %+.4f s; the four-switch runs' spread is %.4f s (min %.4f, max %.4f).  Whole job: %+.4f s; spread "
+                "%.4f s (min %.4f, max %.4f).  The off runs' whole-job spread is %.4f s.\n" % (
+                    (med("vcf", "scan") - med("four", "scan"),) + sp("four", "scan") + (med("vcf", "wall") - med("four", "wall"),) + sp("four", "wall") +
+                    (sp("off", "wall")[0],)))
+        f.write("\nThe claim was that the scan stage stays inside the spread of the runs without the switch: the stage runs behind the scan and adds no launch per "
+                "batch, but the scan now also packs its evidence store (one `evidence_pack` launch per batch, as for `TIDDIT_DEPTH_DIST`).  The scan stage's "
+                "difference above against the spread beside it is the answer this file gives: inside the spread supports the claim for this file, outside it "
+                "retracts it.  Here: %s.\n" % (
+                    "inside the spread, the claim stands for this file" if abs(med("vcf", "scan") - med("four", "scan")) <= sp("four", "scan")[0] else
+                    "OUTSIDE the spread, the claim is retracted for this file: the scan stage pays for packing the evidence store, what `TIDDIT_DEPTH_DIST` and "
+                    "`TIDDIT_VARIANTS` pay when they are on; the stage behind the scan is the `vcf` rows above"))
+        f.write("\nThe file's header: %s.  The synthetic file's reads are cut from the reference in one piece (`synth_bam.write_wgs_sv_bam` with `ref_seqs`), a clip "
+                "included, so it yields no junction (what places, places as `REF`), no boundary, and the stage costs its set-up only: `junction_support` is "
+                "launched only when there is a boundary, so the `kernel` row is absent when the header says 0 records.\n" % (
+                    ", ".join("%s %d" % kv for kv in header.items())))
+        kms, cms = [c["kernel_ms"] for c in alone], [c["call_ms"] for c in alone]
+        f.write("\n`junction_support` alone, on real work: a store built from the same file (%d records, max span %d), one boundary per 10 kb of every contig (%d "
+                "boundaries, flank %d; %d reads cross them in all), 4 calls after a warm-up: the kernel between its two events %s ms (median %.4f), the whole "
+                "call — contig table, upload of table and boundaries, launch, copy back, wait — %s ms (median %.4f) on the host clock.  One wavefront per "
+                "boundary reads its bracket of 16-byte records once: with brackets of a few hundred records this is a latency figure (the 64-ary search's "
+                "dependent loads, then one or a few strided loads per lane), not a bandwidth one.\n" % (
+                    n_records, max_span, len(bounds), F, crossed, ", ".join("%.4f" % v for v in kms), statistics.median(kms), ", ".join("%.3f" % v for v in cms),
+                    statistics.median(cms)))
+        f.write("\nNot measured by this record: real libraries (junctions by the thousand, deep coverage: brackets of tens of thousands of records per boundary, "
+                "long reads with a large max span), the kernel under a profiler, 3 Gb.\n")
 
 
 INS_MODES = ("off", "clips", "ins")
@@ -402,6 +503,8 @@ def main():
     ap.add_argument("--far-switch", default="1")
     ap.add_argument("--ins", action="store_true", help="measure TIDDIT_CLIPS_INS against the TIDDIT_CLIPS-alone job instead")
     ap.add_argument("--ins-switch", default="1")
+    ap.add_argument("--vcf", action="store_true", help="measure TIDDIT_CLIPS_VCF against the job with the four clip switches instead")
+    ap.add_argument("--vcf-switch", default="1")
     ap.add_argument("--render", help="write the --ins record of a saved result line (FILE.json) again; needs --out")
     ap.add_argument("--out")
     a = ap.parse_args()
@@ -416,6 +519,8 @@ def main():
         return main_align(a)
     if a.far:
         return main_far(a)
+    if a.vcf:
+        return main_vcf(a)
     if a.ins:
         return main_ins(a)
     from tiddit_amd import __main__ as cli
