@@ -1044,6 +1044,53 @@ int tdt_clip_ins_sites_device(tdt_ctx *ctx, size_t n, const uint64_t *d_k1, cons
                               int O, int M, uint64_t *d_sn_out, uint32_t *d_r_row, uint32_t *d_l_row, uint32_t *d_tsd, uint32_t *d_status, uint32_t *d_len,
                               uint32_t *d_mm, uint32_t *d_closures, uint64_t *d_seq10, size_t *n_pairs);
 
+/* ---- TIDDIT_CLIPS_MEI: gapped local alignment of short queries to a family library ------------------------------------------ *
+ * Smith-Waterman with affine gaps (Gotoh) of n queries against every sequence of a library, on both strands, with an integer
+ * tie rule that makes the result unique (csrc/tdt_swalign.hip); the definition is tiddit_amd/tiddit_clip_mei.py's.  The LIBRARY is a
+ * tdt_refseq handle of its own whose every sequence is loaded (tdt_refseq_load_fasta): 1 ... TDT_SW_LIB_MAX_SEQS sequences of
+ * 1 ... TDT_SW_LIB_MAX_BASES bases, TDT_SW_LIB_MAX_BASES in all; a problem reads exactly its sequence's bases.  A QUERY is 1 ...
+ * TDT_SW_QMAX bases A C G T = 0 1 2 3 in TDT_SW_SEQ_WORDS words of 56 bits, column 28 w + j in bits 2j + 1 : 2j of word w, zero behind
+ * its last base.  Scores: match +TDT_SW_MATCH, mismatch -TDT_SW_MISMATCH, a gap of k bases -(TDT_SW_GAP_OPEN + k TDT_SW_GAP_EXTEND), a
+ * library base that is not A C G T -TDT_SW_OTHER against anything.  Per query the nine result columns: family (0xffffffff and zeros
+ * behind it when no cell is positive), strand (1: the query's reverse complement aligned), score, qstart, qend (1-based, in the query
+ * as given), fstart, fend (1-based), second (the best score among the other sequences, 0) and second_family (0xffffffff).  The columns
+ * are written whatever A is; A (TDT_SW_MIN_SCORE_LO ... TDT_SW_QMAX) decides the counters sn_out[TDT_SW_SN_N]: queries, closed_queries,
+ * left_queries, right_queries, named (score >= A), unnamed, reverse, ambiguous (named, second == score), pairs_named, pairs_conflict.
+ * tdt_sw_align takes host arrays, tdt_sw_align_device caller-owned device arrays (outputs and sn_out on the device too; a length
+ * above TDT_SW_QMAX is taken as TDT_SW_QMAX there); both take every query as a closed pair of its own.  All nine columns NULL: the
+ * counters alone.  tdt_sw_align_timing: device milliseconds of the calling thread's last run of either: ms2 = the alignment launch, the
+ * reduction.  tdt_clip_mei runs on the pair rows of the handle's last tdt_clip_ins where they lie in HBM: a CLOSED pair gives one
+ * query (its SEQ), an OPEN pair two (its R site's consensus, then its L site's, both in reference direction); an OPEN pair is named
+ * when a part is and the named parts agree in family and strand, else it is a conflict.  tdt_clip_mei_rows reads out, per query, the
+ * pair row, the part (0 SEQ, 1 LEFT, 2 RIGHT), the length and the nine columns; *n in: the room of the arrays, out: the queries; every
+ * array NULL: the count alone.  tdt_clip_mei_timing: device milliseconds of the last tdt_clip_mei: ms3 = the query build, the alignment
+ * launch, the reduction.  Refusals: TDT_E_ARG (null pointers, some but not all output arrays, a library on another device or with a
+ * sequence that is not loaded, tdt_clip_mei without a tdt_clip_ins since the last push, reset or finish, the read-outs without a
+ * tdt_clip_mei since then), TDT_E_RANGE (A, a host query's length, a host query word with a bit set at or behind its last base, the
+ * library limits, 2^31 problems or more, too little room); a refused call leaves its outputs untouched. */
+#define TDT_SW_QMAX 280
+#define TDT_SW_SEQ_WORDS 10
+#define TDT_SW_SN_N 10
+#define TDT_SW_MIN_SCORE_LO 12
+#define TDT_SW_LIB_MAX_SEQS 4096
+#define TDT_SW_LIB_MAX_BASES (1 << 20)
+#define TDT_SW_MATCH 1
+#define TDT_SW_MISMATCH 4
+#define TDT_SW_GAP_OPEN 6
+#define TDT_SW_GAP_EXTEND 1
+#define TDT_SW_OTHER 1
+int tdt_sw_align(tdt_ctx *ctx, tdt_refseq *lib, size_t n, const uint64_t *seq10, const uint32_t *qlen, int A, uint64_t *sn_out, uint32_t *family,
+                 uint32_t *strand, uint32_t *score, uint32_t *qstart, uint32_t *qend, uint32_t *fstart, uint32_t *fend, uint32_t *second,
+                 uint32_t *second_family);
+int tdt_sw_align_device(tdt_ctx *ctx, tdt_refseq *lib, size_t n, const uint64_t *d_seq10, const uint32_t *d_qlen, int A, uint64_t *d_sn_out,
+                        uint32_t *d_family, uint32_t *d_strand, uint32_t *d_score, uint32_t *d_qstart, uint32_t *d_qend, uint32_t *d_fstart,
+                        uint32_t *d_fend, uint32_t *d_second, uint32_t *d_second_family);
+int tdt_sw_align_timing(double *ms2);
+int tdt_clip_mei(tdt_clip *h, tdt_refseq *lib, int A, uint64_t *sn_out);
+int tdt_clip_mei_rows(tdt_clip *h, uint32_t *pair, uint32_t *part, uint32_t *qlen, uint32_t *family, uint32_t *strand, uint32_t *score, uint32_t *qstart,
+                      uint32_t *qend, uint32_t *fstart, uint32_t *fend, uint32_t *second, uint32_t *second_family, size_t *n);
+int tdt_clip_mei_timing(tdt_clip *h, double *ms3);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

@@ -116,6 +116,16 @@ its evidence store as for ``TIDDIT_DEPTH_DIST``, and one launch behind the clip 
 store is neither taken nor freed.  Every other output is what it is without the switch.  A bare ``1`` means the default, so a flank of
 1 cannot be asked for.  Unset or empty is off; the switch without its partners, or any other value, ends the job with an error before
 the scan.  N ranks are refused with ``TIDDIT_CLIPS``.
+
+``TIDDIT_CLIPS_MEI=library.fa`` (valid only together with ``TIDDIT_CLIPS`` and ``TIDDIT_CLIPS_INS``) and ``TIDDIT_CLIPS_MEI_MIN=A``
+(12 ... 280, default 30; valid only with it): ``--sv`` also writes ``{o}.clips.mei.tab`` — every sequence of ``{o}.clips.ins.tab`` (a
+``CLOSED`` pair's ``SEQ``, an ``OPEN`` pair's two flanks) aligned with gaps to every sequence of the library (1 ... 4096 sequences,
+2^20 bases in all: family consensus such as Alu, L1, SVA, HERV-K) on both strands, with the best family, its strand, score and spans
+where the score is at least ``A`` (tiddit_amd/tiddit_clip_mei.py has the definition and the file's format).  The library is packed
+into HBM behind the scan, in a handle of its own, and freed behind the stage.  With ``TIDDIT_CLIPS_VCF`` the ``<INS>`` records of the
+named pairs gain ``MEI`` / ``MEISTRAND`` / ``MEISCORE`` / ``MEISPAN``; every other output is what it is without the switch.  Unset or
+empty is off; a file that cannot be read, a library outside the limits, the switch without its partners, ``TIDDIT_CLIPS_MEI_MIN``
+without the switch or out of range ends the job with an error before the scan.  N ranks are refused with ``TIDDIT_CLIPS``.
 """
 import argparse
 import os
@@ -380,6 +390,15 @@ def run_sv(args, version):
     except ValueError as e:
         # (the same)
         print("error, TIDDIT_CLIPS_INS={}: {}".format(os.environ.get("TIDDIT_CLIPS_INS"), e))
+        sys.exit(1)
+    try:
+        from . import tiddit_clip_mei
+        clips_mei = tiddit_clip_mei.parse_switch(os.environ.get("TIDDIT_CLIPS_MEI"), os.environ.get("TIDDIT_CLIPS_MEI_MIN"), clips is not None,
+                                                 clips_ins is not None)
+    except ValueError as e:
+        # (the same)
+        _var = "TIDDIT_CLIPS_MEI" if os.environ.get("TIDDIT_CLIPS_MEI") else "TIDDIT_CLIPS_MEI_MIN"
+        print("error, {}={}: {}".format(_var, os.environ.get(_var), e))
         sys.exit(1)
     try:
         from . import tiddit_clip_vcf
@@ -750,7 +769,7 @@ def run_sv(args, version):
             # TIDDIT_CLIPS_FAR: ... and placed genome-wide by its seed, the same way
             # TIDDIT_CLIPS_INS: ... and the rows are extended from the second store, paired and closed, the same way
             tiddit_clips.main(counter, prefix, coverage_data, chromosomes, clips[0], None if clips_align is None else (reference,) + clips_align,
-                              far=None if clips_far is None else (reference,) + clips_far, ins=clips_ins, keep=clip_stage_rows)
+                              far=None if clips_far is None else (reference,) + clips_far, ins=clips_ins, keep=clip_stage_rows, mei=clips_mei)
         finally:
             if (clips_align is not None or clips_far is not None) and not indels_norm and snvs is None:
                 reference.close()                     # (only these switches loaded it)
@@ -762,6 +781,8 @@ def run_sv(args, version):
             T.update({"  " + k: v for k, v in tiddit_clip_far.STAGE_SECONDS.items()})
         if clips_ins is not None:
             T.update({"  " + k: v for k, v in tiddit_clip_ins.STAGE_SECONDS.items()})
+        if clips_mei is not None:
+            T.update({"  " + k: v for k, v in tiddit_clip_mei.STAGE_SECONDS.items()})
         STAGE_NOTES.update(tiddit_clips.STAGE_NOTES)
         if clips_vcf is not None:
             # TIDDIT_CLIPS_VCF: the stages' rows become junctions, and one launch counts the reads that cross every breakpoint intact over
@@ -772,7 +793,9 @@ def run_sv(args, version):
             t = time.time()
             vcf_counts = tiddit_clip_vcf.main(tiddit_variant.LIVE_STORE, prefix, chromosomes, clips_vcf,
                                               tiddit_clip_vcf.header_parts(bam_header, sample_id, version),
-                                              clip_stage_rows.get("align"), clip_stage_rows.get("far"), clip_stage_rows.get("ins"))
+                                              clip_stage_rows.get("align"), clip_stage_rows.get("far"), clip_stage_rows.get("ins"),
+                                              mei=None if clips_mei is None else (clips_mei[1], clip_stage_rows.get("mei", []),
+                                                                                  tiddit_clip_mei.library_index(clips_mei[0])[1]))
             print(tiddit_clip_vcf.summary_line(vcf_counts))
             T["clip junction vcf ({o}.clips.vcf)"] = time.time() - t
             T.update({"  " + k: v for k, v in tiddit_clip_vcf.STAGE_SECONDS.items()})

@@ -212,6 +212,12 @@ SYMBOLS = {
     "tdt_clip_ins_timing": (_i, [_P, _P]),
     "tdt_clip_ins_sites": (_i, [_P, _sz] + [_P] * 4 + [_i, _i, _i] + [_P] * 9 + [ctypes.POINTER(_sz)]),
     "tdt_clip_ins_sites_device": (_i, [_P, _sz] + [_P] * 4 + [_i, _i, _i] + [_P] * 9 + [ctypes.POINTER(_sz)]),
+    "tdt_sw_align": (_i, [_P, _P, _sz, _P, _P, _i] + [_P] * 10),
+    "tdt_sw_align_device": (_i, [_P, _P, _sz, _P, _P, _i] + [_P] * 10),
+    "tdt_sw_align_timing": (_i, [_P]),
+    "tdt_clip_mei": (_i, [_P, _P, _i, _P]),
+    "tdt_clip_mei_rows": (_i, [_P] * 13 + [ctypes.POINTER(_sz)]),
+    "tdt_clip_mei_timing": (_i, [_P, _P]),
     "tdt_refseq_create": (_i, [_P, _i, _P, _PP]),
     "tdt_refseq_destroy": (_i, [_P]),
     "tdt_refseq_load_fasta": (_i, [_P, _i, _P, _i64, _i64, _i, _i]),

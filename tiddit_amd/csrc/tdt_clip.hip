@@ -47,6 +47,7 @@
 #include "tdt_clip_align.h"
 #include "tdt_clip_far.h"
 #include "tdt_clip_ins.h"
+#include "tdt_swalign.h"
 #include "tdt_keystore.h"
 
 typedef unsigned long long ull;
@@ -123,6 +124,15 @@ struct tdt_clip {
     bool ins_valid;
     double ms_ins[3];
     hipEvent_t ev_ins[4];                     // made by tdt_clip_ext_enable
+    // ---- TIDDIT_CLIPS_MEI: nothing below is allocated without tdt_clip_mei
+    void *d_mei;                              // the query table, the result columns, the offsets and the counters (grows)
+    size_t mei_cap;
+    sw_table mei_q;                           // ... of the last tdt_clip_mei (inside d_mei), n_mei of them; valid while the pairs are
+    sw_out mei_out;
+    size_t n_mei;
+    bool mei_valid;
+    double ms_mei[3];
+    hipEvent_t ev_mei[4];                     // made by the first tdt_clip_mei
 };
 
 __global__ __launch_bounds__(CLIP_BLOCK) void clip_keys(ks_cols I, int n, ull raw_len, unsigned min_mapq, unsigned min_clip, ull *__restrict__ k1s,
@@ -404,6 +414,9 @@ static void clip_free(tdt_clip *h) {
     if (h->ext) ks_free(&h->X);
     if (h->d_xsite) (void)hipFree(h->d_xsite);
     if (h->d_ins) (void)hipFree(h->d_ins);
+    if (h->d_mei) (void)hipFree(h->d_mei);
+    for (int k = 0; k < 4; k++)
+        if (h->ev_mei[k]) (void)hipEventDestroy(h->ev_mei[k]);
     if (h->d_pairs) (void)hipFree(h->d_pairs);
     for (int k = 0; k < 4; k++)
         if (h->ev_ins[k]) (void)hipEventDestroy(h->ev_ins[k]);
@@ -452,7 +465,7 @@ extern "C" int tdt_clip_create(tdt_ctx *ctx, int n_contigs, int min_mapq, int mi
 extern "C" int tdt_clip_destroy(tdt_clip *h) { return ks_destroy(h, clip_free); }
 
 extern "C" int tdt_clip_reset(tdt_clip *h) {
-    if (h) h->n_rows = 0, h->align_valid = h->far_valid = h->ins_valid = false;
+    if (h) h->n_rows = 0, h->align_valid = h->far_valid = h->ins_valid = h->mei_valid = false;
     if (h && h->ext) {
         const int rc = ks_reset(&h->X);
         if (rc) return rc;
@@ -468,7 +481,7 @@ static auto clip_launch(tdt_clip *h, size_t n, size_t raw_len) {
             hipLaunchKernelGGL(clip_keys, grid, dim3(CLIP_BLOCK), 0, h->ctx->stream, I, (int)n, (ull)raw_len, (unsigned)h->min_mapq, (unsigned)h->min_clip,
                                h->S.k1, h->S.k2, (ull)h->S.cap, h->S.d_state);
         });
-        if (rc == TDT_OK) h->n_rows = 0, h->align_valid = h->far_valid = h->ins_valid = false;
+        if (rc == TDT_OK) h->n_rows = 0, h->align_valid = h->far_valid = h->ins_valid = h->mei_valid = false;
         if (rc || !h->ext) return rc;
         // TIDDIT_CLIPS_INS: the extension keys of the same batch into the second store, TDT_CLIP_EXT_MAX_PER_READ slots per read
         return ks_launch(&h->X, n * TDT_CLIP_EXT_MAX_PER_READ, [&] {
@@ -576,7 +589,7 @@ extern "C" int tdt_clip_finish(tdt_clip *h, uint64_t min_support, uint64_t *sn_o
     // (a minimum support of 1 for the runs: every distinct sequence is a row)
     int rc = ks_finish_counted(h ? &h->S : nullptr, "tdt_clip", h && sn_out && n_rows, min_support, TDT_CLIP_MAX_SUPPORT, 1, SN_PUSH_N, res, seqs);
     if (rc) return rc;
-    h->align_valid = h->far_valid = h->ins_valid = false;
+    h->align_valid = h->far_valid = h->ins_valid = h->mei_valid = false;
     h->last_support = (unsigned)min_support;
     rc = clip_sites_of_rows(h->ctx, h->S, h->S.n_rows, (unsigned)min_support, clip_site_bufs{h->d_site, h->site_cap, h->rows, h->n_rows, h->ms_sites, h->ev}, sites);
     if (rc) {
@@ -937,7 +950,7 @@ extern "C" int tdt_clip_ins(tdt_clip *h, int K, int O, int M, uint64_t *sn_out) 
     int rc = ins_check_range("tdt_clip_ins", K, O, M);
     if (rc) return rc;
     TDT_HIP(hipSetDevice(h->ctx->device));
-    h->ins_valid = false;
+    h->ins_valid = h->mei_valid = false;
     h->n_pairs = 0;
     for (int k = 0; k < 3; k++) h->ms_ins[k] = 0;
     hipStream_t st = h->ctx->stream;
@@ -1066,5 +1079,135 @@ extern "C" int tdt_clip_ins_timing(tdt_clip *h, double *ms3) {
         return TDT_E_ARG;
     }
     for (int k = 0; k < 3; k++) ms3[k] = h->ms_ins[k];
+    return TDT_OK;
+}
+
+// ---- TIDDIT_CLIPS_MEI: the pair rows of the last tdt_clip_ins named against a family library where they lie (csrc/tdt_swalign.hip)
+struct clip_mei_bufs {
+    int *off;
+    ull *sn;
+    sw_table Q;
+    sw_out O;
+    size_t lay(void *base, size_t n_pairs) {                       // (room for two queries per pair)
+        tdt_carver cv(base);
+        off = cv.take<int>(n_pairs + 1), sn = cv.take<ull>(TDT_SW_SN_N);
+        size_t head = cv.size;
+        head += Q.lay(base ? (char *)base + head : nullptr, 2 * n_pairs);
+        return head + O.lay(base ? (char *)base + head : nullptr, 2 * n_pairs);
+    }
+};
+
+// sn_out: uint64[TDT_SW_SN_N].  lib: the family library, every sequence loaded; it is read, not kept.  No tdt_clip_ins since the last
+// push, reset or finish: TDT_E_ARG.
+extern "C" int tdt_clip_mei(tdt_clip *h, tdt_refseq *lib, int A, uint64_t *sn_out) {
+    if (!h || !lib || !sn_out) {
+        tdt_set_error("tdt_clip_mei: bad argument");
+        return TDT_E_ARG;
+    }
+    if (!h->S.rows_valid || !h->ins_valid) {
+        tdt_set_error("tdt_clip_mei: no tdt_clip_ins since the last push, reset or finish");
+        return TDT_E_ARG;
+    }
+    const size_t np = h->n_pairs;
+    int rc = sw_check("tdt_clip_mei", h->ctx, lib, 2 * np, A);
+    if (rc) return rc;
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    h->mei_valid = false;
+    h->n_mei = 0;
+    for (int k = 0; k < 3; k++) h->ms_mei[k] = 0;
+    for (int k = 0; k < 4; k++)
+        if (!h->ev_mei[k]) TDT_HIP(hipEventCreate(&h->ev_mei[k]));
+    hipStream_t st = h->ctx->stream;
+    clip_mei_bufs B;
+    rc = clip_grow("tdt_clip_mei", &h->d_mei, &h->mei_cap, B.lay(nullptr, np));
+    if (rc) return rc;
+    B.lay(h->d_mei, np);
+    uint64_t res[TDT_SW_SN_N] = {};
+    int nq = 0;
+    const ins_sites S{h->rows.k1, h->rows.side, h->ext_eclen, h->ext_cons5};
+    TDT_HIP(hipMemsetAsync(B.sn, 0, sizeof res, st));
+    TDT_HIP(hipEventRecord(h->ev_mei[0], st));
+    rc = sw_offsets_launch(h->ctx, np, h->pairs.status, B.off);
+    if (rc == TDT_OK) rc = sw_build_launch(h->ctx, S, np, h->pairs, B.off, B.Q);
+    if (rc) return rc;
+    TDT_HIP(hipEventRecord(h->ev_mei[1], st));
+    TDT_HIP(hipMemcpyAsync(&nq, B.off + np, 4, hipMemcpyDeviceToHost, st));
+    rc = tdt_ctx_sync(h->ctx);
+    if (rc) return rc;
+    const sw_queries Q{B.Q.seq10, B.Q.qlen, B.Q.pair, B.Q.part};
+    sw_work W{};
+    void *d_work = nullptr;
+    const size_t problems = (size_t)nq * 2 * (size_t)lib->n_contigs;
+    if (nq && tdt_dev_malloc(&d_work, W.lay(nullptr, problems)) != hipSuccess) {
+        tdt_set_error("tdt_clip_mei: out of device memory (%zu problems)", problems);
+        return TDT_E_NOMEM;
+    }
+    W.lay(d_work, problems);
+    hipError_t e = hipSuccess;
+    rc = sw_align_launch(h->ctx, lib, (size_t)nq, Q, W);
+    if (rc == TDT_OK) e = hipEventRecord(h->ev_mei[2], st);
+    if (rc == TDT_OK && e == hipSuccess) rc = sw_reduce_launch(h->ctx, lib, (size_t)nq, Q, W, A, B.O, B.sn);
+    if (rc == TDT_OK && e == hipSuccess) e = hipEventRecord(h->ev_mei[3], st);
+    if (rc == TDT_OK && e == hipSuccess) e = hipMemcpyAsync(res, B.sn, sizeof res, hipMemcpyDeviceToHost, st);
+    if (rc == TDT_OK && e == hipSuccess) rc = tdt_ctx_sync(h->ctx);
+    (void)hipStreamSynchronize(st);
+    if (d_work) (void)hipFree(d_work);
+    if (rc) return rc;
+    TDT_HIP(e);
+    for (int k = 0; k < 3; k++) {
+        float ms = 0;
+        TDT_HIP(hipEventElapsedTime(&ms, h->ev_mei[k], h->ev_mei[k + 1]));
+        h->ms_mei[k] = ms;
+    }
+    h->mei_q = B.Q, h->mei_out = B.O;
+    h->n_mei = (size_t)nq;
+    h->mei_valid = true;
+    memcpy(sn_out, res, sizeof res);
+    return TDT_OK;
+}
+
+// The queries of the last tdt_clip_mei, in the order of the pair rows (an OPEN pair's LEFT query, then its RIGHT query): the pair row,
+// the part, the length and the nine result columns.  *n in: the room of the arrays (ignored when all twelve are NULL), out: the
+// queries.  Too little room: TDT_E_RANGE, nothing written.
+extern "C" int tdt_clip_mei_rows(tdt_clip *h, uint32_t *pair, uint32_t *part, uint32_t *qlen, uint32_t *family, uint32_t *strand, uint32_t *score, uint32_t *qstart,
+                                 uint32_t *qend, uint32_t *fstart, uint32_t *fend, uint32_t *second, uint32_t *second_family, size_t *n) {
+    uint32_t *dst[12] = {pair, part, qlen, family, strand, score, qstart, qend, fstart, fend, second, second_family};
+    int given = 0;
+    for (int k = 0; k < 12; k++) given += dst[k] != nullptr;
+    if (!h || !n || (given && given != 12)) {
+        tdt_set_error("tdt_clip_mei_rows: bad argument");
+        return TDT_E_ARG;
+    }
+    if (!h->S.rows_valid || !h->ins_valid || !h->mei_valid) {
+        tdt_set_error("tdt_clip_mei_rows: no tdt_clip_mei since the last push, reset, finish or tdt_clip_ins");
+        return TDT_E_ARG;
+    }
+    const size_t have = h->n_mei;
+    if (given) {
+        if (*n < have) {
+            tdt_set_error("tdt_clip_mei_rows: room for %zu queries, %zu kept", *n, have);
+            return TDT_E_RANGE;
+        }
+        if (have) {
+            TDT_HIP(hipSetDevice(h->ctx->device));
+            hipStream_t st = h->ctx->stream;
+            const sw_table &Q = h->mei_q;
+            const sw_out &O = h->mei_out;
+            const unsigned *src[12] = {Q.pair, Q.part, Q.qlen, O.family, O.strand, O.score, O.qstart, O.qend, O.fstart, O.fend, O.second, O.second_family};
+            for (int k = 0; k < 12; k++) TDT_HIP(hipMemcpyAsync(dst[k], src[k], have * 4, hipMemcpyDeviceToHost, st));
+            TDT_HIP(hipStreamSynchronize(st));
+        }
+    }
+    *n = have;
+    return TDT_OK;
+}
+
+// device milliseconds of the last tdt_clip_mei: ms3 = the query build (offsets, table), the alignment launch, the reduction
+extern "C" int tdt_clip_mei_timing(tdt_clip *h, double *ms3) {
+    if (!h || !ms3 || !h->S.rows_valid || !h->ins_valid || !h->mei_valid) {
+        tdt_set_error("tdt_clip_mei_timing: bad argument, or no tdt_clip_mei since the last push, reset, finish or tdt_clip_ins");
+        return TDT_E_ARG;
+    }
+    for (int k = 0; k < 3; k++) ms3[k] = h->ms_mei[k];
     return TDT_OK;
 }

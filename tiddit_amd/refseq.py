@@ -101,6 +101,20 @@ def check_against_bam(fasta, names, lengths):
             raise ValueError("contig %s has %d bases in the BAM header and %d in the reference FASTA" % (name, ln, fasta.index[name][0]))
 
 
+def load_all(fasta, ctx=None):
+    """Every sequence of ``fasta`` (a FastaFile) in the order of its index, the lengths from the index -> RefSeq (a family library of
+    ``TIDDIT_CLIPS_MEI``, say: a handle of its own beside the job's reference)"""
+    names = list(fasta.references)
+    ref = RefSeq([fasta.index[n][0] for n in names], ctx=ctx)
+    try:
+        for tid, name in enumerate(names):
+            ref.load_fasta(tid, *fasta.fetch_raw(name))
+    except Exception:
+        ref.close()
+        raise
+    return ref
+
+
 def load_for_bam(fasta, names, lengths, ctx=None):
     """The reference of a job: every contig of the BAM header (``names``, ``lengths``) from ``fasta`` (a FastaFile), matched by name ->
     (RefSeq, seconds reading the file, seconds in the loads: upload + pack).  ValueError (:func:`check_against_bam`) before anything is

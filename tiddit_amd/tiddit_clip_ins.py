@@ -47,8 +47,9 @@ for the eleven counters in the order of ``SN``, then ``#CHROM POS END TSD R_SUPP
 CLOSURES SEQ LEFT_SEQ RIGHT_SEQ`` and one row per pair, all tab-separated.  ``POS = P_R``, ``END = P_L``.
 
 NOT built: insertions with a deleted stretch (``P_L > P_R + 1``); one-sided sites; checking the consensus tails against the
-reference; more than 140 columns; naming mobile-element families; joining the rows to ``{o}.vcf`` (tiddit_clip_vcf.py, ``TIDDIT_CLIPS_VCF``, writes them as genotyped
-records of their own file, ``{o}.clips.vcf``); N ranks (refused with ``TIDDIT_CLIPS``).
+reference; more than 140 columns; joining the rows to ``{o}.vcf`` (tiddit_clip_vcf.py, ``TIDDIT_CLIPS_VCF``, writes them as genotyped
+records of their own file, ``{o}.clips.vcf``); N ranks (refused with ``TIDDIT_CLIPS``).  Naming the inserted sequences against a library of
+mobile-element families is tiddit_clip_mei.py's (``TIDDIT_CLIPS_MEI``).
 """
 import ctypes
 import time

@@ -63,6 +63,11 @@ base is ``P``.  The store is 0-based ``start``, exclusive ``end`` (tiddit_depth_
         ``FORMAT`` is ``GT:RV:RR:LQ:DPF``: the genotype, ``R_SUPPORT,L_SUPPORT``, ``span_R,span_L``, ``span_lowq_R,span_lowq_L`` and
         ``left_R,right_R,left_L,right_L``, the base-exact depth step across each breakpoint.
 
+With ``TIDDIT_CLIPS_MEI`` (tiddit_clip_mei.py) the ``<INS>`` record of a pair that rule 6 there names gains, behind ``SRC`` and
+``MISMATCH``, ``MEI=family;MEISTRAND=+|-;MEISCORE=n;MEISPAN=fstart,fend``; the header gains the four ``##INFO`` lines and
+``##clips_vcf_mei_min_score=A`` behind the flank line.  Records of unnamed pairs and all other records are unchanged, and without
+the switch the file is byte for byte what it is without this paragraph.
+
 NOT built: mates of INV rows and one-sided records; discordant-pair support (``DV``) for the clip records; cross-referencing or merging
 with the records of ``{o}.vcf``; ``HOMSEQ`` and a real ``REF`` base; genotype likelihoods / ``GQ``; N ranks (refused with
 ``TIDDIT_CLIPS``).
@@ -92,6 +97,10 @@ _INFO = (("SVTYPE", "1", "String", "Type of structural variant"),
          ("RIGHT_SVINSSEQ", "1", "String", "Known sequence at the right end of an open insertion"),
          ("SRC", ".", "String", "The clip stages that found the junction: align, far, ins"),
          ("MISMATCH", ".", "Integer", "Mismatches of the two sites' placements (R, L), or inside a closed insertion's overlap"))
+_INFO_MEI = (("MEI", "1", "String", "Family of the library that the inserted sequence aligns to best"),
+             ("MEISTRAND", "1", "String", "Strand of the family the inserted sequence lies on"),
+             ("MEISCORE", "1", "Integer", "Local alignment score against the family (match 1, mismatch 4, gap 6 + length)"),
+             ("MEISPAN", "2", "Integer", "First and last base of the family that the alignment covers"))
 _FILTER = (("Ambiguous", "A site's consensus places more than once, a site is in several insertion pairs, or an insertion closes at several lengths"),)
 _FORMAT = (("GT", "1", "String", "Genotype"),
            ("RV", "2", "Integer", "Clipped reads that support the event at the R and the L site"),
@@ -153,11 +162,12 @@ def junctions_of(rows, far, counts):
     return out
 
 
-def events_of(align_rows=None, far_rows=None, ins_rows=None):
+def events_of(align_rows=None, far_rows=None, ins_rows=None, mei_calls=None):
     """rules 1 to 3: the rows of the three stages (None: the stage did not run) -> (counts: a dict over ``SN`` without ``records`` and
     ``ambiguous`` filled, events): an event is a dict with ``type`` (DEL / DUP / BND / INS), the two sites ``tid_r P_r tid_l P_l``,
     ``sup`` = (R_SUPPORT, L_SUPPORT), ``src``, ``ambiguous``, ``mm`` (a tuple, or None) and, by type, ``len hom`` or ``tsd len seq left
-    right``; and ``tid pos end``, the (first) record's place.  The events ascend as rule 6 orders them."""
+    right``; and ``tid pos end``, the (first) record's place.  The events ascend as rule 6 orders them.  ``mei_calls``: None, or {index
+    into ``ins_rows``: (family, strand, score, fstart, fend)} of ``tiddit_clip_mei.calls_for_vcf``: an INS event of such a row has it as ``mei``."""
     counts = {k: 0 for k in SN}
     found = junctions_of(align_rows, False, counts) if align_rows is not None else {}
     src = {k: "align" for k in found}
@@ -185,14 +195,15 @@ def events_of(align_rows=None, far_rows=None, ins_rows=None):
     for row in ins_rows or ():
         in_r[(row[0], row[1])] = in_r.get((row[0], row[1]), 0) + 1
         in_l[(row[0], row[2])] = in_l.get((row[0], row[2]), 0) + 1
-    for tid, pr, pl, tsd, rs, ls, _, _, status, ln, mm, closures, seq, left, right in ins_rows or ():
+    for p, (tid, pr, pl, tsd, rs, ls, _, _, status, ln, mm, closures, seq, left, right) in enumerate(ins_rows or ()):
         if (tid, pr, tid, pl) in found:
             counts["ins_explained"] += 1
             continue
         counts["ins_rows"] += 1
         events.append({"type": "INS", "tid_r": tid, "P_r": pr, "tid_l": tid, "P_l": pl, "sup": (rs, ls), "src": "ins",
                        "ambiguous": in_r[(tid, pr)] > 1 or in_l[(tid, pl)] > 1 or closures > 1, "mm": None if ln is None else (mm,), "tsd": tsd,
-                       "len": ln, "seq": seq, "left": left, "right": right, "tid": tid, "pos": pr - tsd, "end": pr - tsd})
+                       "len": ln, "seq": seq, "left": left, "right": right, "tid": tid, "pos": pr - tsd, "end": pr - tsd,
+                       "mei": None if mei_calls is None else mei_calls.get(p)})
     events.sort(key=lambda e: (e["tid"], e["pos"], e["end"], e["type"], e["tid_l"], e["P_l"]))
     return counts, events
 
@@ -265,21 +276,26 @@ def records_of(events, support, names):
             info += ("SVINSSEQ=%s;" % e["seq"]) if e["len"] is not None else "LEFT_SVINSSEQ=%s;RIGHT_SVINSSEQ=%s;" % (e["left"], e["right"])
         else:
             info = "SVTYPE=%s;END=%d;SVLEN=%d;CIPOS=0,%d;HOMLEN=%d;" % (typ, e["end"], -e["len"] if typ == "DEL" else e["len"], e["hom"], e["hom"])
+        if typ == "INS" and e.get("mei") is not None:
+            tail += ";MEI=%s;MEISTRAND=%s;MEISCORE=%d;MEISPAN=%d,%d" % e["mei"]
         out.append(((e["tid"], e["pos"], e["end"], typ, n, 0), line(e["tid"], e["pos"], "CLIP_%d" % n, "<%s>" % typ, info + tail)))
     out.sort(key=lambda r: r[0])
     return out
 
 
-def write_file(path, parts, F, counts, records):
-    """``{o}.clips.vcf`` (rule 6): ``parts`` of :func:`header_parts`, ``counts`` a dict over ``SN``, ``records`` of :func:`records_of`"""
+def write_file(path, parts, F, counts, records, mei_min=None):
+    """``{o}.clips.vcf`` (rule 6): ``parts`` of :func:`header_parts`, ``counts`` a dict over ``SN``, ``records`` of :func:`records_of``;
+    ``mei_min``: None, or the minimum score of ``TIDDIT_CLIPS_MEI``"""
     contig_lines, cmd, columns, version = parts
     out = ["##fileformat=VCFv4.1", "##source=TIDDIT-%s clips_vcf v1" % version]
     out += ['##ALT=<ID={},Description="{}">'.format(*row) for row in _ALT]
     out += contig_lines
-    out += ['##INFO=<ID={},Number={},Type={},Description="{}">'.format(*row) for row in _INFO]
+    out += ['##INFO=<ID={},Number={},Type={},Description="{}">'.format(*row) for row in _INFO + (_INFO_MEI if mei_min is not None else ())]
     out += ['##FILTER=<ID={},Description="{}">'.format(*row) for row in _FILTER]
     out += ['##FORMAT=<ID={},Number={},Type={},Description="{}">'.format(*row) for row in _FORMAT]
     out.append("##clips_vcf_flank=%d" % F)
+    if mei_min is not None:
+        out.append("##clips_vcf_mei_min_score=%d" % mei_min)
     out += ["##clips_vcf_%s=%d" % (k, counts[k]) for k in SN]
     out += [cmd, columns]
     out += [r[1] for r in records]
@@ -293,13 +309,22 @@ def finish_counts(counts, events, records):
     return counts
 
 
-def definition_file(path, parts, names, lengths, F, records_of_contig, align_rows=None, far_rows=None, ins_rows=None):
+def _mei_calls(mei):
+    """``mei`` = None or (A, the rows of ``tiddit_clip_mei.file_rows``, the families' names) -> (A or None, the calls or None)"""
+    if mei is None:
+        return None, None
+    from . import tiddit_clip_mei
+    return mei[0], tiddit_clip_mei.calls_for_vcf(mei[1], mei[0], mei[2])
+
+
+def definition_file(path, parts, names, lengths, F, records_of_contig, align_rows=None, far_rows=None, ins_rows=None, mei=None):
     """the file from the definition alone (what the tests compare a job's file with): ``records_of_contig(tid)`` -> the contig's
     (start, end, bits) -> the counters"""
-    counts, events = events_of(align_rows, far_rows, ins_rows)
+    mei_min, calls = _mei_calls(mei)
+    counts, events = events_of(align_rows, far_rows, ins_rows, calls)
     support = [boundary_support(records_of_contig(t), lengths[t], b, F) for t, b in boundaries_of(events)]
     records = records_of(events, support, names)
-    write_file(path, parts, F, finish_counts(counts, events, records), records)
+    write_file(path, parts, F, finish_counts(counts, events, records), records, mei_min)
     return counts
 
 
@@ -309,12 +334,14 @@ def summary_line(counts):
             "{inv_rows} inv").format(**counts)
 
 
-def main(store, prefix, names, F, parts, align_rows=None, far_rows=None, ins_rows=None):
+def main(store, prefix, names, F, parts, align_rows=None, far_rows=None, ins_rows=None, mei=None):
     """the stage behind the clip stages: the junctions on the host, ONE launch over the live store for all boundaries (the store stays
-    as it is), the file -> the counters (:func:`summary_line`).  Without a boundary nothing is launched."""
+    as it is), the file -> the counters (:func:`summary_line`).  Without a boundary nothing is launched.  ``mei``: None, or (A, the
+    rows of ``tiddit_clip_mei.file_rows``, the families' names) of ``TIDDIT_CLIPS_MEI``."""
     STAGE_SECONDS.clear()
     t = time.time()
-    counts, events = events_of(align_rows, far_rows, ins_rows)
+    mei_min, calls = _mei_calls(mei)
+    counts, events = events_of(align_rows, far_rows, ins_rows, calls)
     bounds = boundaries_of(events)
     STAGE_SECONDS["clip vcf junctions (host)"] = time.time() - t
     t = time.time()
@@ -324,6 +351,6 @@ def main(store, prefix, names, F, parts, align_rows=None, far_rows=None, ins_row
         STAGE_SECONDS["  clip vcf junction_support kernel (device time)"] = store.junction_ms() * 1e-3
     t = time.time()
     records = records_of(events, support, names)
-    write_file(prefix + ".clips.vcf", parts, F, finish_counts(counts, events, records), records)
+    write_file(prefix + ".clips.vcf", parts, F, finish_counts(counts, events, records), records, mei_min)
     STAGE_SECONDS["clip vcf text (host)"] = time.time() - t
     return counts

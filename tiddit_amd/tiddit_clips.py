@@ -305,6 +305,28 @@ class ClipCounter(KeyedCounter):
         """ms of the last ``ins``: [the extension store's finish, the gather, the pair launches]"""
         return self._out("ins_timing", 3, numpy.float64)
 
+    # ---- TIDDIT_CLIPS_MEI (tiddit_clip_mei.py): the pair rows of the last ``ins`` named against a family library
+    def mei(self, lib, A):
+        """``tdt_clip_mei`` on the pair rows of the last ``ins``, where they lie; ``lib``: a refseq.RefSeq with every sequence loaded
+        -> uint64[tiddit_clip_mei.SIZE]"""
+        from . import tiddit_clip_mei
+        sn = numpy.zeros(tiddit_clip_mei.SIZE, dtype=numpy.uint64)
+        _native.check(self._c("mei")(self.handle, lib.handle, int(A), _native.ptr(sn)))
+        self._n_mei = int(sn[tiddit_clip_mei.SN_INDEX["queries"]])
+        return sn
+
+    def mei_rows(self):
+        """-> (pair row, part, QLEN uint32[], the nine result columns uint32[]) of the last ``mei``, one entry per query"""
+        n = ctypes.c_size_t(getattr(self, "_n_mei", 0))
+        cols = [numpy.zeros(n.value, dtype=numpy.uint32) for _ in range(12)]
+        if n.value:
+            _native.check(self._c("mei_rows")(self.handle, *[_native.ptr(c) for c in cols], ctypes.byref(n)))
+        return cols[0], cols[1], cols[2], tuple(cols[3:])
+
+    def mei_timing(self):
+        """ms of the last ``mei``: [the query build, the alignment launch, the reduction]"""
+        return self._out("mei_timing", 3, numpy.float64)
+
 
 # ------------------------------------------------------------------------------------------- the file
 def write_file(path, counts, rows, names, coverage_data, min_support, min_mapq, min_clip):
@@ -333,14 +355,16 @@ def summary_line(counts):
                                         "malformed")))
 
 
-def main(counter, prefix, coverage_data, names, S, align=None, far=None, ins=None, keep=None):
+def main(counter, prefix, coverage_data, names, S, align=None, far=None, ins=None, keep=None, mei=None):
     """the stage behind the scan: the sort, the run lengths and the vote on the device, the file and the summary line.  ``align``:
     None, or (reference, W, K, M) of ``TIDDIT_CLIPS_ALIGN`` — the rows are then realigned where they lie, behind the finish and before
     the counter is closed (tiddit_clip_align.main, which writes ``{o}.clips.align.tab``); ``far``: None, or (reference, K, M) of
     ``TIDDIT_CLIPS_FAR`` — the rows are placed genome-wide the same way (tiddit_clip_far.main, ``{o}.clips.far.tab``); the reference is not
     closed here; ``ins``: None, or (K, O, M) of ``TIDDIT_CLIPS_INS`` — the counter has its extension store (``enable_ext``), and the rows are
     extended, paired and closed where they lie (tiddit_clip_ins.main, ``{o}.clips.ins.tab``); ``keep``: None, or a dict that receives the rows of
-    the stages that ran under ``"align"`` / ``"far"`` / ``"ins"`` (``TIDDIT_CLIPS_VCF``, tiddit_clip_vcf.py, joins them behind this stage)"""
+    the stages that ran under ``"align"`` / ``"far"`` / ``"ins"`` / ``"mei"`` (``TIDDIT_CLIPS_VCF``, tiddit_clip_vcf.py, joins them behind this stage);
+    ``mei``: None, or (library path, A) of ``TIDDIT_CLIPS_MEI`` — behind the INS stage its pair rows are named against the family library
+    where they lie (tiddit_clip_mei.main, ``{o}.clips.mei.tab``)"""
     STAGE_SECONDS.clear()
     STAGE_NOTES.clear()
     t = time.time()
@@ -369,16 +393,20 @@ def main(counter, prefix, coverage_data, names, S, align=None, far=None, ins=Non
             counter.close()
             raise
         t += time.time() - t_far                                # (the same: tiddit_clip_far.STAGE_SECONDS)
-    ins_counts = None
+    ins_counts = mei_counts = None
     if ins is not None:
         from . import tiddit_clip_ins
         t_ins = time.time()
         try:
-            ins_counts = tiddit_clip_ins.main(counter, rows, prefix, names, *ins, rows_out=None if keep is None else keep.setdefault("ins", []))
+            ins_rows = [] if keep is None else keep.setdefault("ins", [])
+            ins_counts = tiddit_clip_ins.main(counter, rows, prefix, names, *ins, rows_out=ins_rows)
+            if mei is not None:
+                from . import tiddit_clip_mei
+                mei_counts = tiddit_clip_mei.main(counter, ins_rows, prefix, names, *mei, rows_out=None if keep is None else keep.setdefault("mei", []))
         except BaseException:
             counter.close()
             raise
-        t += time.time() - t_ins                                # (the same: tiddit_clip_ins.STAGE_SECONDS)
+        t += time.time() - t_ins                                # (the same: tiddit_clip_ins.STAGE_SECONDS, tiddit_clip_mei.STAGE_SECONDS)
     counter.close()
     STAGE_SECONDS["clip sites (device: two sorts, gather, run lengths, site heads, vote, rows)"] = time.time() - t
     for k, v in zip(("sort by K2", "gather of K1", "sort by K1", "run lengths + rows", "site heads + vote + site rows"), ms.tolist()):
@@ -395,4 +423,6 @@ def main(counter, prefix, coverage_data, names, S, align=None, far=None, ins=Non
         print(tiddit_clip_far.summary_line(far_counts))
     if ins_counts is not None:
         print(tiddit_clip_ins.summary_line(ins_counts))
+    if mei_counts is not None:
+        print(tiddit_clip_mei.summary_line(mei_counts))
     return counts
