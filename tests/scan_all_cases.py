@@ -1,8 +1,10 @@
 """One small file with something in it for EVERY consumer of the ``--sv`` scan, and every consumer's result on it from the definitions.
 
-The scan decodes each batch once into HBM and up to eight consumers launch on the same columns and record bytes — the 50-bp histogram,
+The scan decodes each batch once into HBM and up to ten consumers launch on the same columns and record bytes — the 50-bp histogram,
 the coverage track, the evidence store, the allele counters, the QC tables, the duplicate key store, the indel key store (with or without
-left-normalisation), the signal predicates and gather.  Every one of them has an aimed case module of its own; this module is what they
+left-normalisation), the SNV key store, the clip key store with its extension store, the signal predicates and gather.  Behind the scan
+the clip chain runs on what the scan left: the clip rows realigned, placed genome-wide, paired into insertions, named against a family
+library and written as a genotyped VCF over the evidence store.  Every one of them has an aimed case module of its own; this module is what they
 are run on TOGETHER: :func:`generate` writes a coordinate-sorted BAM, its reference FASTA and an allele sites VCF into a directory,
 everything derived from ``SEED`` (no golden file), and :func:`expected` gives every consumer's result from its definition over the host
 reader's batches — never from a device result.
@@ -19,7 +21,13 @@ generator plants, on a grid of ``GRID`` bases over every contig of ``MIN_CONTIG`
     unclipped 5' end from several ``pos``); the pairs carry ``MC``; and a few reverse fragment sets with a member that reaches its end
     over a 50 000-base ``N`` skip, thousands of records — several spans — before the others;
   * three sites per grid point, every third of them heterozygous: about half of the bulk reads over it get the alternative base;
-  * a clipped read, a split read (``SA``) or a pair with its mate on another contig.
+  * a clipped read, a split read (``SA``) or a pair with its mate on another contig;
+  * at every fourth grid point (``k % 4 == 3``, which the three signals above leave unused) one clip-site event, five unpaired reads per
+    junction side on both strands, every one clipped by 30 bases or more (the extension store fills): a deletion of 40 ... 110 bases whose
+    clipped bases are the reference at the other side (every fifth event one with a microhomology of 1 ... 8 bases), a junction to the
+    clean window of a grid point on another contig, and facing R / L sites around sequence the reference does not hold — 48 ... 56 bases
+    (a closed pair) or 260 (an open pair), cut from a library of three families that is written beside the BAM (``all.mei.fa``), the third
+    family always on the minus strand, every second one behind a target-site duplication; one closed insertion on the last, small contig.
 
 Every bulk pair that is a proper pair of two ``100M`` reads also gets ``MC:Z:100M``."""
 import os
@@ -36,7 +44,19 @@ MIN_BQ = 13
 TRACK = (100, 20)                  # the coverage track's bin size and MAPQ cut
 OTHER_TRACK_BIN = 250              # a carry made for this bin size is of no use to a scan that writes TRACK
 FAR_SKIP = 50000                   # the N skip of the far member of a reverse fragment set
+SNV_SUPPORTS, SNV_Q, SNV_BQ = (2, 3), 20, MIN_BQ
+CLIP_SUPPORTS, CLIP_Q, CLIP_L = (2, 4), 20, 10
+CLIP_S = 4                         # the reporting support: what the chain behind the scan runs at
+ALIGN = (150, 20, 2)               # TIDDIT_CLIPS_ALIGN's W, K, M (the planted deletions lie inside W; the definition costs 2 W comparisons per site)
+FAR = (20, 2)                      # TIDDIT_CLIPS_FAR's K, M
+INS = (20, 12, 1)                  # TIDDIT_CLIPS_INS's K, O, M
+MEI_MIN = 30                       # TIDDIT_CLIPS_MEI_MIN
+FLANK = 10                         # TIDDIT_CLIPS_VCF's F
+FAMILIES = (("FamA", 300), ("FamB", 900), ("FamC", 500))
+MINUS_FAMILY = 2                   # the family whose copies are planted reverse-complemented
+CLIP_ANCHORS, INS_ANCHORS = (70, 66, 62, 58, 54), (60, 56, 52, 48, 44)        # aligned bases of the five reads of a junction side; the rest is clipped
 NAMES = ("all.bam", "all.fa", "sites.vcf")
+LIBRARY_NAME = "all.mei.fa"             # the family library, beside the three (the other modules that take this file know those three)
 _M, _I, _D, _N, _S = 0, 1, 2, 3, 4
 
 
@@ -47,6 +67,20 @@ def contigs():
 
 def paths(directory):
     return tuple(os.path.join(directory, n) for n in NAMES)
+
+
+def library_path(directory):
+    return os.path.join(directory, LIBRARY_NAME)
+
+
+def library():
+    """the family library of the planted insertions: [(name, text)], random bases"""
+    rng = np.random.default_rng([SEED, 4])
+    return [(name, "".join("ACGT"[int(x)] for x in rng.integers(0, 4, n))) for name, n in FAMILIES]
+
+
+def _rc(text):
+    return text[::-1].translate(str.maketrans("ACGT", "TGCA"))
 
 
 # ------------------------------------------------------------------------------------------- the reference
@@ -133,7 +167,10 @@ class _Planter:
         self.recs = []                                  # (tid, pos, record bytes)
         self.n = 0
         self.info = {"repeat_events": 0, "both_strand_events": 0, "long_insertions": 0, "noisy_reads": 0, "unanchored": 0, "dup_sets": 0, "far_sets": 0,
-                     "clip_reads": 0, "split_reads": 0, "discordant_pairs": 0}
+                     "clip_reads": 0, "split_reads": 0, "discordant_pairs": 0,
+                     "clip_deletions": 0, "clip_hom_deletions": 0, "clip_translocations": 0, "clip_closed": 0, "clip_open": 0, "clip_minus": 0}
+        self.library = library()
+        self.taken = set()                              # the grid points whose clean window is a translocation's other side
 
     def bases(self, tid, p, n):
         return self.seqs[self.table[tid][0]][p:p + n].tobytes().decode().upper()
@@ -249,15 +286,100 @@ class _Planter:
             self.pair("sd", tid, g + 400, [(_M, rl)], 1200 + 37 * k % 5000, tid2=t2)
             self.info["discordant_pairs"] += 1
 
+    # ---- the clip-site events (k % 4 == 3)
+    def clipped(self, tid, pos, m, rev, lead="", trail=""):
+        """an unpaired read of m reference bases at pos with these clipped bases in front of and behind them"""
+        cigar = ([(_S, len(lead))] if lead else []) + [(_M, m)] + ([(_S, len(trail))] if trail else [])
+        self.put(self.name("c"), 0x10 if rev else 0, tid, pos, cigar, lead + self.bases(tid, pos, m) + trail)
+
+    def r_site(self, tid, e, tail, anchors=CLIP_ANCHORS):
+        """five reads whose last aligned base is e (1-based), clipped into ``tail``: P = e, side R"""
+        for j, m in enumerate(anchors):
+            self.clipped(tid, e - m, m, j % 2, trail=tail[:READ_LEN - m])
+
+    def l_site(self, tid, s, head, anchors=CLIP_ANCHORS):
+        """five reads whose first aligned base is s (0-based), clipped into the end of ``head``: P = s + 1, side L"""
+        for j, m in enumerate(anchors):
+            self.clipped(tid, s, m, (j + 1) % 2, lead=head[len(head) - (READ_LEN - m):])
+
+    def _same(self, ta, a, tb, b, limit=8):
+        """how many bases from a on contig ta equal those from b on tb, up to limit"""
+        x, y = self.seqs[self.table[ta][0]], self.seqs[self.table[tb][0]]
+        h = 0
+        while h < limit and x[a + h] == y[b + h]:
+            h += 1
+        return h
+
+    def deletion(self, k, tid, g, homology):
+        """[a, a + n) is gone, left-most placement; both aligners extend through the h bases the two sides share: the R site ends h
+        bases behind a and is clipped into a + n + h ..., the L site starts at a + n and is clipped into ... a"""
+        s = self.seqs[self.table[tid][0]]
+        a = g + 30
+        for n in range(40 + 7 * k % 30, 111):
+            h = self._same(tid, a, tid, a + n, 9)
+            if s[a - 1] != s[a + n - 1] and (1 <= h <= 8 if homology else h == 0):
+                break
+        else:
+            raise AssertionError("no deletion length with the homology asked for at grid point %d" % k)
+        self.r_site(tid, a + h, self.bases(tid, a + n + h, 50))
+        self.l_site(tid, a + n, self.bases(tid, a - 50, 50))
+        self.info["clip_hom_deletions" if homology else "clip_deletions"] += 1
+
+    def translocation(self, k, tid, g, points):
+        """contig tid up to e continues at x on another contig, in the clean window of a grid point nobody else uses for this"""
+        i = (k + len(points) // 2) % len(points)
+        while points[i][1] == tid or i in self.taken:
+            i = (i + 1) % len(points)
+        self.taken.add(i)
+        _, t2, g2 = points[i]
+        a, b = self.seqs[self.table[tid][0]], self.seqs[self.table[t2][0]]
+        e, x = g + 100, g2 - 30
+        while a[e - 1] == b[x - 1]:                     # (left-most: nothing in front of the junction is shared)
+            x += 1
+        h = self._same(tid, e, t2, x)
+        self.r_site(tid, e + h, self.bases(t2, x + h, 50))
+        self.l_site(t2, x, self.bases(tid, e - 50, 50))
+        self.info["clip_translocations"] += 1
+
+    def insertion(self, i, tid, b, long):
+        """bases the reference does not hold behind base b (1-based), every second time behind a target-site duplication of 12 bases: the
+        R site at b is clipped into their start, the L site at b + 1 - d into their end; cut from family i % 3"""
+        f = i % 3
+        fam = self.library[f][1]
+        n = 260 if long else 48 + i % 9
+        o = 17 * i % (len(fam) - n)
+        ins = _rc(fam[o:o + n]) if f == MINUS_FAMILY else fam[o:o + n]
+        d = 12 * (i // 3 % 2)
+        s = self.seqs[self.table[tid][0]]
+        while chr(s[b]) == ins[0] or chr(s[b - d - 1]) == ins[-1]:       # (no base of the insertion continues either flank)
+            b += 1
+        self.r_site(tid, b, (ins + self.bases(tid, b - d, 60))[:60], INS_ANCHORS)
+        self.l_site(tid, b - d, (self.bases(tid, b - 60, 60) + ins)[-60:], INS_ANCHORS)
+        self.info["clip_open" if long else "clip_closed"] += 1
+        self.info["clip_minus"] += f == MINUS_FAMILY
+
+    def clips(self, k, tid, g, points):
+        kind, i = k // 4 % 5, k // 20
+        if kind in (0, 4):
+            self.deletion(k, tid, g, kind == 4)
+        elif kind == 1:
+            self.translocation(k, tid, g, points)
+        else:
+            self.insertion(i, tid, g + 100, kind == 3)
+
 
 def _plant(table, seqs):
     P = _Planter(table, seqs)
     big = [t for t, (_, L) in enumerate(table) if L >= MIN_CONTIG]
-    for k, tid, g in grid_points(table):
+    points = grid_points(table)
+    for k, tid, g in points:
         P.indels(k, tid, g)
         P.dups(k, tid, g)
         P.signals(k, tid, g, big)
+        if k % 4 == 3:
+            P.clips(k, tid, g, points)
     small = len(table) - 1
+    P.insertion(1, small, 700, False)
     for j in range(3):                                  # the last placed records of the file: an event, a fragment set, reads over two sites
         P.read(small, 400 + 5 * j, [(_M, 45 - 5 * j), (_D, 4), (_M, 55 + 5 * j)], j % 2)
     for j in range(2):
@@ -267,13 +389,14 @@ def _plant(table, seqs):
 
 # ------------------------------------------------------------------------------------------- the file
 def generate(directory, threads=4):
-    """write the three files of ``NAMES`` into ``directory`` -> what was planted (a dict of counts, the sites, the record count)"""
+    """write the three files of ``NAMES`` and the family library into ``directory`` -> what was planted (a dict of counts, the sites, the record count)"""
     from tiddit_amd import bamio, synth_bam
     table = contigs()
     bam, fa, vcf = paths(directory)
     seqs, sites = reference()
     _write_fasta(fa, table, seqs)
     _write_sites(vcf, table, sites)
+    _write_fasta(library_path(directory), [(n, len(t)) for n, t in library()], {n: np.frombuffer(t.encode(), dtype=np.uint8) for n, t in library()})
     bulk_path = bam + ".bulk"
     synth_bam.write_wgs_sv_bam(bulk_path, table, depth=DEPTH, read_len=READ_LEN, seed=SEED, sv_per_mb=SV_PER_MB, threads=threads, ref_seqs=seqs)
     rd = bamio.BamReader(bulk_path)
@@ -424,6 +547,13 @@ def partial(b, sites, ref):
     tiddit_alleles.count_batch(table, stats, sites.site_pos, sites.site_off, b, MIN_Q, MIN_BQ)
     out["alleles"], out["allele_stats"] = table, stats
     out["cols"] = {k: np.array(getattr(b, k)) for k in COLS}
+    from tiddit_amd import tiddit_clip_ins, tiddit_clips, tiddit_snvs
+    out["snv_keys"], out["snv_sn"] = [], {}
+    tiddit_snvs.keys_of_batch_by_read(b, out["snv_keys"], out["snv_sn"], ref, SNV_Q, SNV_BQ)
+    out["clip_keys"], out["clip_sn"] = [], {}
+    tiddit_clips.keys_of_batch_by_read(b, out["clip_keys"], out["clip_sn"], CLIP_Q, CLIP_L)
+    out["ext_events"], out["ext_keys"], out["ext_sn"] = [], [], {}
+    tiddit_clip_ins.events_of_batch_by_read(b, out["ext_events"], out["ext_keys"], out["ext_sn"], CLIP_Q, CLIP_L)
     return out
 
 
@@ -456,10 +586,11 @@ def _indel_summary(keys, sn):
 def combine(parts):
     """the partial results of a sequence of batches -> every consumer's result:
     indels / indels_norm: (sorted key rows, {S: (counts, [K1, K2, SUPPORT, REV])}[, norm_stats]); dups: (sorted key rows, counts); qc: uint64[];
-    alleles: (uint32[sites][8], reads_used, malformed); cov / track: {contig: float64 bins}; store: ({tid: (start, end, mate_pos, bits)}, int64 spans)"""
+    alleles: (uint32[sites][8], reads_used, malformed); cov / track: {contig: float64 bins}; store: ({tid: (start, end, mate_pos, bits)}, int64 spans);
+    snvs / clips: (sorted key rows, {S: (counts, the row columns)}); clip_ext: the extension keys' sorted rows; clip_chain: :func:`chain`"""
     import oracle
     import variant_stage_cases as V
-    from tiddit_amd import tiddit_dup, tiddit_indels
+    from tiddit_amd import tiddit_clips, tiddit_dup, tiddit_indels, tiddit_snvs
     table = contigs()
     res = {"records": sum(p["n"] for p in parts)}
     keys = [k for p in parts for k in p["indel_keys"]]
@@ -481,7 +612,106 @@ def combine(parts):
     rec, spans = V.pack_reference(cols, MIN_Q, MAX_INS, len(table))
     placed = cols["tid"][cols["tid"] >= 0]
     res["store"] = ({t: store_fields(rec[placed == t]) for t in range(len(table))}, spans)
+    keys = [k for p in parts for k in p["snv_keys"]]
+    res["snvs"] = (key_rows(keys), _keyed_summary(tiddit_snvs, keys, _sum_sn(parts, "snv_sn"), SNV_SUPPORTS, tiddit_snvs.SnvCounter.ROW_DTYPES))
+    keys, sn = [k for p in parts for k in p["clip_keys"]], _sum_sn(parts, "clip_sn")
+    res["clips"] = (key_rows(keys), _keyed_summary(tiddit_clips, keys, sn, CLIP_SUPPORTS, tiddit_clips.ROW_DTYPES))
+    res["clip_ext"] = key_rows([k for p in parts for k in p["ext_keys"]])
+    res["clip_chain"] = chain(tiddit_clips.summarise(keys, sn, CLIP_S)[1], [e for p in parts for e in p["ext_events"]], _sum_sn(parts, "ext_sn"), res["store"][0])
     return res
+
+
+def _keyed_summary(module, keys, sn, supports, dtypes):
+    """{S: (counts, the row columns in the handle's dtypes)} from a keyed consumer's ``summarise``"""
+    out = {}
+    for S in supports:
+        counts, rows = module.summarise(keys, sn, S)
+        out[S] = (counts, [np.array([r[c] for r in rows], dtype=dt) for c, dt in enumerate(dtypes)])
+    return out
+
+
+_PLACED = {}                # a site's placement by its definition: a function of the reference and the site alone, asked for again by every combine
+_NAMED = {}                 # the same for a query's result against the library
+_REFERENCE = []
+
+
+def _placed(stage, fn, site, *settings):
+    if not _REFERENCE:
+        _REFERENCE.append(host_reference())
+    key = (stage,) + site + settings
+    if key not in _PLACED:
+        _PLACED[key] = fn(_REFERENCE[0], *site, *settings)
+    return _PLACED[key]
+
+
+def library_codes():
+    from tiddit_amd import refseq
+    return [refseq.codes_of_bases(np.frombuffer(t.encode(), dtype=np.uint8)) for _, t in library()]
+
+
+def chain(clip_rows, ext_events, ext_sn, store):
+    """the five stages behind the clip counter from their definitions: ``clip_rows`` of ``tiddit_clips.summarise`` at ``CLIP_S``, the extended
+    events of every read with their push counters, the ``store`` definition's records {tid: (start, end, mate_pos, bits)} ->
+    {"align" / "far" / "ins" / "mei": (counts, the stage's rows), "vcf": (counts, the record lines)}"""
+    from tiddit_amd import tiddit_clip_align as A, tiddit_clip_far as F, tiddit_clip_ins as I, tiddit_clip_mei as M, tiddit_clip_vcf as V
+    table = contigs()
+    names, lengths = [n for n, _ in table], [l for _, l in table]
+    sites = [(k1, side, sup, clen) for k1, side, sup, _, _, clen, _, _, _ in clip_rows]
+    where = [(k1 >> 32, k1 & 0xffffffff, side, clen, cons) for k1, side, _, _, _, clen, cons, _, _ in clip_rows]
+    out = {}
+    out["align"] = A.summarise(sites, [_placed("align", A.place_site, w, *ALIGN) for w in where], ALIGN[2])
+    out["far"] = F.summarise(sites, [_placed("far", F.place_site, w, *FAR) for w in where], FAR[1])
+    counts, ext_sites, pairs = I.summarise(ext_events, ext_sn, CLIP_S, *INS)
+    k1, _, eclen, cons5 = I.site_columns(ext_sites)
+    cols, seq10 = I.pair_columns(pairs)
+    ins_rows = I.file_rows(k1, [s[2] for s in ext_sites], eclen, cons5, cols, seq10)
+    out["ins"] = (counts, ins_rows)
+    qs = M.queries_of_rows(ins_rows)
+    new = sorted({t for _, _, t in qs} - set(_NAMED))
+    _NAMED.update(zip(new, M.results([M.codes_of_text(t) for t in new], library_codes())))
+    res = [_NAMED[t] for _, _, t in qs]
+    counts, _ = M.summarise(res, [pt for _, pt, _ in qs], MEI_MIN, [p for p, _, _ in qs])
+    mei_rows = M.file_rows(ins_rows, [p for p, _, _ in qs], [pt for _, pt, _ in qs], [len(t) for _, _, t in qs], list(zip(*res)) if res else [[]] * M.RESULT_COLUMNS)
+    out["mei"] = (counts, mei_rows)
+    counts, events = V.events_of(out["align"][1], out["far"][1], ins_rows, M.calls_for_vcf(mei_rows, MEI_MIN, [n for n, _ in library()]))
+    support = []
+    for t, b in V.boundaries_of(events):
+        start, end, _, bits = store[t]
+        near = (start <= b + FLANK) & (end >= b - FLANK)             # (a record away from both flank bases counts nowhere in the definition)
+        support.append(V.boundary_support(zip(start[near].tolist(), end[near].tolist(), bits[near].tolist()), lengths[t], b, FLANK))
+    records = V.records_of(events, support, names)
+    out["vcf"] = (V.finish_counts(counts, events, records), [line for _, line in records])
+    return out
+
+
+STAGE_FILES = (".clips.tab", ".clips.align.tab", ".clips.far.tab", ".clips.ins.tab", ".clips.mei.tab", ".clips.vcf")
+
+
+def header_parts():
+    """what a job of this file gives tiddit_clip_vcf as its header parts"""
+    from tiddit_amd import tiddit_clip_vcf
+    return tiddit_clip_vcf.header_parts({"SQ": [{"SN": n, "LN": l} for n, l in contigs()]}, "ALL", "scan_all")
+
+
+def write_definition_files(prefix, parts, E, library_path):
+    """the six files of the clip stages from the definitions: the modules' own ``definition_file`` where they have one, ``write_file``
+    over the definition's rows where they do not; ``parts``: the batches' partial results, ``E`` their :func:`combine`"""
+    from tiddit_amd import tiddit_clip_align as A, tiddit_clip_far as F, tiddit_clip_ins as I, tiddit_clip_mei as M, tiddit_clip_vcf as V, tiddit_clips
+    table = contigs()
+    names, lengths = [n for n, _ in table], [l for _, l in table]
+    keys, sn = [k for p in parts for k in p["clip_keys"]], _sum_sn(parts, "clip_sn")
+    counts, rows = tiddit_clips.summarise(keys, sn, CLIP_S)
+    tiddit_clips.write_file(prefix + ".clips.tab", counts, rows, names, E["cov"], CLIP_S, CLIP_Q, CLIP_L)
+    chain = E["clip_chain"]
+    A.write_file(prefix + ".clips.align.tab", *chain["align"], names, *ALIGN)
+    F.write_file(prefix + ".clips.far.tab", *chain["far"], names, *FAR)
+    I.definition_file(prefix + ".clips.ins.tab", [e for p in parts for e in p["ext_events"]], _sum_sn(parts, "ext_sn"), names, CLIP_S, *INS)
+    M.definition_file(prefix + ".clips.mei.tab", chain["ins"][1], names, library_path, MEI_MIN)
+    store = E["store"][0]
+    of = lambda t: zip(store[t][0].tolist(), store[t][1].tolist(), store[t][3].tolist())
+    V.definition_file(prefix + ".clips.vcf", header_parts(), names, lengths, FLANK, of, chain["align"][1], chain["far"][1], chain["ins"][1],
+                      mei=(MEI_MIN, chain["mei"][1], [n for n, _ in library()]))
+
 
 
 def store_fields(rec):
@@ -489,7 +719,7 @@ def store_fields(rec):
     return tuple(np.ascontiguousarray(rec[f]) for f in ("start", "end", "mate_pos", "bits"))
 
 
-CONSUMERS = ("indels", "indels_norm", "dups", "qc", "alleles", "cov", "track", "store")
+CONSUMERS = ("indels", "indels_norm", "dups", "qc", "alleles", "cov", "track", "store", "snvs", "clips", "clip_ext", "clip_chain")
 
 
 def _eq(a, b):

@@ -4,9 +4,13 @@ one consumer to a batch and strips every other switch from its jobs.
 Part A runs ``tiddit_signal._scan`` itself, in process, on the file of tests/scan_all_cases.py (something in every 256 KiB of it for every
 consumer; every expectation from the definitions over the host reader's batches): all consumers attached at 64-KiB spans — dozens of
 batches, records straddling every span, the three pinned result slots, the row thread a batch behind, the key stores' reserve -> ask ->
-grow with a span inflating ahead —, the same at 1-MiB spans and at the default chunk, every consumer alone against the all-on run, the
-statistics pass's carried batches replayed to every consumer (with and without a usable second coverage column), the three stores grown
-mid-scan from room for 64 items, and an allocation refused mid-scan through the library's own hook.  Every comparison is exact.
+grow with a span inflating ahead and three keyed consumers on one stream, ONE resident reference shared by the left-normalisation, the SNV
+counter and the clip placements —, and behind that scan the clip chain on the live objects: ``tiddit_clips.main`` with the align, far, ins
+and mei stages on the counter where its rows lie, then ``tiddit_clip_vcf.main`` on ``tiddit_variant.LIVE_STORE`` in place, every row and
+every file against the definitions'.  The same at 1-MiB spans and at the default chunk, every consumer alone against the all-on run, the
+statistics pass's carried batches replayed to every consumer (with and without a usable second coverage column), the six stores grown
+mid-scan from room for 64 items, host ingest for the three keyed consumers together, and an allocation refused mid-scan through the
+library's own hook.  Every comparison is exact.
 
 Part B runs `tiddit --sv` on the sv_e2e_small fixture as fresh child processes, each under its own time limit and checked before the next
 is started: one job per switch family, then every switch in ONE job — at the default chunk and at 4-MiB spans — whose files must be the
@@ -16,6 +20,7 @@ import ctypes
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -27,7 +32,15 @@ from test_gpu_indels import SWITCHES, _files, _ok
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ATTACHABLE = ("track", "store", "alleles", "qc", "dups", "indels")          # beside the 50-bp histogram and the signal predicates, which every scan runs
+# what every attachable consumer drives in tiddit_signal: its switches, then the counter the scan leaves (beside the 50-bp histogram and the
+# signal predicates, which every scan runs).  ``_scan`` sets and resets exactly these; tests/test_scan_all_refs_cpu.py holds the table
+# against tiddit_signal's globals, so that the next consumer cannot be left out silently.
+DRIVES = {"track": ("COV_TRACK",), "store": ("KEEP_EVIDENCE",), "alleles": ("ALLELES", "ALLELE_COUNTER"), "qc": ("QC", "QC_COUNTER"),
+          "dups": ("DUPS", "DUP_COUNTER"), "indels": ("INDELS", "INDEL_REFERENCE", "INDEL_COUNTER"), "snvs": ("SNVS", "SNV_REFERENCE", "SNV_COUNTER"),
+          "clips": ("CLIPS", "CLIPS_INS", "CLIP_COUNTER")}
+ATTACHABLE = tuple(DRIVES)
+OFF = {"KEEP_EVIDENCE": False, "CLIPS_INS": False}                          # (every other switch is off as None)
+STAGES = ("align", "far", "ins", "mei")
 SPAN = str(1 << 16)
 
 
@@ -38,13 +51,17 @@ class Made:
 
 @pytest.fixture(scope="module")
 def made(tmp_path_factory):
-    """the file, the definitions' results, the sites and the resident reference (one for every scan of the module)"""
+    """the file, the definitions' results and files, the sites and the resident reference (one for every scan of the module)"""
     from tiddit_amd import fasta, refseq
     m = Made()
     m.dir = str(tmp_path_factory.mktemp("scan_all"))
     m.info = C.generate(m.dir)
     m.bam, m.fa, m.vcf = C.paths(m.dir)
-    m.E = C.expected(m.dir)
+    m.library = C.library_path(m.dir)
+    parts = C.partials(m.dir)
+    m.E = C.combine(parts)
+    C.write_definition_files(os.path.join(m.dir, "want"), parts, m.E, m.library)
+    m.files = {ext: _content(os.path.join(m.dir, "want") + ext) for ext in C.STAGE_FILES}
     m.sites = C.sites_table(m.dir)
     table = C.contigs()
     m.names, m.lengths = [n for n, _ in table], [l for _, l in table]
@@ -53,10 +70,45 @@ def made(tmp_path_factory):
     m.reference.close()
 
 
-def _collect(S, tables, data, splits, clips, cov, seen):
+def _keyed(h, supports):
+    """a keyed counter's store as a sorted multiset, and its counters and rows at every support"""
+    k1, k2 = h.keys()
+    by_support = {}
+    for s in supports:
+        counts = h.finish(s)
+        by_support[s] = (counts, list(h.rows()))
+    return C.key_rows(list(zip(k1.tolist(), k2.tolist()))), by_support
+
+
+def _chain(m, S, cov):
+    """the clip chain behind the scan as ``__main__`` runs it, on the live objects: the counter where its rows lie, the shared reference,
+    the evidence store in place -> the rows the stages kept and every file they wrote (under a prefix of their own)"""
+    from tiddit_amd import tiddit_clip_mei, tiddit_clip_vcf, tiddit_clips, tiddit_variant
+    prefix = os.path.join(tempfile.mkdtemp(dir=m.dir), "live")
+    keep = {}
+    counter, S.CLIP_COUNTER = S.CLIP_COUNTER, None                             # (tiddit_clips.main closes it, whatever happens)
+    tiddit_clips.main(counter, prefix, cov, m.names, C.CLIP_S, align=(m.reference,) + C.ALIGN, far=(m.reference,) + C.FAR, ins=C.INS, keep=keep,
+                      mei=(m.library, C.MEI_MIN))
+    assert counter.handle is None and sorted(keep) == sorted(STAGES)
+    tiddit_clip_vcf.main(tiddit_variant.LIVE_STORE, prefix, m.names, C.FLANK, C.header_parts(), keep["align"], keep["far"], keep["ins"],
+                         mei=(C.MEI_MIN, keep["mei"], tiddit_clip_mei.library_index(m.library)[1]))
+    return {"rows": {k: [tuple(r) for r in keep[k]] for k in STAGES}, "files": {ext: _content(prefix + ext) for ext in C.STAGE_FILES}}
+
+
+def _collect(m, S, tables, data, splits, clips, cov, seen):
     """everything one scan left behind, in the shapes of scan_all_cases.combine"""
     from tiddit_amd import tiddit_variant
     R = {"batches": len(seen), "records": sum(seen), "cov": cov}
+    if S.SNV_COUNTER is not None:
+        R["snvs"] = _keyed(S.SNV_COUNTER, C.SNV_SUPPORTS)
+        R["snv_reserve"] = S.SNV_COUNTER.reserve_stats()
+    if S.CLIP_COUNTER is not None:
+        e1, e2 = S.CLIP_COUNTER.ext_keys()
+        R["clips"] = _keyed(S.CLIP_COUNTER, C.CLIP_SUPPORTS) + (C.key_rows(list(zip(e1.tolist(), e2.tolist()))),)
+        R["clip_reserve"] = S.CLIP_COUNTER.reserve_stats()
+        if tiddit_variant.LIVE_STORE is not None:
+            # (in front of everything below: the junction support reads the store in place, and what the store holds is collected behind it)
+            R["chain"] = _chain(m, S, cov)
     if tables is not None:
         data, splits = tables.rows()
         text = {n: tables.clips(t) for t, n in enumerate(tables.names)}
@@ -98,6 +150,7 @@ def _scan(m, on, norm=True):
     module globals, the counters, the store, the tables and a carry nobody took are closed and reset whatever happens"""
     from tiddit_amd import bamio, tiddit_signal as S, tiddit_variant
     assert set(on) <= set(ATTACHABLE)
+    assert all(getattr(S, n) is OFF.get(n) for names in DRIVES.values() for n in names)
     seen = []
     real = S._device_scan
 
@@ -114,16 +167,19 @@ def _scan(m, on, norm=True):
         S.DUPS = True if "dups" in on else None
         S.INDELS = (2, C.INDEL_Q) if "indels" in on else None
         S.INDEL_REFERENCE = m.reference if "indels" in on and norm else None
+        S.SNVS = (C.SNV_SUPPORTS[0], C.SNV_Q, C.SNV_BQ) if "snvs" in on else None
+        S.SNV_REFERENCE = m.reference if "snvs" in on else None                # (the one handle the indel counter holds)
+        S.CLIPS = (C.CLIP_S, C.CLIP_Q, C.CLIP_L) if "clips" in on else None
+        S.CLIPS_INS = "clips" in on                                            # (clips always with the extension store)
         header, chromosomes, cov, data, splits, clips, tables = S._scan(m.bam, C.MIN_Q, C.MAX_INS, C.MIN_CONTIG, C.MIN_ANCHOR, C.MIN_CLIP, 50)
         assert chromosomes == [n for n, l in zip(m.names, m.lengths) if l >= C.MIN_CONTIG]
-        return _collect(S, tables, data, splits, clips, cov, seen)
+        return _collect(m, S, tables, data, splits, clips, cov, seen)
     finally:
         S._device_scan = real
-        S.COV_TRACK, S.KEEP_EVIDENCE, S.ALLELES, S.QC, S.DUPS, S.INDELS, S.INDEL_REFERENCE = None, False, None, None, None, None, None
-        for name in ("ALLELE_COUNTER", "QC_COUNTER", "DUP_COUNTER", "INDEL_COUNTER"):
-            if getattr(S, name) is not None:
+        for name in (n for names in DRIVES.values() for n in names):
+            if name.endswith("_COUNTER") and getattr(S, name) is not None:
                 getattr(S, name).close()
-            setattr(S, name, None)
+            setattr(S, name, OFF.get(name))
         S.COV_TRACK_BINS = None
         if tiddit_variant.LIVE_STORE is not None:
             tiddit_variant.LIVE_STORE.close()
@@ -133,7 +189,7 @@ def _scan(m, on, norm=True):
         bamio.set_carry(None)
 
 
-PARTS = ("cov", "signals", "track", "store", "alleles", "qc", "dups", "indels")
+PARTS = ("cov", "signals", "track", "store", "alleles", "qc", "dups", "indels", "snvs", "clips", "chain")
 
 
 def _differing(a, b, parts=PARTS):
@@ -149,8 +205,28 @@ def all_on(made):
         return _scan(made, ATTACHABLE)
 
 
-def _equals_definitions(R, E):
-    """every consumer's result of an all-on run against scan_all_cases.expected"""
+def _as_run(E, files):
+    """the definitions' results in the shapes an all-on run leaves them (:func:`_collect`): what a run that is right returns"""
+    R = {k: E[k] for k in ("records", "cov", "track", "store", "alleles", "qc", "dups", "snvs")}
+    R["indels"] = E["indels_norm"]
+    R["clips"] = E["clips"] + (E["clip_ext"],)
+    R["chain"] = {"rows": {k: E["clip_chain"][k][1] for k in STAGES}, "files": dict(files)}
+    return R
+
+
+def _same_keyed(name, got, want, supports):
+    """a keyed consumer's store and, per support, its counters and row columns; every failure names the part"""
+    assert np.array_equal(got[0], want[0]), "%s: the keys" % name
+    for s in supports:
+        assert np.array_equal(got[1][s][0], want[1][s][0]), "%s: the counters at support %d: %s, %s" % (name, s, got[1][s][0].tolist(), want[1][s][0].tolist())
+        assert len(got[1][s][1]) == len(want[1][s][1])
+        for c, (x, y) in enumerate(zip(got[1][s][1], want[1][s][1])):
+            assert np.array_equal(x, y), "%s: row column %d at support %d" % (name, c, s)
+
+
+def _equals_definitions(R, E, files):
+    """every consumer's result of an all-on run against scan_all_cases.expected, and the clip chain's rows and files against the
+    definitions' (``files``: scan_all_cases.write_definition_files)"""
     assert R["records"] == E["records"]
     assert list(R["cov"]) == list(E["cov"]) and list(R["track"]) == list(E["track"])
     # piece by piece, so that a failure names what differs ...
@@ -170,14 +246,32 @@ def _equals_definitions(R, E):
     assert np.array_equal(R["store"][1], E["store"][1])
     for t in E["store"][0]:
         assert all(np.array_equal(x, y) for x, y in zip(R["store"][0][t], E["store"][0][t])), t
+    _same_keyed("snvs", R["snvs"], E["snvs"], C.SNV_SUPPORTS)
+    _same_keyed("clips", R["clips"], E["clips"], C.CLIP_SUPPORTS)
+    assert np.array_equal(R["clips"][2], E["clip_ext"]) and len(E["clip_ext"]) > 0, "clips: the extension keys"
+    for stage in STAGES:
+        got, want = R["chain"]["rows"][stage], E["clip_chain"][stage][1]
+        assert len(got) == len(want) > 0, "chain: the number of %s rows: %d, %d" % (stage, len(got), len(want))
+        for c, (x, y) in enumerate(zip(zip(*got), zip(*want))):
+            assert x == y, "chain: column %d of the %s rows" % (c, stage)
+    assert sorted(R["chain"]["files"]) == sorted(files) == sorted(C.STAGE_FILES)
+    for ext in C.STAGE_FILES:
+        assert R["chain"]["files"][ext] == files[ext], "chain: the file %s" % ext
     # ... and each as a whole: shapes, dtypes, nothing more and nothing less than the definition gives
-    for name, want in (("indels", "indels_norm"), ("dups", "dups"), ("qc", "qc"), ("alleles", "alleles"), ("cov", "cov"), ("track", "track"), ("store", "store")):
+    for name, want in (("indels", "indels_norm"), ("dups", "dups"), ("qc", "qc"), ("alleles", "alleles"), ("cov", "cov"), ("track", "track"), ("store", "store"),
+                       ("snvs", "snvs")):
         assert C._eq(R[name], E[want]), name
+    assert C._eq(R["clips"], E["clips"] + (E["clip_ext"],)), "clips"
+    assert C._eq(R["chain"], _as_run(E, files)["chain"]), "chain"
 
 
 def test_all_on_at_64k_spans_every_consumer_equals_its_definition(made, all_on):
     assert all_on["batches"] >= 24 and all_on["records"] == made.info["n_records"] and list(all_on["track"]) == made.names
-    _equals_definitions(all_on, made.E)
+    _equals_definitions(all_on, made.E, made.files)
+    # the chain ran on something: every class of event the file holds (tests/test_scan_all_refs_cpu.py pins the definitions' counts)
+    vcf = all_on["chain"]["files"][".clips.vcf"]
+    assert vcf.count(b"SVTYPE=DEL") >= 3 and vcf.count(b"SVTYPE=BND") >= 6 and vcf.count(b";MEI=") >= 3
+    assert all_on["snv_reserve"][2] > 64 and all_on["clip_reserve"][2] > 64
 
 
 def test_all_on_signal_rows_clips_and_bins_equal_a_host_ingest_scan_with_nothing_attached(made, all_on, monkeypatch):
@@ -243,7 +337,7 @@ def test_carried_batches_reach_every_consumer_and_are_gone_afterwards(made, all_
     assert 3 <= len(held) < all_on["batches"]                                  # (at least 3 and fewer than all batches were retained)
     assert R["batches"] == all_on["batches"] and R["records"] == all_on["records"]
     assert _differing(R, all_on) == []
-    _equals_definitions(R, made.E)
+    _equals_definitions(R, made.E, made.files)
     assert all(b._retained is None and not b._live for b in held)
     assert ctx.lib.tdt_device_cache_bytes(ctx.handle) > 0                      # (their buffers and the reader's went to the ingest cache)
     _native.check(ctx.lib.tdt_device_cache_flush(ctx.handle, None))
@@ -251,8 +345,8 @@ def test_carried_batches_reach_every_consumer_and_are_gone_afterwards(made, all_
 
 
 def _tiny(monkeypatch, dup_class=None):
-    """the three stores of the scan start with room for 64 items (the names as ``_scan`` looks them up)"""
-    from tiddit_amd import tiddit_dup, tiddit_indels, tiddit_region
+    """the six stores of the scan start with room for 64 items (the names as ``_scan`` looks them up)"""
+    from tiddit_amd import tiddit_clips, tiddit_dup, tiddit_indels, tiddit_region, tiddit_snvs
 
     def small(cls):
         class Tiny(cls):
@@ -262,6 +356,12 @@ def _tiny(monkeypatch, dup_class=None):
     monkeypatch.setattr(tiddit_dup, "DupCounter", small(dup_class or tiddit_dup.DupCounter))
     monkeypatch.setattr(tiddit_indels, "IndelCounter", small(tiddit_indels.IndelCounter))
     monkeypatch.setattr(tiddit_region, "EvidenceStore", small(tiddit_region.EvidenceStore))
+    monkeypatch.setattr(tiddit_snvs, "SnvCounter", small(tiddit_snvs.SnvCounter))
+
+    class TinyClips(small(tiddit_clips.ClipCounter)):
+        def enable_ext(self, capacity=None):
+            super().enable_ext(capacity=64)
+    monkeypatch.setattr(tiddit_clips, "ClipCounter", TinyClips)
 
 
 def _grown(R):
@@ -269,6 +369,10 @@ def _grown(R):
     assert asks >= 1 and grows >= 1 and cap > 64, R["indel_reserve"]
     # (the dup store has no accessor for its capacity: it holds more keys than it had room for, and its kernel never writes past its room)
     assert len(R["dups"][0]) > 64 and R["store_capacity"] > 64
+    for name in ("snv_reserve", "clip_reserve"):
+        asks, grows, cap = R[name]
+        assert asks >= 1 and grows >= 1 and cap > 64, (name, R[name])
+    assert len(R["clips"][2]) > 64                                             # (the extension store has no accessor either)
 
 
 def test_the_stores_grow_mid_scan(made, all_on, monkeypatch):
@@ -276,9 +380,20 @@ def test_the_stores_grow_mid_scan(made, all_on, monkeypatch):
     _tiny(monkeypatch)
     R = _scan(made, ATTACHABLE)
     assert R["batches"] == all_on["batches"] and _differing(R, all_on) == []
-    _equals_definitions(R, made.E)
+    _equals_definitions(R, made.E, made.files)                                 # (the junction support among it: the evidence store it read had grown)
     _grown(R)
-    assert all_on["indel_reserve"][1] == 0                                     # (the all-on run's stores were made large enough: nothing grew there)
+    assert all_on["indel_reserve"][1] == all_on["snv_reserve"][1] == all_on["clip_reserve"][1] == 0       # (the all-on run's stores were made large enough: nothing grew there)
+
+
+def test_host_ingest_with_the_three_keyed_consumers_together(made, all_on, monkeypatch):
+    """``TIDDIT_HOST_INGEST=1``: the host reader's batches through ``push_host_batch`` of the indel, the SNV and the clip counter, which
+    share one upload block per handle"""
+    monkeypatch.setenv("TIDDIT_HOST_INGEST", "1")
+    H = _scan(made, ("indels", "snvs", "clips"))
+    assert H["batches"] == 0 and H["records"] == 0                             # (no device batch)
+    assert [k for k in PARTS if k in H] == ["cov", "signals", "indels", "snvs", "clips"]
+    assert _differing(H, all_on, ("indels", "snvs", "clips")) == []
+    assert len(H["snvs"][0]) > 0 and len(H["clips"][0]) > 0 and len(H["clips"][2]) > 0
 
 
 def test_an_allocation_refused_mid_scan_is_retried_behind_the_cache_flush(made, all_on, monkeypatch):
@@ -302,17 +417,21 @@ def test_an_allocation_refused_mid_scan_is_retried_behind_the_cache_flush(made, 
         lib.tdt_debug_fail_next_malloc(0)
     assert len(armed) == 1 and len(held) >= 3
     assert R["batches"] == all_on["batches"] and _differing(R, all_on) == []
-    _equals_definitions(R, made.E)
+    _equals_definitions(R, made.E, made.files)
     _grown(R)
 
 
 # ---- part B: every switch in one job ----------------------------------------------------------------------------------------------
-ALL_SWITCHES = tuple(SWITCHES) + ("TIDDIT_INDELS_NORM", "TIDDIT_INGEST_CHUNK", "TIDDIT_NO_CARRY")
-SUMMARIES = ("qc tables:", "duplicates:", "indels:", "indels, left-normalised:", "allele counts:", "note: TIDDIT_CNV skips", "note: TIDDIT_ASCN skips")
+ALL_SWITCHES = tuple(SWITCHES) + ("TIDDIT_INDELS_NORM", "TIDDIT_INGEST_CHUNK", "TIDDIT_NO_CARRY", "TIDDIT_SNVS", "TIDDIT_CLIPS", "TIDDIT_CLIPS_ALIGN",
+                                  "TIDDIT_CLIPS_FAR", "TIDDIT_CLIPS_INS", "TIDDIT_CLIPS_VCF", "TIDDIT_CLIPS_MEI", "TIDDIT_CLIPS_MEI_MIN")
+NOT_SCAN_SWITCHES = ()          # a switch of the package's docstring that the jobs need not strip would be named here; today there is none
+SUMMARIES = ("qc tables:", "duplicates:", "indels:", "indels, left-normalised:", "allele counts:", "note: TIDDIT_CNV skips", "note: TIDDIT_ASCN skips",
+             "snvs:", "clips:", "clips align:", "clips far:", "clips ins:", "clips mei:", "clips vcf:")
 # the files of each family (everything else is written by every job); .vcf and .genotyped.vcf carry one line that names the job's own prefix,
 # ``##TIDDITcmd=`` (the command line): they are compared without exactly that line
 OWNED = {"qc": (".qc.tab",), "dups": (".dup.tab",), "indels": (".indels.tab",), "acn": (".alleles.tab", ".cnv.bed", ".ascn.bed"), "track": (".bed",),
-         "variants": (".vcf", ".depth_dist.tab", ".depth_summary.tab"), "genotype": (".genotyped.vcf",)}
+         "variants": (".vcf", ".depth_dist.tab", ".depth_summary.tab"), "genotype": (".genotyped.vcf",), "snvs": (".snvs.tab",),
+         "clips": (".clips.tab", ".clips.align.tab", ".clips.far.tab", ".clips.ins.tab", ".clips.mei.tab", ".clips.vcf")}
 
 
 def _job(bam, fa, out, fx, timeout=600, **env):
@@ -335,6 +454,22 @@ def _write_sites(path, fa, contigs):
                 f.write("%s\t%d\t.\t%s\t%s\t.\t.\t.\n" % (name, p + 1, ref, "ACGT"[("ACGT".index(ref) + 1) % 4] if ref in "ACGT" else "A"))
 
 
+def _write_library(path, fa, contigs):
+    """three families: pieces of the fixture's own reference (an inserted copy of one of them is a dispersed duplication, which the
+    mei stage names) — the first as it stands, the second reverse-complemented, the third with every 50th base changed"""
+    from tiddit_amd.fasta import FastaFile
+    fasta = FastaFile(fa)
+    name, ln = max(contigs, key=lambda c: c[1])
+    seq = "".join(c if c in "ACGT" else "A" for c in fasta.fetch(name).upper())
+    cut = lambda i, n: seq[(i * ln) // 4:(i * ln) // 4 + n]
+    third = list(cut(3, 400))
+    third[::50] = ["ACGT"[("ACGT".index(c) + 1) % 4] for c in third[::50]]
+    families = (("FamOne", cut(1, 300)), ("FamTwo", cut(2, 500)[::-1].translate(str.maketrans("ACGT", "TGCA"))), ("FamThree", "".join(third)))
+    with open(path, "w") as f:
+        for n, t in families:
+            f.write(">%s\n" % n + "".join(t[o:o + 60] + "\n" for o in range(0, len(t), 60)))
+
+
 @pytest.fixture(scope="module")
 def jobs(golden_dir, tmp_path_factory):
     """(each job is checked before the next one is started: a crash, a time-out or a GPU error ends the fixture there)"""
@@ -343,17 +478,20 @@ def jobs(golden_dir, tmp_path_factory):
     bam, fa, contigs = materialise(fx, d, threads=min(16, os.cpu_count() or 1))
     sites = os.path.join(d, "sites.vcf")
     _write_sites(sites, fa, contigs)
+    library = os.path.join(d, "families.fa")
+    _write_library(library, fa, contigs)
     paths = {n: os.path.join(d, n) for n in tuple(OWNED) + ("all", "all4m")}
     family = {"qc": dict(TIDDIT_QC="1"), "dups": dict(TIDDIT_DUPS="1"), "indels": dict(TIDDIT_INDELS="1:20", TIDDIT_INDELS_NORM="1"),
               "acn": dict(TIDDIT_ALLELES=sites, TIDDIT_CNV="1", TIDDIT_ASCN="1"), "track": dict(TIDDIT_COV_TRACK="500"),
-              "variants": dict(TIDDIT_VARIANTS="1", TIDDIT_DEPTH_DIST="1")}
+              "variants": dict(TIDDIT_VARIANTS="1", TIDDIT_DEPTH_DIST="1"), "snvs": dict(TIDDIT_SNVS="2"),
+              "clips": dict(TIDDIT_CLIPS="2", TIDDIT_CLIPS_ALIGN="1", TIDDIT_CLIPS_FAR="1", TIDDIT_CLIPS_INS="1", TIDDIT_CLIPS_VCF="1", TIDDIT_CLIPS_MEI=library)}
     out = {}
     for name, env in family.items():
         out[name] = _ok(_job(bam, fa, paths[name], fx, **env))
     family["genotype"] = dict(TIDDIT_GENOTYPE=paths["variants"] + ".vcf")
     out["genotype"] = _ok(_job(bam, fa, paths["genotype"], fx, **family["genotype"]))
     every = {k: v for env in family.values() for k, v in env.items()}
-    assert len(every) == sum(len(env) for env in family.values()) == 11
+    assert len(every) == sum(len(env) for env in family.values()) == 18
     out["all"] = _ok(_job(bam, fa, paths["all"], fx, **every))
     out["all4m"] = _ok(_job(bam, fa, paths["all4m"], fx, TIDDIT_INGEST_CHUNK=str(4 << 20), **every))
     assert os.path.getsize(bam) > 5 * (4 << 20)                                # (the small-span job sees more than five spans)
@@ -401,7 +539,8 @@ def test_the_summary_lines_are_the_owning_jobs(jobs):
     want = [l for n in OWNED for l in _summaries(out[n])]
     got = _summaries(out["all"])
     assert sorted(got) == sorted(want) and len(got) >= 5
-    assert {l.split(":")[0].split(",")[0] for l in got} >= {"qc tables", "duplicates", "indels", "allele counts"}
+    assert {l.split(":")[0].split(",")[0] for l in got} >= {"qc tables", "duplicates", "indels", "allele counts", "snvs", "clips", "clips align", "clips far",
+                                                            "clips ins", "clips mei", "clips vcf"}
 
 
 def test_the_all_on_job_at_4_mib_spans_writes_the_same_bytes(jobs):

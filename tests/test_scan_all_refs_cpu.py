@@ -1,7 +1,12 @@
 """The file of tests/scan_all_cases.py holds what it says it holds — so that tests/test_gpu_scan_all.py can never pass on an empty table —
 is the same bytes when made twice, and every consumer's definition over it is what the GPU tests need it to be: independent of where the
-host batches are cut, and changed by any one batch left out or fed twice."""
+host batches are cut, and changed by any one batch left out or fed twice.  The comparison helper of the GPU module names the part in
+which a result departs from its definition, and the GPU module's tables name every consumer switch of tiddit_signal and every switch of
+the package's docstring."""
+import ast
+import copy
 import os
+import re
 
 import numpy as np
 import pytest
@@ -20,6 +25,7 @@ def made(tmp_path_factory):
 
 
 def test_size_contigs_and_the_unplaced_tail(made):
+    """(67 936 records with the clip events planted, 1 250 of them theirs: the bound of 80 000 stands)"""
     d, info, batches, parts, E = made
     table = C.contigs()
     assert 30000 <= info["n_records"] == E["records"] <= 80000
@@ -121,10 +127,66 @@ def test_every_batch_holds_something_for_every_consumer(made):
     assert len(bare) <= 2, bare
 
 
+def test_every_batch_yields_an_snv_key_and_a_clip_key(made):
+    d, info, batches, parts, E = made
+    assert len(parts) >= 24
+    for i, p in enumerate(parts):
+        assert len(p["snv_keys"]) >= 1 and len(p["clip_keys"]) >= 1, i
+    assert len(E["clip_ext"]) > 0 and sum(len(p["ext_keys"]) for p in parts) == len(E["clip_ext"])
+    assert sum(1 for p in parts if p["ext_keys"]) >= len(parts) - 2           # (clips of more than 28 columns nearly everywhere)
+    # both supports report rows, and the smaller support more of them
+    for name, supports in (("snvs", C.SNV_SUPPORTS), ("clips", C.CLIP_SUPPORTS)):
+        n = [len(E[name][1][s][1][0]) for s in supports]
+        assert n[0] > n[1] >= 100, (name, n)
+    k1, side, sup, rev = E["clips"][1][C.CLIP_S][1][:4]
+    assert int(((sup >= 4) & (rev >= 1) & (sup > rev)).sum()) >= 200           # the planted sites: support >= 4 on both strands
+
+
+def test_the_clip_chain_holds_every_class_of_event(made):
+    from tiddit_amd import tiddit_clip_ins as I, tiddit_clip_mei as M
+    d, info, batches, parts, E = made
+    chain = E["clip_chain"]
+    align, far, ins, mei = (chain[k][1] for k in ("align", "far", "ins", "mei"))
+    # mated DEL junctions from align, some of them with a microhomology
+    dels = [r for r in align if r[2] == 1 and r[9] == "DEL" and r[11] is not None]
+    assert len(dels) >= 3 and sum(1 for r in dels if r[12] > 0) >= 3 and sum(1 for r in dels if r[12] == 0) >= 3
+    assert info["clip_deletions"] >= 3 and info["clip_hom_deletions"] >= 3
+    # placements that only far finds: on another contig, where align has nothing
+    unaligned = {r[:3] for r in align if r[9] is None}
+    only_far = [r for r in far if r[10] is not None and r[:3] in unaligned]
+    assert len(only_far) >= 3 and sum(1 for r in only_far if r[10] == "BND" and r[13] is not None) >= 3 and info["clip_translocations"] >= 3
+    # closed and open pairs
+    assert sum(1 for r in ins if r[8] == I.CLOSED) >= 3 and sum(1 for r in ins if r[8] == I.OPEN) >= 3
+    assert sum(1 for r in ins if r[3] > 0) >= 3 and sum(1 for r in ins if r[3] == 0) >= 3               # with and without a target-site duplication
+    # named pairs
+    calls = M.calls_for_vcf(mei, C.MEI_MIN, [n for n, _ in C.library()])
+    assert len(calls) >= 3 and sum(1 for c in calls.values() if c[1] == "-") >= 1 and len({c[0] for c in calls.values()}) >= 2
+    assert info["clip_minus"] >= 1
+    # the VCF
+    counts, lines = chain["vcf"]
+    kinds = [dict(kv.split("=", 1) for kv in l.split("\t")[7].split(";")) for l in lines]
+    assert sum(1 for k in kinds if k["SVTYPE"] == "DEL") >= 1 and sum(1 for k in kinds if k["SVTYPE"] == "BND") >= 2
+    assert sum(1 for l, k in zip(lines, kinds) if k["SVTYPE"] == "INS" and "MEI" in k and "\t<INS>\t" in l) >= 1
+    assert counts["records"] == len(lines) and counts["junctions"] >= 6 and counts["ins_rows"] >= 6
+
+
+def test_the_definitions_files_are_written_and_hold_the_chains_rows(made, tmp_path):
+    d, info, batches, parts, E = made
+    prefix = str(tmp_path / "want")
+    C.write_definition_files(prefix, parts, E, C.library_path(d))
+    for ext in C.STAGE_FILES:
+        assert os.path.getsize(prefix + ext) > 500, ext
+    body = [l for l in open(prefix + ".clips.vcf").read().split("\n") if l and not l.startswith("#")]
+    assert body == E["clip_chain"]["vcf"][1]
+    for ext, stage in ((".clips.align.tab", "align"), (".clips.far.tab", "far"), (".clips.ins.tab", "ins"), (".clips.mei.tab", "mei")):
+        rows = [l for l in open(prefix + ext).read().split("\n") if l and not l.startswith(("#", "SN\t"))]
+        assert len(rows) == len(E["clip_chain"][stage][1]), ext
+
+
 def test_the_file_is_the_same_bytes_when_made_twice(made, tmp_path):
     d = made[0]
     C.generate(str(tmp_path), threads=2)
-    for a, b in zip(C.paths(d), C.paths(str(tmp_path))):
+    for a, b in zip(C.paths(d) + (C.library_path(d),), C.paths(str(tmp_path)) + (C.library_path(str(tmp_path)),)):
         assert open(a, "rb").read() == open(b, "rb").read(), os.path.basename(a)
 
 
@@ -143,3 +205,105 @@ def test_one_batch_left_out_or_fed_twice_changes_every_result(made, which):
     i = {"first": 0, "middle": len(parts) // 2, "last": len(parts) - 1}[which]
     assert C.differing(C.combine(parts[:i] + parts[i + 1:]), E) == list(C.CONSUMERS)
     assert C.differing(C.combine(parts[:i + 1] + parts[i:]), E) == list(C.CONSUMERS)
+
+
+# ---- the GPU module's comparison helper and tables ---------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def right(made, tmp_path_factory):
+    """what an all-on run that is right leaves behind, from the definitions alone"""
+    import test_gpu_scan_all as G
+    d, info, batches, parts, E = made
+    prefix = os.path.join(str(tmp_path_factory.mktemp("scan_all_files")), "want")
+    C.write_definition_files(prefix, parts, E, C.library_path(d))
+    files = {ext: G._content(prefix + ext) for ext in C.STAGE_FILES}
+    return G, E, files
+
+
+def _one_snv_key_dropped(R):
+    R["snvs"] = (R["snvs"][0][1:], R["snvs"][1])
+
+
+def _one_snv_row_support_off(R):
+    R["snvs"][1][C.SNV_SUPPORTS[1]][1][2][0] += 1
+
+
+def _one_clip_consensus_changed(R):
+    R["clips"][1][C.CLIP_S][1][6][5] ^= 1
+
+
+def _one_extension_key_changed(R):
+    R["clips"][2][0, 1] ^= 4
+
+
+def _one_align_partner_moved(R):
+    rows = R["chain"]["rows"]["align"]
+    i = next(i for i, r in enumerate(rows) if r[5] is not None)
+    rows[i] = rows[i][:5] + (rows[i][5] + 1,) + rows[i][6:]
+
+
+def _one_mei_family_changed(R):
+    rows = R["chain"]["rows"]["mei"]
+    rows[0] = rows[0][:6] + ((rows[0][6] + 1) % 3,) + rows[0][7:]
+
+
+def _one_boundary_support_off_by_one(R):
+    lines = R["chain"]["files"][".clips.vcf"].split(b"\n")
+    i = next(i for i, l in enumerate(lines) if l and not l.startswith(b"#"))
+    f = lines[i].split(b"\t")
+    sample = f[9].split(b":")                                                   # GT:RV:RR:LQ:DPF
+    a, b = sample[2].split(b",")
+    sample[2] = b"%d,%s" % (int(a) + 1, b)
+    f[9] = b":".join(sample)
+    lines[i] = b"\t".join(f)
+    R["chain"]["files"][".clips.vcf"] = b"\n".join(lines)
+
+
+DEPARTURES = ((_one_snv_key_dropped, "snvs: the keys"), (_one_snv_row_support_off, "snvs: row column 2"), (_one_clip_consensus_changed, "clips: row column 6"),
+              (_one_extension_key_changed, "clips: the extension keys"), (_one_align_partner_moved, "chain: column 5 of the align rows"),
+              (_one_mei_family_changed, "chain: column 6 of the mei rows"), (_one_boundary_support_off_by_one, "chain: the file .clips.vcf"))
+
+
+def test_the_comparison_passes_on_the_definitions_and_names_each_departure(right):
+    G, E, files = right
+    G._equals_definitions(G._as_run(E, files), E, files)
+    noticed = 0
+    for depart, named in DEPARTURES:
+        R = copy.deepcopy(G._as_run(E, files))
+        depart(R)
+        with pytest.raises(AssertionError) as e:
+            G._equals_definitions(R, E, files)
+        assert str(e.value).startswith(named), (depart.__name__, str(e.value)[:200])
+        assert G._differing(R, G._as_run(E, files), ("snvs", "clips", "chain")) == [named.split(":")[0]]
+        noticed += 1
+    assert noticed == len(DEPARTURES) == 7                                     # departures, each noticed and named
+
+
+NOT_CONSUMERS = ("AFTER_SCAN", "BACKGROUND_WRITES", "COV_TRACK_BINS", "STAGE_SECONDS", "WRITE_SECONDS")      # what __main__ sets or reads in tiddit_signal that attaches nothing
+
+
+def test_every_consumer_switch_and_counter_of_the_scan_is_driven_by_the_attachable_table():
+    import test_gpu_scan_all as G
+    from tiddit_amd import tiddit_signal as S
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    source = open(os.path.join(repo, "tiddit_amd", "__main__.py")).read()
+    counters = {n for n in vars(S) if n.endswith("_COUNTER")}
+    switches = set(re.findall(r"tiddit_signal\.([A-Z][A-Z_]*)\b", source)) - set(NOT_CONSUMERS) - counters
+    assert counters >= {"ALLELE_COUNTER", "QC_COUNTER", "DUP_COUNTER", "INDEL_COUNTER", "SNV_COUNTER", "CLIP_COUNTER"}
+    assert switches >= {"COV_TRACK", "KEEP_EVIDENCE", "ALLELES", "QC", "DUPS", "INDELS", "SNVS", "CLIPS", "CLIPS_INS"}
+    driven = [n for names in G.DRIVES.values() for n in names]
+    assert len(driven) == len(set(driven)) and tuple(G.DRIVES) == G.ATTACHABLE
+    assert counters | switches == set(driven), sorted((counters | switches) ^ set(driven))
+    assert all(hasattr(S, n) for n in driven)
+    assert all(getattr(S, n) is G.OFF.get(n) for n in driven)                  # (and every one of them is off as the module is imported)
+
+
+def test_every_switch_the_package_names_is_stripped_from_the_jobs_environment():
+    import test_gpu_scan_all as G
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    doc = ast.get_docstring(ast.parse(open(os.path.join(repo, "tiddit_amd", "__main__.py")).read()))
+    named = set(re.findall(r"TIDDIT_[A-Z0-9_]*[A-Z0-9]", doc))
+    assert len(named) >= 19 and {"TIDDIT_SNVS", "TIDDIT_CLIPS", "TIDDIT_CLIPS_ALIGN", "TIDDIT_CLIPS_FAR", "TIDDIT_CLIPS_INS", "TIDDIT_CLIPS_VCF", "TIDDIT_CLIPS_MEI"} <= named
+    assert len(G.NOT_SCAN_SWITCHES) <= 4 and not set(G.NOT_SCAN_SWITCHES) & set(G.ALL_SWITCHES)
+    left = named - set(G.ALL_SWITCHES) - set(G.NOT_SCAN_SWITCHES)
+    assert not left, sorted(left)
+    assert len(set(G.ALL_SWITCHES)) == len(G.ALL_SWITCHES)
