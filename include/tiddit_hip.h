@@ -834,6 +834,47 @@ int tdt_debug_refseq_fill(tdt_refseq *h, int tid, int byte);
 int tdt_indel_set_reference(tdt_indel *h, tdt_refseq *ref);
 int tdt_indel_norm_stats(tdt_indel *h, uint64_t *out3);
 
+/* ---- tandem repeats at known loci (TIDDIT_STR) --------------------------------------------------------------- *
+ * The repeat lengths the reads of the --sv scan show at the loci of a catalogue (csrc/tdt_str.hip); the definition is
+ * tiddit_amd/tiddit_str.py's.  A handle keeps the loci table in HBM — lstart / lend: int32, 0-based half-open, contig-major, per contig
+ * 1 <= start < end and start >= the end in front + 1, so both ascend; motif: one uint32 per locus, the motif's length m (1 ...
+ * TDT_STR_MAX_MOTIF) in bits 0 ... 3 and the BAM 4-bit code (1 2 4 8) of its letter i in bits 4 + 4 i ...; loc_off: int64[n_contigs + 1],
+ * loc_off[0] == 0 — and a store of keys: per (eligible read, one of the first TDT_STR_MAX_PER_READ loci in its reach) with an outcome
+ * K1 = the locus index and K2 = kind << 33 | L << 1 | rev (kind 0: the read spans the locus with `flank` aligned bases on both sides,
+ * L = the query bases between the two anchor bases; 1 / 2: anchored on the left, L = how far the read's bases repeat the motif behind
+ * the anchor, closed / open at the read's end; 3 / 4: the same from the right anchor leftwards), and TDT_STR_SN_N uint64 push
+ * counters: records, eligible, in_reach, malformed, no_alignment, no_sequence, span_keys, left_keys, right_keys, unanchored, over_cap.
+ * A read with no locus in reach never has its bytes looked at; nothing outside raw[0, raw_len) is ever read.  Before every launch room
+ * for TDT_STR_MAX_PER_READ keys per read is reserved.  tdt_str_push_device takes the pointer table tdt_ingest_arrays filled (TDT_COL_*;
+ * it reads the END column beside the keyed consumers' six), enqueues the launch on the context's stream and waits for nothing unless
+ * the reserve must ask or grow; tdt_str_push uploads host columns, runs the same kernel and returns when it is done.  tdt_str_finish
+ * sorts the store and measures the runs of equal (K1, K2 >> 1) as tdt_indel_finish does, fills sn_out[TDT_STR_SN_N] and keeps EVERY
+ * set as a row (it has no reporting threshold); the store is left as it was.  tdt_str_rows / _keys / _timing / _reserve_stats: as
+ * tdt_indel's.  Refusals: TDT_E_ARG (null pointers, loc_off[0] != 0 or offsets that decrease, loci that break the table's rules, a
+ * motif outside its form, record offsets that decrease, n >= 2^31, tdt_str_rows without a finish since the last push or reset),
+ * TDT_E_RANGE (more than 2^24 contigs or loci, flank outside 1 ... TDT_STR_MAX_FLANK, min_mapq outside 0 ... 255, too little room in
+ * tdt_str_keys / tdt_str_rows, 2^30 keys or more at the finish); a refused call leaves its outputs untouched.  The read-out calls
+ * synchronise the stream.  tdt_str_sn_size() = TDT_STR_SN_N. */
+#define TDT_STR_SN_N 11
+#define TDT_STR_MAX_PER_READ 4
+#define TDT_STR_MAX_MOTIF 6
+#define TDT_STR_MAX_FLANK 100
+#define TDT_STR_MAX_LOCI (1 << 24)
+typedef struct tdt_str tdt_str;
+int tdt_str_create(tdt_ctx *ctx, const int32_t *lstart, const int32_t *lend, const uint32_t *motif, const int64_t *loc_off, int n_contigs,
+                   int flank, int min_mapq, size_t capacity, tdt_str **out);
+int tdt_str_destroy(tdt_str *h);
+int tdt_str_reset(tdt_str *h);
+int tdt_str_push_device(tdt_str *h, const void *const *d_arrays14, size_t n, size_t raw_len);
+int tdt_str_push(tdt_str *h, const uint16_t *flag, const int32_t *tid, const int32_t *pos, const int32_t *end, const uint8_t *mapq,
+                 const uint64_t *rec_off, size_t n, const uint8_t *raw, size_t raw_len);
+int tdt_str_keys(tdt_str *h, uint64_t *k1, uint64_t *k2, size_t *n);
+int tdt_str_finish(tdt_str *h, uint64_t *sn_out, size_t *n_rows);
+int tdt_str_rows(tdt_str *h, uint64_t *k1, uint64_t *k2, uint32_t *support, uint32_t *rev, size_t *n);
+int tdt_str_timing(tdt_str *h, double *ms4);
+int tdt_str_reserve_stats(tdt_str *h, uint64_t *out3);
+size_t tdt_str_sn_size(void);
+
 /* ---- SNV candidates (TIDDIT_SNVS) ------------------------------------------------------------------------ *
  * Every position where eligible reads carry a base that differs from the resident reference (csrc/tdt_snv.hip); the definition is
  * tiddit_amd/tiddit_snvs.py's.  A handle keeps a store of keys in HBM — per keyed event (an M / = / X base of an eligible read whose

@@ -290,6 +290,17 @@ def variant_stage(tiddit_variant, tiddit_vcf_header, prefix, contigs, bam_header
 
 
 def run_sv(args, version):
+    """``tiddit --sv``; the switches of the scan are documented at the head of this file, and one more here.
+
+    ``TIDDIT_STR=loci.bed`` with ``TIDDIT_STR_CUTS=F``, ``F:S`` or ``F:S:Q`` (flank 5, minimum spanning reads 5, minimum MAPQ 20; valid only
+    with ``TIDDIT_STR``): ``--sv`` also writes ``{o}.str.tab`` — for every locus of a tab-separated catalogue ``chrom start end motif [id]``
+    (0-based half-open, plain or gzip, motifs of 1 to 6 bases) the repeat lengths the eligible reads (MAPQ >= ``Q``) show between its two
+    neighbour bases with ``F`` aligned bases on both sides, a genotype where at least ``S`` reads span it, and how far reads that end inside
+    the repeat keep repeating the motif — through soft clips — with a flag where that is longer than any spanning read shows
+    (tiddit_amd/tiddit_str.py has the definition and the file's format), from a key store the scan fills in HBM and one sort behind it.  No
+    second pass over the BAM, no reference in HBM.  Unset or empty is off; a file that cannot be read, cuts of another form, or the cuts
+    without the switch end the job with an error before the scan.  One process only, refused on N ranks like ``TIDDIT_INDELS``.
+    """
     from . import tiddit_cluster, tiddit_coverage_analysis, tiddit_gc, tiddit_signal, tiddit_stats
     from .bamio import BamReader
     from .fasta import FastaFile
@@ -355,6 +366,13 @@ def run_sv(args, version):
     except ValueError as e:
         # (the same)
         print("error, TIDDIT_INDELS_NORM={}: {}".format(os.environ.get("TIDDIT_INDELS_NORM"), e))
+        sys.exit(1)
+    try:
+        from . import tiddit_str
+        strs = tiddit_str.parse_switch(os.environ.get("TIDDIT_STR"), os.environ.get("TIDDIT_STR_CUTS"))
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_STR_CUTS={}: {}".format(os.environ.get("TIDDIT_STR_CUTS"), e))
         sys.exit(1)
     try:
         from . import tiddit_snvs
@@ -470,6 +488,16 @@ def run_sv(args, version):
             print("error, TIDDIT_ALLELES={}: {}".format(alleles[0], e))
             sys.exit(1)
         t_sites = time.time() - t_sites
+    str_loci = None
+    if strs is not None:
+        # TIDDIT_STR: the loci are read now, on every rank — a file that cannot be read ends the job before anything is made
+        t_loci = time.time()
+        try:
+            str_loci = tiddit_str.read_loci(strs[0], chromosomes, [contig_length[c] for c in chromosomes])
+        except (OSError, EOFError, UnicodeDecodeError) as e:
+            print("error, TIDDIT_STR={}: {}".format(strs[0], e))
+            sys.exit(1)
+        t_loci = time.time() - t_loci
     # one process per GPU on ONE file (BASELINE configs[4]; `torchrun --nproc-per-node N -m tiddit_amd --sv ...`): rank 0 owns the
     # output files and the host-only stages, the signal scan and the clustering are shared (tiddit_signal.main_sharded,
     # tiddit_cluster.main_sharded)
@@ -496,6 +524,11 @@ def run_sv(args, version):
     if multi and indels is not None:
         # (the same: an event's support is spread over the shards, and merging per-rank rows needs an exchange of keys)
         print("error, TIDDIT_INDELS is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
+              "keys on another rank")
+        sys.exit(1)
+    if multi and strs is not None:
+        # (the same: a locus's reads are spread over the shards)
+        print("error, TIDDIT_STR is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
               "keys on another rank")
         sys.exit(1)
     if multi and snvs is not None:
@@ -688,6 +721,10 @@ def run_sv(args, version):
         tiddit_signal.CLIPS = clips
         # TIDDIT_CLIPS_INS: ... and a key per further chunk of 28 clipped bases, one more launch per batch
         tiddit_signal.CLIPS_INS = clips_ins is not None
+    if str_loci is not None:
+        # TIDDIT_STR: ... and a key per (read, known repeat locus in its reach), one launch per batch
+        str_tap = tiddit_str.attach(str_loci, strs[1:])
+        T["str loci ({} accepted; host)".format(len(str_loci))] = t_loci
     with stage("tiddit: signal extraction + coverage"):
         signal_main = tiddit_signal.main_sharded if multi else tiddit_signal.main
         try:
@@ -709,6 +746,7 @@ def run_sv(args, version):
             tiddit_signal.SNV_REFERENCE = None        # (the same)
             tiddit_signal.CLIPS = None
             tiddit_signal.CLIPS_INS = False
+            tiddit_str.detach()
             if gc_job is not None and sys.exc_info()[0] is not None and "thread" in gc_job:
                 gc_job["thread"].join()          # (the scan failed: no helper thread outlives the error)
     if rank == 0:
@@ -751,6 +789,14 @@ def run_sv(args, version):
         T["small indels ({o}.indels.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_indels.STAGE_SECONDS.items()})
         STAGE_NOTES.update(tiddit_indels.STAGE_NOTES)
+    if str_loci is not None:
+        # (the same: the sort, the genotype rule and the file)
+        counter, str_tap.counter = str_tap.counter, None
+        t = time.time()
+        tiddit_str.main(counter, str_loci, prefix, strs[1:])
+        T["tandem repeats ({o}.str.tab)"] = time.time() - t
+        T.update({"  " + k: v for k, v in tiddit_str.STAGE_SECONDS.items()})
+        STAGE_NOTES.update(tiddit_str.STAGE_NOTES)
     if snvs is not None:
         # (the same)
         counter, tiddit_signal.SNV_COUNTER = tiddit_signal.SNV_COUNTER, None

@@ -172,6 +172,17 @@ SYMBOLS = {
     "tdt_indel_sn_size": (_sz, []),
     "tdt_indel_set_reference": (_i, [_P, _P]),
     "tdt_indel_norm_stats": (_i, [_P, _P]),
+    "tdt_str_create": (_i, [_P, _P, _P, _P, _P, _i, _i, _i, _sz, _PP]),
+    "tdt_str_destroy": (_i, [_P]),
+    "tdt_str_reset": (_i, [_P]),
+    "tdt_str_push_device": (_i, [_P, _P, _sz, _sz]),
+    "tdt_str_push": (_i, [_P] * 7 + [_sz, _P, _sz]),
+    "tdt_str_keys": (_i, [_P, _P, _P, ctypes.POINTER(_sz)]),
+    "tdt_str_finish": (_i, [_P, _P, ctypes.POINTER(_sz)]),
+    "tdt_str_rows": (_i, [_P, _P, _P, _P, _P, ctypes.POINTER(_sz)]),
+    "tdt_str_timing": (_i, [_P, _P]),
+    "tdt_str_reserve_stats": (_i, [_P, _P]),
+    "tdt_str_sn_size": (_sz, []),
     "tdt_snv_create": (_i, [_P, _i, _i, _i, _sz, _P, _PP]),
     "tdt_snv_destroy": (_i, [_P]),
     "tdt_snv_reset": (_i, [_P]),

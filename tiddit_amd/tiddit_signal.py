@@ -415,6 +415,15 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             # (room for 8 keys per read is reserved before each launch, behind which a reserve asks the device for the real count)
             clipc.enable_ext(capacity=min(max(os.path.getsize(bam_file_name) // 16, 1 << 16), 1 << 26))
         T["clip keys (push)"] = 0.0
+    strc = None
+    if STR is not None:
+        # TIDDIT_STR: the loci table and a key store in HBM; every batch costs one more launch on the columns and bytes it already holds there
+        from . import tiddit_str
+        # (room for 4 keys per read is reserved before each launch; a few per cent of the reads give a key: the store starts small and a
+        #  reserve that does not fit asks the device for the real count)
+        strc = tiddit_str.StrCounter(STR.loci, STR.flank, STR.min_mapq, capacity=min(max(os.path.getsize(bam_file_name) // 64, 1 << 16), 1 << 26),
+                                     ctx=getattr(reader, "ctx", None))
+        T["str keys (push)"] = 0.0
     tables = data = splits = clips = None
     if isinstance(reader, DeviceBamReader):
         from .sigtab import SignalTables
@@ -497,6 +506,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                     t3b = time.time()
                     T["clip keys (push)"] += t3b - t3
                     t3 = t3b
+                if strc is not None:                            # (the same, beside the clip push)
+                    strc.push_device_batch(b)
+                    t3b = time.time()
+                    T["str keys (push)"] += t3b - t3
+                    t3 = t3b
                 # the per-read chain of worker (:171-221) on the device; only the selected reads come back (fields + raw records)
                 # (once the scan's kernels are enqueued nothing will read the batch's raw bytes again: the next span's inflate is started
                 #  behind them — DeviceBamReader.ahead() — and runs while this thread waits for the selected reads and hands them on)
@@ -541,6 +555,10 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 t1b = time.time()
                 clipc.push_host_batch(b)
                 T["clip keys (push)"] += time.time() - t1b
+            if strc is not None:
+                t1b = time.time()
+                strc.push_host_batch(b)
+                T["str keys (push)"] += time.time() - t1b
             tid = b.tid
             flag = b.flag.astype(numpy.int32)
             placed = tid >= 0
@@ -613,6 +631,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             snvs.close()
         if clipc is not None:
             clipc.close()
+        if strc is not None:
+            strc.close()
         raise
     finally:
         pool.shutdown(wait=True)                              # (also on an error: no row thread outlives the scan)
@@ -637,6 +657,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         snvs.ctx.sync()                                         # (the same)
     if clipc is not None:
         clipc.ctx.sync()                                        # (the same)
+    if strc is not None:
+        strc.ctx.sync()                                         # (the same)
     reader.close()
     ALLELE_COUNTER = alleles                                    # (the caller reads the counters and closes it)
     QC_COUNTER = qc                                             # (the same)
@@ -644,6 +666,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
     INDEL_COUNTER = indels                                      # (the same)
     SNV_COUNTER = snvs                                          # (the same)
     CLIP_COUNTER = clipc                                        # (the same)
+    if STR is not None:
+        STR.counter = strc                                      # (the same, in the tap that asked for it)
     if store is not None:
         from . import tiddit_variant
         if tiddit_variant.LIVE_STORE is not None:
@@ -705,6 +729,8 @@ SNV_COUNTER = None          # that counter after the last scan that had SNVS set
 CLIPS = None                # (min_support, min_mapq, min_clip): the scan also stores a key per soft clip of the reads (tiddit_clips.ClipCounter), one launch per batch
 CLIPS_INS = False           # with CLIPS: the counter also stores the clipped bases beyond column 28 (ClipCounter.enable_ext; tiddit_clip_ins.py)
 CLIP_COUNTER = None         # that counter after the last scan that had CLIPS set (the caller runs its finish and closes it), else None
+STR = None                  # a tiddit_str.ScanTap (set and cleared by tiddit_str.attach / detach): the scan also stores a key per (read, known repeat locus in its reach)
+                            # (tiddit_str.StrCounter), one launch per batch, and leaves that counter in the tap (the caller runs its finish and closes it)
 INDEL_COUNTER = None        # that counter after the last scan that had INDELS set (the caller runs its finish and closes it), else None
 KEEP_EVIDENCE = False       # the scan packs every placed record into an evidence store for the variant stage (tiddit_variant.LIVE_STORE)
 AFTER_SCAN = []             # callables main() invokes once the file has been scanned, before the tables are written (host-only work from there on)
