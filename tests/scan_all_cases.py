@@ -1,10 +1,12 @@
 """One small file with something in it for EVERY consumer of the ``--sv`` scan, and every consumer's result on it from the definitions.
 
-The scan decodes each batch once into HBM and up to ten consumers launch on the same columns and record bytes — the 50-bp histogram,
+The scan decodes each batch once into HBM and up to eleven consumers launch on the same columns and record bytes — the 50-bp histogram,
 the coverage track, the evidence store, the allele counters, the QC tables, the duplicate key store, the indel key store (with or without
-left-normalisation), the SNV key store, the clip key store with its extension store, the signal predicates and gather.  Behind the scan
-the clip chain runs on what the scan left: the clip rows realigned, placed genome-wide, paired into insertions, named against a family
-library and written as a genotyped VCF over the evidence store.  Every one of them has an aimed case module of its own; this module is what they
+left-normalisation), the SNV key store, the clip key store with its extension store, the STR key store, the signal predicates and gather.
+Behind the scan the clip chain runs on what the scan left: the clip rows realigned, placed genome-wide, paired into insertions, named
+against a family library and written as a genotyped VCF over the evidence store; and the STR stage genotypes the catalogued repeats — the
+one planted at ``g + 200`` of every grid point, written beside the BAM as ``all.str.bed``.  (tests/scan_random_cases.py writes files of
+random legal records over the same reference, sites, catalogue and library: the definitions below apply to them unchanged.)  Every one of them has an aimed case module of its own; this module is what they
 are run on TOGETHER: :func:`generate` writes a coordinate-sorted BAM, its reference FASTA and an allele sites VCF into a directory,
 everything derived from ``SEED`` (no golden file), and :func:`expected` gives every consumer's result from its definition over the host
 reader's batches — never from a device result.
@@ -57,6 +59,10 @@ MINUS_FAMILY = 2                   # the family whose copies are planted reverse
 CLIP_ANCHORS, INS_ANCHORS = (70, 66, 62, 58, 54), (60, 56, 52, 48, 44)        # aligned bases of the five reads of a junction side; the rest is clipped
 NAMES = ("all.bam", "all.fa", "sites.vcf")
 LIBRARY_NAME = "all.mei.fa"             # the family library, beside the three (the other modules that take this file know those three)
+STR_NAME = "all.str.bed"                # the catalogue of tandem-repeat loci (TIDDIT_STR), beside them too
+STR_F, STR_S, STR_Q = 5, 3, 20          # TIDDIT_STR_CUTS: the flank, the minimum number of spanning reads for a genotype, the minimum MAPQ
+STR_CUTS = (STR_F, STR_S, STR_Q)
+STR_FILE = ".str.tab"
 _M, _I, _D, _N, _S = 0, 1, 2, 3, 4
 
 
@@ -71,6 +77,28 @@ def paths(directory):
 
 def library_path(directory):
     return os.path.join(directory, LIBRARY_NAME)
+
+
+def str_path(directory):
+    return os.path.join(directory, STR_NAME)
+
+
+def str_rows(table=None):
+    """the catalogue: the repeat planted at ``g + 200`` of every grid point, [(chrom, start, end, unit, id)] — 16 bases each"""
+    table = table or contigs()
+    return [(table[tid][0], g + 200, g + 216, repeat_of(k)[0], "g%d" % k) for k, tid, g in grid_points(table)]
+
+
+_LOCI = []
+
+
+def str_loci():
+    """the catalogue as the STR definition and the device handle take it (tiddit_str.Loci; what ``read_loci`` gives of the written file)"""
+    from tiddit_amd import tiddit_str
+    if not _LOCI:
+        table = contigs()
+        _LOCI.append(tiddit_str.loci_of_rows([tuple(map(str, r)) for r in str_rows(table)], [n for n, _ in table], [l for _, l in table]))
+    return _LOCI[0]
 
 
 def library():
@@ -388,15 +416,38 @@ def _plant(table, seqs):
 
 
 # ------------------------------------------------------------------------------------------- the file
+def write_beside(directory, table, seqs, sites):
+    """what lies beside the BAM, the same for every file over this reference: the FASTA, the sites VCF, the family library, the STR catalogue"""
+    _, fa, vcf = paths(directory)
+    _write_fasta(fa, table, seqs)
+    _write_sites(vcf, table, sites)
+    _write_fasta(library_path(directory), [(n, len(t)) for n, t in library()], {n: np.frombuffer(t.encode(), dtype=np.uint8) for n, t in library()})
+    with open(str_path(directory), "w") as f:
+        f.write("".join("%s\t%d\t%d\t%s\t%s\n" % r for r in str_rows(table)))
+
+
+def write_records(bam, table, records):
+    """a coordinate-sorted BAM of records that are ALREADY encoded (``bamio.encode_record`` bytes, in file order).  ``BamWriter.write``
+    takes a record's fields and encodes them itself, and there is no public entry for ready bytes: they go into the writer's buffer,
+    which is cut into BGZF blocks of 0xff00 bytes here as the writer cuts it, in the one place of the tests that does so"""
+    from tiddit_amd import bamio
+    text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % c for c in table) + "@RG\tID:rg1\tSM:ALL\n"
+    w = bamio.BamWriter(bam, table, text=text)
+    for lo in range(0, len(records), 512):
+        w._buf += b"".join(records[lo:lo + 512])
+        while len(w._buf) >= 0xff00:
+            w._f.write(bamio._bgzf_block(bytes(w._buf[:0xff00]), w.level))
+            del w._buf[:0xff00]
+    w.close()
+
+
 def generate(directory, threads=4):
-    """write the three files of ``NAMES`` and the family library into ``directory`` -> what was planted (a dict of counts, the sites, the record count)"""
+    """write the three files of ``NAMES``, the family library and the STR catalogue into ``directory`` -> what was planted (a dict of counts, the sites, the record count)"""
     from tiddit_amd import bamio, synth_bam
     table = contigs()
     bam, fa, vcf = paths(directory)
     seqs, sites = reference()
-    _write_fasta(fa, table, seqs)
-    _write_sites(vcf, table, sites)
-    _write_fasta(library_path(directory), [(n, len(t)) for n, t in library()], {n: np.frombuffer(t.encode(), dtype=np.uint8) for n, t in library()})
+    write_beside(directory, table, seqs, sites)
     bulk_path = bam + ".bulk"
     synth_bam.write_wgs_sv_bam(bulk_path, table, depth=DEPTH, read_len=READ_LEN, seed=SEED, sv_per_mb=SV_PER_MB, threads=threads, ref_seqs=seqs)
     rd = bamio.BamReader(bulk_path)
@@ -441,14 +492,7 @@ def generate(directory, threads=4):
     tk = np.array([t if t >= 0 else 1 << 30 for t, _ in keys], dtype=np.int64)
     pk = np.array([p for _, p in keys], dtype=np.int64)
     order = np.lexsort((np.arange(len(keys)), pk, tk))               # (stable: equal positions keep bulk-then-planted order)
-    text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % c for c in table) + "@RG\tID:rg1\tSM:ALL\n"
-    w = bamio.BamWriter(bam, table, text=text)
-    for lo in range(0, len(order), 2048):
-        w._buf += b"".join(records[i] for i in order[lo:lo + 2048].tolist())
-        while len(w._buf) >= 0xff00:
-            w._f.write(bamio._bgzf_block(bytes(w._buf[:0xff00]), w.level))
-            del w._buf[:0xff00]
-    w.close()
+    write_records(bam, table, [records[i] for i in order.tolist()])
     info.update(n_records=len(records), n_planted=len(planted), sites=sites)
     return info
 
@@ -512,8 +556,8 @@ def sites_table(directory):
     return tiddit_alleles.read_sites(paths(directory)[2], [n for n, _ in table], [l for _, l in table])
 
 
-def signal_selected(b, min_q=MIN_Q, max_ins=MAX_INS, min_contig=MIN_CONTIG, min_anchor=MIN_ANCHOR, min_clip=MIN_CLIP):
-    """the reads of a host batch the signal predicates select — clip | split | discordant, tiddit_signal.pyx:184-221 on whole columns"""
+def signal_kinds(b, min_q=MIN_Q, max_ins=MAX_INS, min_contig=MIN_CONTIG, min_anchor=MIN_ANCHOR, min_clip=MIN_CLIP):
+    """the reads of a host batch each signal predicate selects -> (clip, split, discordant), tiddit_signal.pyx:184-221 on whole columns"""
     big = np.array([l >= min_contig for _, l in contigs()], dtype=bool)
     tid, flag = b.tid.astype(np.int64), b.flag.astype(np.int64)
     ok = np.zeros(len(tid), dtype=bool)
@@ -526,6 +570,12 @@ def signal_selected(b, min_q=MIN_Q, max_ins=MAX_INS, min_contig=MIN_CONTIG, min_
                                                        ((l_op == 4) & (l_len > min_clip) & (f_op == 0) & (f_len > min_anchor)))
     split = primary & (b.sa_off >= 0)
     disc = primary & ((flag & 0x8) == 0) & ((flag & 0x1) != 0) & ((isize > max_ins) | ~same)
+    return clip, split, disc
+
+
+def signal_selected(b, *cuts):
+    """the reads of a host batch the signal predicates select — clip | split | discordant"""
+    clip, split, disc = signal_kinds(b, *cuts)
     return clip | split | disc
 
 
@@ -554,6 +604,9 @@ def partial(b, sites, ref):
     tiddit_clips.keys_of_batch_by_read(b, out["clip_keys"], out["clip_sn"], CLIP_Q, CLIP_L)
     out["ext_events"], out["ext_keys"], out["ext_sn"] = [], [], {}
     tiddit_clip_ins.events_of_batch_by_read(b, out["ext_events"], out["ext_keys"], out["ext_sn"], CLIP_Q, CLIP_L)
+    from tiddit_amd import tiddit_str
+    out["str_keys"], out["str_sn"] = [], {}
+    tiddit_str.keys_of_batch(b, str_loci(), out["str_keys"], out["str_sn"], STR_F, STR_Q)
     return out
 
 
@@ -587,7 +640,8 @@ def combine(parts):
     """the partial results of a sequence of batches -> every consumer's result:
     indels / indels_norm: (sorted key rows, {S: (counts, [K1, K2, SUPPORT, REV])}[, norm_stats]); dups: (sorted key rows, counts); qc: uint64[];
     alleles: (uint32[sites][8], reads_used, malformed); cov / track: {contig: float64 bins}; store: ({tid: (start, end, mate_pos, bits)}, int64 spans);
-    snvs / clips: (sorted key rows, {S: (counts, the row columns)}); clip_ext: the extension keys' sorted rows; clip_chain: :func:`chain`"""
+    snvs / clips: (sorted key rows, {S: (counts, the row columns)}); clip_ext: the extension keys' sorted rows; clip_chain: :func:`chain`;
+    str: (sorted key rows, the push counters uint64[], the four row columns, the table of ``tiddit_str.summarise`` at ``STR_S``)"""
     import oracle
     import variant_stage_cases as V
     from tiddit_amd import tiddit_clips, tiddit_dup, tiddit_indels, tiddit_snvs
@@ -618,7 +672,16 @@ def combine(parts):
     res["clips"] = (key_rows(keys), _keyed_summary(tiddit_clips, keys, sn, CLIP_SUPPORTS, tiddit_clips.ROW_DTYPES))
     res["clip_ext"] = key_rows([k for p in parts for k in p["ext_keys"]])
     res["clip_chain"] = chain(tiddit_clips.summarise(keys, sn, CLIP_S)[1], [e for p in parts for e in p["ext_events"]], _sum_sn(parts, "ext_sn"), res["store"][0])
+    res["str"] = str_result([k for p in parts for k in p["str_keys"]], _sum_sn(parts, "str_sn"))
     return res
+
+
+def str_result(keys, sn):
+    """the STR consumer's result from every keyed outcome and the summed push counters, in the shapes the device handle gives them"""
+    from tiddit_amd import tiddit_str
+    rows = tiddit_str.rows_of_keys(keys)
+    cols = tuple(np.array([r[c] for r in rows], dtype=dt) for c, dt in enumerate(tiddit_str.StrCounter.ROW_DTYPES))
+    return (key_rows(keys), tiddit_str.counts_of(sn), cols, tiddit_str.summarise(str_loci(), rows, STR_S))
 
 
 def _keyed_summary(module, keys, sn, supports, dtypes):
@@ -694,9 +757,9 @@ def header_parts():
 
 
 def write_definition_files(prefix, parts, E, library_path):
-    """the six files of the clip stages from the definitions: the modules' own ``definition_file`` where they have one, ``write_file``
-    over the definition's rows where they do not; ``parts``: the batches' partial results, ``E`` their :func:`combine`"""
-    from tiddit_amd import tiddit_clip_align as A, tiddit_clip_far as F, tiddit_clip_ins as I, tiddit_clip_mei as M, tiddit_clip_vcf as V, tiddit_clips
+    """the six files of the clip stages and ``.str.tab`` from the definitions: the modules' own ``definition_file`` where they have one,
+    ``write_file`` over the definition's rows where they do not; ``parts``: the batches' partial results, ``E`` their :func:`combine`"""
+    from tiddit_amd import tiddit_clip_align as A, tiddit_clip_far as F, tiddit_clip_ins as I, tiddit_clip_mei as M, tiddit_clip_vcf as V, tiddit_clips, tiddit_str
     table = contigs()
     names, lengths = [n for n, _ in table], [l for _, l in table]
     keys, sn = [k for p in parts for k in p["clip_keys"]], _sum_sn(parts, "clip_sn")
@@ -711,7 +774,7 @@ def write_definition_files(prefix, parts, E, library_path):
     of = lambda t: zip(store[t][0].tolist(), store[t][1].tolist(), store[t][3].tolist())
     V.definition_file(prefix + ".clips.vcf", header_parts(), names, lengths, FLANK, of, chain["align"][1], chain["far"][1], chain["ins"][1],
                       mei=(MEI_MIN, chain["mei"][1], [n for n, _ in library()]))
-
+    tiddit_str.write_file(prefix + STR_FILE, str_loci(), E["str"][1], E["str"][3], *STR_CUTS)
 
 
 def store_fields(rec):
@@ -719,7 +782,7 @@ def store_fields(rec):
     return tuple(np.ascontiguousarray(rec[f]) for f in ("start", "end", "mate_pos", "bits"))
 
 
-CONSUMERS = ("indels", "indels_norm", "dups", "qc", "alleles", "cov", "track", "store", "snvs", "clips", "clip_ext", "clip_chain")
+CONSUMERS = ("indels", "indels_norm", "dups", "qc", "alleles", "cov", "track", "store", "snvs", "clips", "clip_ext", "clip_chain", "str")
 
 
 def _eq(a, b):

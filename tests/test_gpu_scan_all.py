@@ -2,15 +2,18 @@
 one consumer to a batch and strips every other switch from its jobs.
 
 Part A runs ``tiddit_signal._scan`` itself, in process, on the file of tests/scan_all_cases.py (something in every 256 KiB of it for every
-consumer; every expectation from the definitions over the host reader's batches): all consumers attached at 64-KiB spans — dozens of
+consumer; every expectation from the definitions over the host reader's batches): all eleven consumers attached at 64-KiB spans — dozens of
 batches, records straddling every span, the three pinned result slots, the row thread a batch behind, the key stores' reserve -> ask ->
-grow with a span inflating ahead and three keyed consumers on one stream, ONE resident reference shared by the left-normalisation, the SNV
+grow with a span inflating ahead and four keyed consumers on one stream (the STR counter with a column the others do not need, ``end``,
+and its counter left in a tap, not in a module global), ONE resident reference shared by the left-normalisation, the SNV
 counter and the clip placements —, and behind that scan the clip chain on the live objects: ``tiddit_clips.main`` with the align, far, ins
 and mei stages on the counter where its rows lie, then ``tiddit_clip_vcf.main`` on ``tiddit_variant.LIVE_STORE`` in place, every row and
-every file against the definitions'.  The same at 1-MiB spans and at the default chunk, every consumer alone against the all-on run, the
+every file against the definitions', and ``tiddit_str.main`` on the live STR counter, its ``.str.tab`` byte for byte the definitions'.
+The same at 1-MiB spans and at the default chunk, every consumer alone against the all-on run, the
 statistics pass's carried batches replayed to every consumer (with and without a usable second coverage column), the six stores grown
-mid-scan from room for 64 items, host ingest for the three keyed consumers together, and an allocation refused mid-scan through the
-library's own hook.  Every comparison is exact.
+mid-scan from room for 64 items, host ingest for the four keyed consumers together, and an allocation refused mid-scan through the
+library's own hook.  Every comparison is exact.  tests/test_gpu_scan_random.py runs the same pass, with this module's ``_scan``, ``_collect``
+and comparison, over the random legal records of tests/scan_random_cases.py.
 
 Part B runs `tiddit --sv` on the sv_e2e_small fixture as fresh child processes, each under its own time limit and checked before the next
 is started: one job per switch family, then every switch in ONE job — at the default chunk and at 4-MiB spans — whose files must be the
@@ -37,7 +40,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # against tiddit_signal's globals, so that the next consumer cannot be left out silently.
 DRIVES = {"track": ("COV_TRACK",), "store": ("KEEP_EVIDENCE",), "alleles": ("ALLELES", "ALLELE_COUNTER"), "qc": ("QC", "QC_COUNTER"),
           "dups": ("DUPS", "DUP_COUNTER"), "indels": ("INDELS", "INDEL_REFERENCE", "INDEL_COUNTER"), "snvs": ("SNVS", "SNV_REFERENCE", "SNV_COUNTER"),
-          "clips": ("CLIPS", "CLIPS_INS", "CLIP_COUNTER")}
+          "clips": ("CLIPS", "CLIPS_INS", "CLIP_COUNTER"), "str": ("STR",)}        # (STR: a tiddit_str.ScanTap, the counter inside it)
 ATTACHABLE = tuple(DRIVES)
 OFF = {"KEEP_EVIDENCE": False, "CLIPS_INS": False}                          # (every other switch is off as None)
 STAGES = ("align", "far", "ins", "mei")
@@ -49,23 +52,32 @@ class Made:
     pass
 
 
-@pytest.fixture(scope="module")
-def made(tmp_path_factory):
-    """the file, the definitions' results and files, the sites and the resident reference (one for every scan of the module)"""
-    from tiddit_amd import fasta, refseq
+def make(directory, generate=C.generate):
+    """``generate(directory)`` writes the file and what lies beside it -> the file, the definitions' results and files, the sites, the
+    loci and the resident reference (the caller closes ``reference``)"""
+    from tiddit_amd import fasta, refseq, tiddit_str
     m = Made()
-    m.dir = str(tmp_path_factory.mktemp("scan_all"))
-    m.info = C.generate(m.dir)
+    m.dir = directory
+    m.info = generate(m.dir)
     m.bam, m.fa, m.vcf = C.paths(m.dir)
     m.library = C.library_path(m.dir)
     parts = C.partials(m.dir)
     m.E = C.combine(parts)
     C.write_definition_files(os.path.join(m.dir, "want"), parts, m.E, m.library)
-    m.files = {ext: _content(os.path.join(m.dir, "want") + ext) for ext in C.STAGE_FILES}
+    m.files = {ext: _content(os.path.join(m.dir, "want") + ext) for ext in C.STAGE_FILES + (C.STR_FILE,)}
     m.sites = C.sites_table(m.dir)
     table = C.contigs()
     m.names, m.lengths = [n for n, _ in table], [l for _, l in table]
+    m.loci = tiddit_str.read_loci(C.str_path(m.dir), m.names, m.lengths)
+    assert m.loci.rows == C.str_loci().rows and not any(m.loci.skipped.values())
     m.reference = refseq.load_for_bam(fasta.FastaFile(m.fa), m.names, m.lengths)[0]
+    return m
+
+
+@pytest.fixture(scope="module")
+def made(tmp_path_factory):
+    """the file of scan_all_cases with everything :func:`make` gives (one resident reference for every scan of the module)"""
+    m = make(str(tmp_path_factory.mktemp("scan_all")))
     yield m
     m.reference.close()
 
@@ -142,13 +154,34 @@ def _collect(m, S, tables, data, splits, clips, cov, seen):
         if h.reference is not None:
             R["indels"] += (tuple(int(v) for v in h.norm_stats()),)
         R["indel_reserve"] = h.reserve_stats()
+    if S.STR is not None and S.STR.counter is not None:
+        R["str"] = _str(m, S.STR, R)
     return R
+
+
+def _str(m, tap, R):
+    """the counter the scan left in the tap: its store, counters and rows, then the stage behind the scan as ``__main__`` runs it, on that
+    live counter under a prefix of its own -> (sorted key rows, counters, row columns, the table at ``STR_S``, the file it wrote)"""
+    from tiddit_amd import tiddit_str
+    h = tap.counter                                                            # (left in the tap until the stage takes it: ``_scan`` closes what is there)
+    k1, k2 = h.keys()
+    counts = h.finish()
+    rows = h.rows()
+    R["str_reserve"] = h.reserve_stats()
+    prefix = os.path.join(tempfile.mkdtemp(dir=m.dir), "live")
+    tap.counter = None
+    try:
+        again = tiddit_str.main(h, tap.loci, prefix, C.STR_CUTS)
+    finally:
+        h.close()                                                              # (tiddit_str.main closes it behind its last read; whatever happens, it is closed here)
+    assert h.handle is None and np.array_equal(again, counts)
+    return (C.key_rows(list(zip(k1.tolist(), k2.tolist()))), counts, rows, tiddit_str.summarise(tap.loci, rows, C.STR_S), _content(prefix + C.STR_FILE))
 
 
 def _scan(m, on, norm=True):
     """``tiddit_signal._scan`` on the module's file with the consumers ``on`` attached -> what it left behind (:func:`_collect`); the
     module globals, the counters, the store, the tables and a carry nobody took are closed and reset whatever happens"""
-    from tiddit_amd import bamio, tiddit_signal as S, tiddit_variant
+    from tiddit_amd import bamio, tiddit_signal as S, tiddit_str, tiddit_variant
     assert set(on) <= set(ATTACHABLE)
     assert all(getattr(S, n) is OFF.get(n) for names in DRIVES.values() for n in names)
     seen = []
@@ -171,11 +204,16 @@ def _scan(m, on, norm=True):
         S.SNV_REFERENCE = m.reference if "snvs" in on else None                # (the one handle the indel counter holds)
         S.CLIPS = (C.CLIP_S, C.CLIP_Q, C.CLIP_L) if "clips" in on else None
         S.CLIPS_INS = "clips" in on                                            # (clips always with the extension store)
+        if "str" in on:
+            assert tiddit_str.attach(m.loci, C.STR_CUTS) is S.STR              # (as __main__ attaches it: a tap the scan leaves its counter in)
         header, chromosomes, cov, data, splits, clips, tables = S._scan(m.bam, C.MIN_Q, C.MAX_INS, C.MIN_CONTIG, C.MIN_ANCHOR, C.MIN_CLIP, 50)
         assert chromosomes == [n for n, l in zip(m.names, m.lengths) if l >= C.MIN_CONTIG]
         return _collect(m, S, tables, data, splits, clips, cov, seen)
     finally:
         S._device_scan = real
+        if S.STR is not None and S.STR.counter is not None:                    # (a counter a scan left in the tap and nobody took)
+            S.STR.counter.close()
+        tiddit_str.detach()
         for name in (n for names in DRIVES.values() for n in names):
             if name.endswith("_COUNTER") and getattr(S, name) is not None:
                 getattr(S, name).close()
@@ -189,7 +227,7 @@ def _scan(m, on, norm=True):
         bamio.set_carry(None)
 
 
-PARTS = ("cov", "signals", "track", "store", "alleles", "qc", "dups", "indels", "snvs", "clips", "chain")
+PARTS = ("cov", "signals", "track", "store", "alleles", "qc", "dups", "indels", "snvs", "clips", "chain", "str")
 
 
 def _differing(a, b, parts=PARTS):
@@ -210,7 +248,8 @@ def _as_run(E, files):
     R = {k: E[k] for k in ("records", "cov", "track", "store", "alleles", "qc", "dups", "snvs")}
     R["indels"] = E["indels_norm"]
     R["clips"] = E["clips"] + (E["clip_ext"],)
-    R["chain"] = {"rows": {k: E["clip_chain"][k][1] for k in STAGES}, "files": dict(files)}
+    R["chain"] = {"rows": {k: E["clip_chain"][k][1] for k in STAGES}, "files": {ext: files[ext] for ext in C.STAGE_FILES}}
+    R["str"] = E["str"] + (files[C.STR_FILE],)
     return R
 
 
@@ -254,15 +293,27 @@ def _equals_definitions(R, E, files):
         assert len(got) == len(want) > 0, "chain: the number of %s rows: %d, %d" % (stage, len(got), len(want))
         for c, (x, y) in enumerate(zip(zip(*got), zip(*want))):
             assert x == y, "chain: column %d of the %s rows" % (c, stage)
-    assert sorted(R["chain"]["files"]) == sorted(files) == sorted(C.STAGE_FILES)
+    assert sorted(R["chain"]["files"]) == sorted(C.STAGE_FILES) and sorted(files) == sorted(C.STAGE_FILES + (C.STR_FILE,))
     for ext in C.STAGE_FILES:
         assert R["chain"]["files"][ext] == files[ext], "chain: the file %s" % ext
+    keys, counts, cols, table, text = R["str"]
+    wkeys, wcounts, wcols, wtable = E["str"]
+    assert np.array_equal(keys, wkeys), "str: the keys"
+    assert np.array_equal(counts, wcounts), "str: the counters: %s, %s" % (counts.tolist(), wcounts.tolist())
+    assert len(cols) == len(wcols) == 4
+    for c, (x, y) in enumerate(zip(cols, wcols)):
+        assert np.array_equal(x, y), "str: row column %d" % c
+    assert len(table) == len(wtable)
+    for k, (x, y) in enumerate(zip(table, wtable)):
+        assert x == y, "str: the table's row of locus %d: %s, %s" % (k, x, y)
+    assert text == files[C.STR_FILE], "str: the file %s" % C.STR_FILE
     # ... and each as a whole: shapes, dtypes, nothing more and nothing less than the definition gives
     for name, want in (("indels", "indels_norm"), ("dups", "dups"), ("qc", "qc"), ("alleles", "alleles"), ("cov", "cov"), ("track", "track"), ("store", "store"),
                        ("snvs", "snvs")):
         assert C._eq(R[name], E[want]), name
     assert C._eq(R["clips"], E["clips"] + (E["clip_ext"],)), "clips"
     assert C._eq(R["chain"], _as_run(E, files)["chain"]), "chain"
+    assert C._eq(R["str"], _as_run(E, files)["str"]), "str"
 
 
 def test_all_on_at_64k_spans_every_consumer_equals_its_definition(made, all_on):
@@ -271,7 +322,8 @@ def test_all_on_at_64k_spans_every_consumer_equals_its_definition(made, all_on):
     # the chain ran on something: every class of event the file holds (tests/test_scan_all_refs_cpu.py pins the definitions' counts)
     vcf = all_on["chain"]["files"][".clips.vcf"]
     assert vcf.count(b"SVTYPE=DEL") >= 3 and vcf.count(b"SVTYPE=BND") >= 6 and vcf.count(b";MEI=") >= 3
-    assert all_on["snv_reserve"][2] > 64 and all_on["clip_reserve"][2] > 64
+    assert all_on["snv_reserve"][2] > 64 and all_on["clip_reserve"][2] > 64 and all_on["str_reserve"][2] > 64
+    assert len(all_on["str"][0]) > 0 and sum(1 for t in all_on["str"][3] if t[2] is not None) > 0       # (STR keys, and loci genotyped from them)
 
 
 def test_all_on_signal_rows_clips_and_bins_equal_a_host_ingest_scan_with_nothing_attached(made, all_on, monkeypatch):
@@ -346,7 +398,7 @@ def test_carried_batches_reach_every_consumer_and_are_gone_afterwards(made, all_
 
 def _tiny(monkeypatch, dup_class=None):
     """the six stores of the scan start with room for 64 items (the names as ``_scan`` looks them up)"""
-    from tiddit_amd import tiddit_clips, tiddit_dup, tiddit_indels, tiddit_region, tiddit_snvs
+    from tiddit_amd import tiddit_clips, tiddit_dup, tiddit_indels, tiddit_region, tiddit_snvs, tiddit_str
 
     def small(cls):
         class Tiny(cls):
@@ -357,6 +409,7 @@ def _tiny(monkeypatch, dup_class=None):
     monkeypatch.setattr(tiddit_indels, "IndelCounter", small(tiddit_indels.IndelCounter))
     monkeypatch.setattr(tiddit_region, "EvidenceStore", small(tiddit_region.EvidenceStore))
     monkeypatch.setattr(tiddit_snvs, "SnvCounter", small(tiddit_snvs.SnvCounter))
+    monkeypatch.setattr(tiddit_str, "StrCounter", small(tiddit_str.StrCounter))
 
     class TinyClips(small(tiddit_clips.ClipCounter)):
         def enable_ext(self, capacity=None):
@@ -369,7 +422,7 @@ def _grown(R):
     assert asks >= 1 and grows >= 1 and cap > 64, R["indel_reserve"]
     # (the dup store has no accessor for its capacity: it holds more keys than it had room for, and its kernel never writes past its room)
     assert len(R["dups"][0]) > 64 and R["store_capacity"] > 64
-    for name in ("snv_reserve", "clip_reserve"):
+    for name in ("snv_reserve", "clip_reserve", "str_reserve"):
         asks, grows, cap = R[name]
         assert asks >= 1 and grows >= 1 and cap > 64, (name, R[name])
     assert len(R["clips"][2]) > 64                                             # (the extension store has no accessor either)
@@ -385,15 +438,18 @@ def test_the_stores_grow_mid_scan(made, all_on, monkeypatch):
     assert all_on["indel_reserve"][1] == all_on["snv_reserve"][1] == all_on["clip_reserve"][1] == 0       # (the all-on run's stores were made large enough: nothing grew there)
 
 
-def test_host_ingest_with_the_three_keyed_consumers_together(made, all_on, monkeypatch):
-    """``TIDDIT_HOST_INGEST=1``: the host reader's batches through ``push_host_batch`` of the indel, the SNV and the clip counter, which
-    share one upload block per handle"""
+KEYED = ("indels", "snvs", "clips", "str")
+
+
+def test_host_ingest_with_the_four_keyed_consumers_together(made, all_on, monkeypatch):
+    """``TIDDIT_HOST_INGEST=1``: the host reader's batches through ``push_host_batch`` of the indel, the SNV, the clip and the STR counter,
+    which share one upload block per handle (the STR counter with a column more: ``end``)"""
     monkeypatch.setenv("TIDDIT_HOST_INGEST", "1")
-    H = _scan(made, ("indels", "snvs", "clips"))
+    H = _scan(made, KEYED)
     assert H["batches"] == 0 and H["records"] == 0                             # (no device batch)
-    assert [k for k in PARTS if k in H] == ["cov", "signals", "indels", "snvs", "clips"]
-    assert _differing(H, all_on, ("indels", "snvs", "clips")) == []
-    assert len(H["snvs"][0]) > 0 and len(H["clips"][0]) > 0 and len(H["clips"][2]) > 0
+    assert [k for k in PARTS if k in H] == ["cov", "signals"] + list(KEYED)
+    assert _differing(H, all_on, KEYED) == []
+    assert len(H["snvs"][0]) > 0 and len(H["clips"][0]) > 0 and len(H["clips"][2]) > 0 and len(H["str"][0]) > 0
 
 
 def test_an_allocation_refused_mid_scan_is_retried_behind_the_cache_flush(made, all_on, monkeypatch):
@@ -423,15 +479,18 @@ def test_an_allocation_refused_mid_scan_is_retried_behind_the_cache_flush(made, 
 
 # ---- part B: every switch in one job ----------------------------------------------------------------------------------------------
 ALL_SWITCHES = tuple(SWITCHES) + ("TIDDIT_INDELS_NORM", "TIDDIT_INGEST_CHUNK", "TIDDIT_NO_CARRY", "TIDDIT_SNVS", "TIDDIT_CLIPS", "TIDDIT_CLIPS_ALIGN",
-                                  "TIDDIT_CLIPS_FAR", "TIDDIT_CLIPS_INS", "TIDDIT_CLIPS_VCF", "TIDDIT_CLIPS_MEI", "TIDDIT_CLIPS_MEI_MIN")
-NOT_SCAN_SWITCHES = ()          # a switch of the package's docstring that the jobs need not strip would be named here; today there is none
+                                  "TIDDIT_CLIPS_FAR", "TIDDIT_CLIPS_INS", "TIDDIT_CLIPS_VCF", "TIDDIT_CLIPS_MEI", "TIDDIT_CLIPS_MEI_MIN", "TIDDIT_STR", "TIDDIT_STR_CUTS")
+NOT_SCAN_SWITCHES = ()          # a switch of the package's docstrings that the jobs need not strip would be named here; today there is none
 SUMMARIES = ("qc tables:", "duplicates:", "indels:", "indels, left-normalised:", "allele counts:", "note: TIDDIT_CNV skips", "note: TIDDIT_ASCN skips",
-             "snvs:", "clips:", "clips align:", "clips far:", "clips ins:", "clips mei:", "clips vcf:")
+             "snvs:", "clips:", "clips align:", "clips far:", "clips ins:", "clips mei:", "clips vcf:", "str:")
 # the files of each family (everything else is written by every job); .vcf and .genotyped.vcf carry one line that names the job's own prefix,
 # ``##TIDDITcmd=`` (the command line): they are compared without exactly that line
 OWNED = {"qc": (".qc.tab",), "dups": (".dup.tab",), "indels": (".indels.tab",), "acn": (".alleles.tab", ".cnv.bed", ".ascn.bed"), "track": (".bed",),
          "variants": (".vcf", ".depth_dist.tab", ".depth_summary.tab"), "genotype": (".genotyped.vcf",), "snvs": (".snvs.tab",),
-         "clips": (".clips.tab", ".clips.align.tab", ".clips.far.tab", ".clips.ins.tab", ".clips.mei.tab", ".clips.vcf")}
+         "clips": (".clips.tab", ".clips.align.tab", ".clips.far.tab", ".clips.ins.tab", ".clips.mei.tab", ".clips.vcf"),
+         "str": (".str.tab",)}
+STR_CUTS = "5:3:20"
+HOMOPOLYMER, DINUCLEOTIDE = 8, 5          # the catalogue of the fixture: every homopolymer run of 8 or more bases, every dinucleotide run of 5 or more units
 
 
 def _job(bam, fa, out, fx, timeout=600, **env):
@@ -452,6 +511,28 @@ def _write_sites(path, fa, contigs):
             for p in range(996, ln, 997):
                 ref = seq[p]
                 f.write("%s\t%d\t.\t%s\t%s\t.\t.\t.\n" % (name, p + 1, ref, "ACGT"[("ACGT".index(ref) + 1) % 4] if ref in "ACGT" else "A"))
+
+
+def _write_loci(path, fa, contigs):
+    """the STR catalogue of the fixture's own reference: every run of ``HOMOPOLYMER`` or more equal bases and every run of ``DINUCLEOTIDE``
+    or more units of two different bases, with both neighbour bases inside the contig, a run that touches the one in front left out
+    -> the number of rows"""
+    import re
+    from tiddit_amd.fasta import FastaFile
+    fasta = FastaFile(fa)
+    n = 0
+    with open(path, "w") as f:
+        for name, ln in contigs:
+            seq = fasta.fetch(name).upper()
+            runs = [(m.start(), m.end(), m.group(1)) for m in re.finditer(r"([ACGT])\1{%d,}" % (HOMOPOLYMER - 1), seq)]
+            runs += [(m.start(), m.end(), m.group(1)) for m in re.finditer(r"([ACGT]{2})\1{%d,}" % (DINUCLEOTIDE - 1), seq) if m.group(1)[0] != m.group(1)[1]]
+            last = 0
+            for s, e, unit in sorted(runs):
+                if s >= max(1, last + 1) and e <= ln - 1:
+                    f.write("%s\t%d\t%d\t%s\t%s_%d\n" % (name, s, e, unit, name, s))
+                    last = e
+                    n += 1
+    return n
 
 
 def _write_library(path, fa, contigs):
@@ -480,18 +561,21 @@ def jobs(golden_dir, tmp_path_factory):
     _write_sites(sites, fa, contigs)
     library = os.path.join(d, "families.fa")
     _write_library(library, fa, contigs)
+    loci = os.path.join(d, "loci.bed")
+    assert _write_loci(loci, fa, contigs) >= 1
     paths = {n: os.path.join(d, n) for n in tuple(OWNED) + ("all", "all4m")}
     family = {"qc": dict(TIDDIT_QC="1"), "dups": dict(TIDDIT_DUPS="1"), "indels": dict(TIDDIT_INDELS="1:20", TIDDIT_INDELS_NORM="1"),
               "acn": dict(TIDDIT_ALLELES=sites, TIDDIT_CNV="1", TIDDIT_ASCN="1"), "track": dict(TIDDIT_COV_TRACK="500"),
               "variants": dict(TIDDIT_VARIANTS="1", TIDDIT_DEPTH_DIST="1"), "snvs": dict(TIDDIT_SNVS="2"),
-              "clips": dict(TIDDIT_CLIPS="2", TIDDIT_CLIPS_ALIGN="1", TIDDIT_CLIPS_FAR="1", TIDDIT_CLIPS_INS="1", TIDDIT_CLIPS_VCF="1", TIDDIT_CLIPS_MEI=library)}
+              "clips": dict(TIDDIT_CLIPS="2", TIDDIT_CLIPS_ALIGN="1", TIDDIT_CLIPS_FAR="1", TIDDIT_CLIPS_INS="1", TIDDIT_CLIPS_VCF="1", TIDDIT_CLIPS_MEI=library),
+              "str": dict(TIDDIT_STR=loci, TIDDIT_STR_CUTS=STR_CUTS)}
     out = {}
     for name, env in family.items():
         out[name] = _ok(_job(bam, fa, paths[name], fx, **env))
     family["genotype"] = dict(TIDDIT_GENOTYPE=paths["variants"] + ".vcf")
     out["genotype"] = _ok(_job(bam, fa, paths["genotype"], fx, **family["genotype"]))
     every = {k: v for env in family.values() for k, v in env.items()}
-    assert len(every) == sum(len(env) for env in family.values()) == 18
+    assert len(every) == sum(len(env) for env in family.values()) == 20
     out["all"] = _ok(_job(bam, fa, paths["all"], fx, **every))
     out["all4m"] = _ok(_job(bam, fa, paths["all4m"], fx, TIDDIT_INGEST_CHUNK=str(4 << 20), **every))
     assert os.path.getsize(bam) > 5 * (4 << 20)                                # (the small-span job sees more than five spans)
@@ -534,13 +618,22 @@ def test_every_file_of_the_all_on_job_is_the_owning_jobs_file(jobs):
         assert len(_content(paths["all"] + ext)) > 50, ext
 
 
+def test_the_str_family_job_genotypes_loci_of_the_fixtures_own_repeats(jobs):
+    """(the catalogue at runs of 8 bases and 5 units: 272 loci of the fixture's reference, 271 of them genotyped by the definition)"""
+    paths, out = jobs
+    rows = [l.split("\t") for l in open(paths["str"] + ".str.tab").read().split("\n") if l and not l.startswith(("#", "SN\t"))]
+    assert len(rows) >= 1 and all(len(r) == 16 for r in rows)
+    assert sum(1 for r in rows if r[11] != ".") >= 1                            # GT: at least one locus with S or more spanning reads
+    assert open(paths["str"] + ".str.tab").read().startswith("# tiddit_amd str v1 flank=5 min_reads=3 min_mapq=20\n")
+
+
 def test_the_summary_lines_are_the_owning_jobs(jobs):
     paths, out = jobs
     want = [l for n in OWNED for l in _summaries(out[n])]
     got = _summaries(out["all"])
     assert sorted(got) == sorted(want) and len(got) >= 5
     assert {l.split(":")[0].split(",")[0] for l in got} >= {"qc tables", "duplicates", "indels", "allele counts", "snvs", "clips", "clips align", "clips far",
-                                                            "clips ins", "clips mei", "clips vcf"}
+                                                            "clips ins", "clips mei", "clips vcf", "str"}
 
 
 def test_the_all_on_job_at_4_mib_spans_writes_the_same_bytes(jobs):

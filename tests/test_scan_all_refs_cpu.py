@@ -1,9 +1,10 @@
 """The file of tests/scan_all_cases.py holds what it says it holds — so that tests/test_gpu_scan_all.py can never pass on an empty table —
 is the same bytes when made twice, and every consumer's definition over it is what the GPU tests need it to be: independent of where the
 host batches are cut, and changed by any one batch left out or fed twice.  The comparison helper of the GPU module names the part in
-which a result departs from its definition, and the GPU module's tables name every consumer switch of tiddit_signal and every switch of
-the package's docstring."""
+which a result departs from its definition, and the GPU module's tables name every consumer global the scan of tiddit_signal reads and
+every switch any docstring of the package's ``__main__`` names."""
 import ast
+import collections
 import copy
 import os
 import re
@@ -101,6 +102,47 @@ def test_alleles(made):
     assert int(((table[:, :4] > 0).sum(axis=1) >= 2).sum()) >= 300
 
 
+def test_str(made):
+    """(on the file as it stands: 496 loci, 4 210 keys — 2 881 span, 724 left, 605 right —, 48 unanchored, 252 over the cap of four, 4 222
+    reads in reach, 446 loci genotyped, 186 of them heterozygous, 18 flagged LONGER; every floor is half of that)"""
+    from tiddit_amd import tiddit_str as T
+    d, info, batches, parts, E = made
+    table = C.contigs()
+    loci = T.read_loci(C.str_path(d), [n for n, _ in table], [l for _, l in table])
+    assert loci.rows == C.str_loci().rows and len(loci) == len(C.grid_points()) >= 248 and not any(loci.skipped.values())
+    seqs = C.reference()[0]
+    for chrom, s, e, unit, _ in loci.rows:                                     # the catalogue's motif is in phase with the reference at start
+        assert seqs[chrom][s:e].tobytes().decode() == (unit * 16)[:e - s]
+    keys, counts, cols, tab = E["str"]
+    v = lambda k: int(counts[T.SN_INDEX[k]])
+    assert len(keys) == v("span_keys") + v("left_keys") + v("right_keys") >= 2105
+    assert v("span_keys") >= 1440 and v("left_keys") >= 362 and v("right_keys") >= 302 and v("unanchored") >= 24 and v("over_cap") >= 126
+    assert all(v(k) > 0 for k in ("span_keys", "left_keys", "right_keys", "unanchored", "over_cap"))
+    assert v("in_reach") >= 2111 and v("malformed") == 0 and v("records") == E["records"]
+    assert len(cols) == 4 and len(cols[0]) > 0 and int(cols[2].sum()) == len(keys) and int((cols[3] > 0).sum()) > 0
+    called = [t[2] for t in tab if t[2] is not None]
+    assert len(tab) == len(loci) and len(called) >= 223 and sum(1 for g in called if g[0] != g[2]) >= 93
+    assert sum(t[5] for t in tab) >= 9                                         # LONGER
+    assert sum(1 for p in parts if p["str_keys"]) >= len(parts) - 2            # (keys in nearly every batch)
+
+
+def test_str_equals_the_restatement_of_its_case_module(made):
+    """``str_cases.reference_batch`` over the same batches (it looks contigs up in its module's ``NAMES``: set to this file's for the call)"""
+    import str_cases as D
+    from tiddit_amd import tiddit_str as T
+    d, info, batches, parts, E = made
+    loci = [r[:4] for r in C.str_loci().rows]
+    keys, sn = [], collections.Counter()
+    names, D.NAMES = D.NAMES, tuple(n for n, _ in C.contigs())
+    try:
+        for b in batches:
+            D.reference_batch(b, loci, keys, sn, C.STR_F, C.STR_Q)
+    finally:
+        D.NAMES = names
+    assert len(keys) >= 2105
+    assert C._eq(C.str_result(keys, {k: n for k, n in sn.items() if n}), E["str"])
+
+
 def test_signals(made):
     import oracle
     from oracle import signal_oracle
@@ -174,8 +216,10 @@ def test_the_definitions_files_are_written_and_hold_the_chains_rows(made, tmp_pa
     d, info, batches, parts, E = made
     prefix = str(tmp_path / "want")
     C.write_definition_files(prefix, parts, E, C.library_path(d))
-    for ext in C.STAGE_FILES:
+    for ext in C.STAGE_FILES + (C.STR_FILE,):
         assert os.path.getsize(prefix + ext) > 500, ext
+    body = [l.split("\t") for l in open(prefix + C.STR_FILE).read().split("\n") if l and not l.startswith(("#", "SN\t"))]
+    assert len(body) == len(E["str"][3]) and sum(1 for f in body if f[11] != ".") == sum(1 for t in E["str"][3] if t[2] is not None)
     body = [l for l in open(prefix + ".clips.vcf").read().split("\n") if l and not l.startswith("#")]
     assert body == E["clip_chain"]["vcf"][1]
     for ext, stage in ((".clips.align.tab", "align"), (".clips.far.tab", "far"), (".clips.ins.tab", "ins"), (".clips.mei.tab", "mei")):
@@ -186,7 +230,7 @@ def test_the_definitions_files_are_written_and_hold_the_chains_rows(made, tmp_pa
 def test_the_file_is_the_same_bytes_when_made_twice(made, tmp_path):
     d = made[0]
     C.generate(str(tmp_path), threads=2)
-    for a, b in zip(C.paths(d) + (C.library_path(d),), C.paths(str(tmp_path)) + (C.library_path(str(tmp_path)),)):
+    for a, b in zip(C.paths(d) + (C.library_path(d), C.str_path(d)), C.paths(str(tmp_path)) + (C.library_path(str(tmp_path)), C.str_path(str(tmp_path)))):
         assert open(a, "rb").read() == open(b, "rb").read(), os.path.basename(a)
 
 
@@ -215,7 +259,7 @@ def right(made, tmp_path_factory):
     d, info, batches, parts, E = made
     prefix = os.path.join(str(tmp_path_factory.mktemp("scan_all_files")), "want")
     C.write_definition_files(prefix, parts, E, C.library_path(d))
-    files = {ext: G._content(prefix + ext) for ext in C.STAGE_FILES}
+    files = {ext: G._content(prefix + ext) for ext in C.STAGE_FILES + (C.STR_FILE,)}
     return G, E, files
 
 
@@ -258,9 +302,27 @@ def _one_boundary_support_off_by_one(R):
     R["chain"]["files"][".clips.vcf"] = b"\n".join(lines)
 
 
+def _one_str_key_dropped(R):
+    R["str"] = (R["str"][0][1:],) + R["str"][1:]
+
+
+def _one_str_row_support_off(R):
+    R["str"][2][2][0] += 1
+
+
+def _one_str_file_line_changed(R):
+    lines = R["str"][4].split(b"\n")
+    i = next(i for i, l in enumerate(lines) if l and not l.startswith((b"#", b"SN\t")) and l.split(b"\t")[11] == b"0/1")
+    f = lines[i].split(b"\t")
+    f[11] = b"1/1"
+    lines[i] = b"\t".join(f)
+    R["str"] = R["str"][:4] + (b"\n".join(lines),)
+
+
 DEPARTURES = ((_one_snv_key_dropped, "snvs: the keys"), (_one_snv_row_support_off, "snvs: row column 2"), (_one_clip_consensus_changed, "clips: row column 6"),
               (_one_extension_key_changed, "clips: the extension keys"), (_one_align_partner_moved, "chain: column 5 of the align rows"),
-              (_one_mei_family_changed, "chain: column 6 of the mei rows"), (_one_boundary_support_off_by_one, "chain: the file .clips.vcf"))
+              (_one_mei_family_changed, "chain: column 6 of the mei rows"), (_one_boundary_support_off_by_one, "chain: the file .clips.vcf"),
+              (_one_str_key_dropped, "str: the keys"), (_one_str_row_support_off, "str: row column 2"), (_one_str_file_line_changed, "str: the file .str.tab"))
 
 
 def test_the_comparison_passes_on_the_definitions_and_names_each_departure(right):
@@ -273,12 +335,35 @@ def test_the_comparison_passes_on_the_definitions_and_names_each_departure(right
         with pytest.raises(AssertionError) as e:
             G._equals_definitions(R, E, files)
         assert str(e.value).startswith(named), (depart.__name__, str(e.value)[:200])
-        assert G._differing(R, G._as_run(E, files), ("snvs", "clips", "chain")) == [named.split(":")[0]]
+        assert G._differing(R, G._as_run(E, files), ("snvs", "clips", "chain", "str")) == [named.split(":")[0]]
         noticed += 1
-    assert noticed == len(DEPARTURES) == 7                                     # departures, each noticed and named
+    assert noticed == len(DEPARTURES) == 10                                    # departures, each noticed and named
 
 
-NOT_CONSUMERS = ("AFTER_SCAN", "BACKGROUND_WRITES", "COV_TRACK_BINS", "STAGE_SECONDS", "WRITE_SECONDS")      # what __main__ sets or reads in tiddit_signal that attaches nothing
+# the all-capitals globals of tiddit_signal that __main__ sets or the scan reads and that attach nothing: timings, seams, the track's result
+NOT_CONSUMERS = ("AFTER_SCAN", "BACKGROUND_WRITES", "COV_TRACK_BINS", "STAGE_SECONDS", "WRITE_SECONDS", "LAST_SEAM", "READER_SECONDS", "SCAN_SECONDS")
+
+
+def scan_globals(source):
+    """the module-level all-capitals names of tiddit_signal's source that ``_scan`` or a module function it calls (at any depth) reads or
+    sets: what a scan can be steered by or leave behind, however ``__main__`` or anybody else attaches it"""
+    tree = ast.parse(source)
+    top = {t.id for n in tree.body if isinstance(n, (ast.Assign, ast.AnnAssign)) for t in (n.targets if isinstance(n, ast.Assign) else [n.target])
+           if isinstance(t, ast.Name) and re.fullmatch(r"[A-Z][A-Z0-9_]*", t.id)}
+    functions = {n.name: n for n in tree.body if isinstance(n, ast.FunctionDef)}
+    seen, todo, names = set(), ["_scan"], set()
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.add(f)
+        for n in ast.walk(functions[f]):
+            if isinstance(n, ast.Name):
+                names |= {n.id} & top
+                todo += [n.id] if n.id in functions else []
+            elif isinstance(n, ast.Global):
+                names |= set(n.names) & top
+    return names
 
 
 def test_every_consumer_switch_and_counter_of_the_scan_is_driven_by_the_attachable_table():
@@ -287,21 +372,28 @@ def test_every_consumer_switch_and_counter_of_the_scan_is_driven_by_the_attachab
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     source = open(os.path.join(repo, "tiddit_amd", "__main__.py")).read()
     counters = {n for n in vars(S) if n.endswith("_COUNTER")}
-    switches = set(re.findall(r"tiddit_signal\.([A-Z][A-Z_]*)\b", source)) - set(NOT_CONSUMERS) - counters
+    # from tiddit_signal itself — a consumer counts however it is attached (tiddit_str.attach sets STR from its own module) — and, as
+    # before, what __main__ names
+    in_scan = scan_globals(open(os.path.join(repo, "tiddit_amd", "tiddit_signal.py")).read())
+    assert counters <= in_scan <= set(vars(S))
+    switches = (in_scan | set(re.findall(r"tiddit_signal\.([A-Z][A-Z_]*)\b", source))) - set(NOT_CONSUMERS) - counters
     assert counters >= {"ALLELE_COUNTER", "QC_COUNTER", "DUP_COUNTER", "INDEL_COUNTER", "SNV_COUNTER", "CLIP_COUNTER"}
     assert switches >= {"COV_TRACK", "KEEP_EVIDENCE", "ALLELES", "QC", "DUPS", "INDELS", "SNVS", "CLIPS", "CLIPS_INS"}
     driven = [n for names in G.DRIVES.values() for n in names]
     assert len(driven) == len(set(driven)) and tuple(G.DRIVES) == G.ATTACHABLE
     assert counters | switches == set(driven), sorted((counters | switches) ^ set(driven))
-    assert all(hasattr(S, n) for n in driven)
+    assert all(hasattr(S, n) for n in driven) and set(driven) <= in_scan         # (whatever the table drives, the scan itself reads or sets)
     assert all(getattr(S, n) is G.OFF.get(n) for n in driven)                  # (and every one of them is off as the module is imported)
 
 
 def test_every_switch_the_package_names_is_stripped_from_the_jobs_environment():
     import test_gpu_scan_all as G
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    doc = ast.get_docstring(ast.parse(open(os.path.join(repo, "tiddit_amd", "__main__.py")).read()))
-    named = set(re.findall(r"TIDDIT_[A-Z0-9_]*[A-Z0-9]", doc))
+    tree = ast.parse(open(os.path.join(repo, "tiddit_amd", "__main__.py")).read())
+    # every docstring of the file, not the module's alone: a switch documented at the function that reads it counts as much
+    docs = [ast.get_docstring(n) for n in ast.walk(tree) if isinstance(n, (ast.Module, ast.FunctionDef, ast.AsyncFunctionDef, ast.ClassDef))]
+    named = set(re.findall(r"TIDDIT_[A-Z0-9_]*[A-Z0-9]", "\n".join(d for d in docs if d)))
+    assert len(docs) >= 2 and {"TIDDIT_STR", "TIDDIT_STR_CUTS"} <= named
     assert len(named) >= 19 and {"TIDDIT_SNVS", "TIDDIT_CLIPS", "TIDDIT_CLIPS_ALIGN", "TIDDIT_CLIPS_FAR", "TIDDIT_CLIPS_INS", "TIDDIT_CLIPS_VCF", "TIDDIT_CLIPS_MEI"} <= named
     assert len(G.NOT_SCAN_SWITCHES) <= 4 and not set(G.NOT_SCAN_SWITCHES) & set(G.ALL_SWITCHES)
     left = named - set(G.ALL_SWITCHES) - set(G.NOT_SCAN_SWITCHES)
