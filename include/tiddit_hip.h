@@ -669,6 +669,42 @@ int tdt_alleles_push(tdt_alleles *h, const int32_t *tid, const int32_t *pos, con
 int tdt_alleles_counts(tdt_alleles *h, uint32_t *out, uint64_t *reads_used, uint64_t *malformed);
 int tdt_alleles_counts_device(tdt_alleles *h, uint32_t *d_out, uint64_t *d_stat2);
 
+/* ---- read-backed phasing of the known SNV sites (TIDDIT_PHASE) ------------------------------------------ *
+ * No counterpart in the reference; the definition is tiddit_amd/tiddit_phase.py's.  tdt_alleles_phase_enable gives an allele handle a
+ * store of observation keys beside its counters: every push of the handle then costs one more launch (phase_keys) on the batch it has
+ * just counted.  site_codes = one byte per device site, ref2 | alt2 << 2 (A C G T = 0 1 2 3) or 0xff for a site that is not phaseable;
+ * a read's first TDT_PHASE_MAX_OBS observations give the keys K1 = FNV-1a-64(read name) & (2^hash_bits - 1), K2 = site << 1 | allele.
+ * Enabled twice, behind a push, or with n_sites that is not the handle's: TDT_E_ARG; hash_bits outside 1 ... 64, min_q outside 0 ... 255:
+ * TDT_E_RANGE.  tdt_alleles_reset empties the store too.
+ * tdt_alleles_phase_finish(het_flags: HOST, one byte per site; min_link = S): the fragment rows, the links between consecutive clean
+ * heterozygous rows of a fragment, the link rows (N, TRANS) in (j, i) order, the maximum spanning forest of the eligible links, the check
+ * of the others.  got[TDT_PHASE_GOT_N] = malformed reads_used observations capped_reads | fragment_rows discordant_rows
+ * cross_contig_pairs links weak_links forest_edges agree conflict phased_sites blocks | the Boruvka rounds run.  The stores are left as
+ * they were.  The read-outs give the last finish: per site (root = the block's lowest site or -1, phase), the blocks (first site, last
+ * site, sites, eligible links, agree, conflict; ascending), the link rows with their forest flag; a push or reset since: TDT_E_ARG; too
+ * little room (*n in = room, out = count; all-NULL arrays ask for the count alone): TDT_E_RANGE, nothing written.  Every entry without
+ * tdt_alleles_phase_enable: TDT_E_ARG.
+ * tdt_phase_forest: the graph stage alone on ANY link rows (j, i, N, TRANS; row = the index) over n_sites sites: root int32[n_sites],
+ * phase uint8[n_sites], edge_used uint8[n_links], agree / conflict uint32[n_sites] at each block's lowest site.  An end outside
+ * [0, n_sites), two equal ends or TRANS > N: TDT_E_ARG; 2^31 sites or links or more, min_link outside 1 ... 2^31 - 1: TDT_E_RANGE. */
+#define TDT_PHASE_MAX_OBS 8
+#define TDT_PHASE_PUSH_N 4
+#define TDT_PHASE_GOT_N 15
+int tdt_alleles_phase_enable(tdt_alleles *h, const uint8_t *site_codes, size_t n_sites, size_t capacity, int hash_bits);
+int tdt_alleles_phase_keys(tdt_alleles *h, uint64_t *k1, uint64_t *k2, size_t *n);
+int tdt_alleles_phase_finish(tdt_alleles *h, const uint8_t *het_flags, uint64_t min_link, uint64_t *got);
+int tdt_alleles_phase_sites(tdt_alleles *h, int32_t *root, uint8_t *phase, size_t n);
+int tdt_alleles_phase_blocks(tdt_alleles *h, int32_t *start, int32_t *end, uint32_t *sites, uint32_t *edges, uint32_t *agree, uint32_t *conflict,
+                             size_t *n);
+int tdt_alleles_phase_links(tdt_alleles *h, uint32_t *j, uint32_t *i, uint32_t *n_, uint32_t *trans, uint8_t *edge_used, size_t *n);
+int tdt_alleles_phase_timing(tdt_alleles *h, double *ms5);
+int tdt_alleles_phase_reserve_stats(tdt_alleles *h, uint64_t *out3);
+int tdt_phase_forest(tdt_ctx *ctx, const int32_t *j, const int32_t *i, const uint32_t *n, const uint32_t *trans, size_t n_links, size_t n_sites,
+                     uint64_t min_link, int32_t *root, uint8_t *phase, uint8_t *edge_used, uint32_t *agree, uint32_t *conflict);
+int tdt_phase_forest_device(tdt_ctx *ctx, const int32_t *d_j, const int32_t *d_i, const uint32_t *d_n, const uint32_t *d_trans, size_t n_links,
+                            size_t n_sites, uint64_t min_link, int32_t *d_root, uint8_t *d_phase, uint8_t *d_edge_used, uint32_t *d_agree,
+                            uint32_t *d_conflict);
+
 /* ---- read-level QC tables (TIDDIT_QC) ------------------------------------------------------------------ *
  * No counterpart in the reference (its users run `samtools flagstat` / `samtools stats`, one more pass over the file); the definition
  * is tiddit_amd/tiddit_qc.py's.  A handle keeps ONE array of TDT_QC_TOTAL zeroed uint64 counters in HBM, in sections (row-major):

@@ -341,6 +341,15 @@ def run_sv(args, version):
         print("error, TIDDIT_ASCN={}: {}".format(os.environ.get("TIDDIT_ASCN"), e))
         sys.exit(1)
     try:
+        # TIDDIT_PHASE=1 | S | S:H, only together with TIDDIT_ALLELES: read-backed phasing of the heterozygous sites of the sites file
+        # ({o}.phase.tab, {o}.phase.blocks.tab; tiddit_phase.py is the specification and documents the switch)
+        from . import tiddit_phase
+        phase = tiddit_phase.parse_switch(os.environ.get("TIDDIT_PHASE"), alleles is not None)
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_PHASE={}: {}".format(os.environ.get("TIDDIT_PHASE"), e))
+        sys.exit(1)
+    try:
         from . import tiddit_qc
         qc = tiddit_qc.parse_switch(os.environ.get("TIDDIT_QC"))
     except ValueError as e:
@@ -521,6 +530,11 @@ def run_sv(args, version):
         print("error, TIDDIT_DUPS is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
               "keys on another rank")
         sys.exit(1)
+    if multi and phase is not None:
+        # (the same: a fragment's two mates can lie on two shards, and its link would be lost.  TIDDIT_ALLELES alone stays allowed)
+        print("error, TIDDIT_PHASE is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
+              "keys on another rank")
+        sys.exit(1)
     if multi and indels is not None:
         # (the same: an event's support is spread over the shards, and merging per-rank rows needs an exchange of keys)
         print("error, TIDDIT_INDELS is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
@@ -690,6 +704,14 @@ def run_sv(args, version):
     if allele_sites is not None:
         # TIDDIT_ALLELES: ... and counts the reads' bases at the sites, one launch per batch
         tiddit_signal.ALLELES = (allele_sites.site_pos, allele_sites.site_off, alleles[1])
+        if phase is not None:
+            # TIDDIT_PHASE: ... and stores a key per (read, phaseable site it shows REF or ALT at), one more launch per batch inside that push
+            # (the indel counter's capacity rule; more than 2^31 - 1 sites are refused here, before the scan)
+            try:
+                tiddit_signal.ALLELES += ((tiddit_phase.site_codes(allele_sites), min(max(os.path.getsize(args.bam) // 16, 1 << 16), 1 << 26), 64) + phase,)
+            except ValueError as e:
+                print("error, TIDDIT_PHASE={}: {}".format(os.environ.get("TIDDIT_PHASE"), e))
+                sys.exit(1)
     if qc:
         # TIDDIT_QC: ... and fills the read-level QC tables, two launches per batch
         tiddit_signal.QC = True
@@ -769,6 +791,13 @@ def run_sv(args, version):
         allele_table = tiddit_alleles.main(counter, allele_sites, prefix, multi=multi, rank=rank)
         T["allele counts ({o}.alleles.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_alleles.STAGE_SECONDS.items()})
+        if phase is not None:
+            # TIDDIT_PHASE: the finish of the observation store the counter carries, the two files, one summary line
+            t = time.time()
+            tiddit_phase.main(counter, allele_sites, allele_table, prefix, names=chromosomes)
+            T["phase sets ({o}.phase.tab, {o}.phase.blocks.tab)"] = time.time() - t
+            T.update({"  " + k: v for k, v in tiddit_phase.STAGE_SECONDS.items()})
+            STAGE_NOTES.update(tiddit_phase.STAGE_NOTES)
     if qc:
         counter, tiddit_signal.QC_COUNTER = tiddit_signal.QC_COUNTER, None
         t = time.time()

@@ -142,6 +142,16 @@ SYMBOLS = {
     "tdt_alleles_push": (_i, [_P] * 7 + [_sz, _P, _sz]),
     "tdt_alleles_counts": (_i, [_P, _P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "tdt_alleles_counts_device": (_i, [_P, _P, _P]),
+    "tdt_alleles_phase_enable": (_i, [_P, _P, _sz, _sz, _i]),
+    "tdt_alleles_phase_keys": (_i, [_P, _P, _P, ctypes.POINTER(_sz)]),
+    "tdt_alleles_phase_finish": (_i, [_P, _P, ctypes.c_uint64, _P]),
+    "tdt_alleles_phase_sites": (_i, [_P, _P, _P, _sz]),
+    "tdt_alleles_phase_blocks": (_i, [_P] * 7 + [ctypes.POINTER(_sz)]),
+    "tdt_alleles_phase_links": (_i, [_P] * 6 + [ctypes.POINTER(_sz)]),
+    "tdt_alleles_phase_timing": (_i, [_P, _P]),
+    "tdt_alleles_phase_reserve_stats": (_i, [_P, _P]),
+    "tdt_phase_forest": (_i, [_P] * 5 + [_sz, _sz, ctypes.c_uint64] + [_P] * 5),
+    "tdt_phase_forest_device": (_i, [_P] * 5 + [_sz, _sz, ctypes.c_uint64] + [_P] * 5),
     "tdt_qc_create": (_i, [_P, _PP]),
     "tdt_qc_destroy": (_i, [_P]),
     "tdt_qc_reset": (_i, [_P]),

@@ -16,6 +16,7 @@
 // Every counter is an order-independent integer sum: the result equals the per-read definition exactly.
 #include "tdt_batch.h"
 #include "tdt_bam_record.h"
+#include "tdt_phase.h"
 
 typedef unsigned long long ull;
 
@@ -33,6 +34,8 @@ struct tdt_alleles {
     unsigned *d_cnt;                          // ns * 8
     ull *d_stat;                              // {reads used, malformed}
     tdt_batch_io io;                          // columns + raw bytes of the host entry
+    tdt_phase *phase;                         // TIDDIT_PHASE: made by tdt_alleles_phase_enable (csrc/tdt_phase.hip), else NULL
+    bool pushed;                              // a batch has been pushed since the create or the last reset
 };
 
 struct AlIn {
@@ -185,6 +188,7 @@ __global__ __launch_bounds__(AL_BLOCK) void al_count(AlIn I, int n, ull raw_len,
 }
 
 static void al_free(tdt_alleles *h) {
+    if (h->phase) tdt_phase_free(h->phase);
     if (h->d_pos) (void)hipFree(h->d_pos);
     if (h->d_off) (void)hipFree(h->d_off);
     if (h->d_cnt) (void)hipFree(h->d_cnt);
@@ -228,7 +232,7 @@ extern "C" int tdt_alleles_create(tdt_ctx *ctx, const int32_t *site_pos, const i
         }
     }
     TDT_HIP(hipSetDevice(ctx->device));
-    tdt_alleles *h = new tdt_alleles{ctx, n_contigs, min_q, min_bq, ns, nullptr, nullptr, nullptr, nullptr, {nullptr, 0}};
+    tdt_alleles *h = new tdt_alleles{ctx, n_contigs, min_q, min_bq, ns, nullptr, nullptr, nullptr, nullptr, {nullptr, 0}, nullptr, false};
     const size_t N = ns ? ns : 1;
     if (tdt_dev_malloc((void **)&h->d_pos, N * 4) != hipSuccess || tdt_dev_malloc((void **)&h->d_off, (size_t)(n_contigs + 1) * 8) != hipSuccess ||
         tdt_dev_malloc((void **)&h->d_cnt, N * AL_COLS * 4) != hipSuccess || tdt_dev_malloc((void **)&h->d_stat, 256) != hipSuccess) {
@@ -270,7 +274,8 @@ extern "C" int tdt_alleles_reset(tdt_alleles *h) {
     TDT_HIP(hipSetDevice(h->ctx->device));
     TDT_HIP(hipMemsetAsync(h->d_cnt, 0, (h->ns ? h->ns : 1) * AL_COLS * 4, h->ctx->stream));
     TDT_HIP(hipMemsetAsync(h->d_stat, 0, 256, h->ctx->stream));
-    return TDT_OK;
+    h->pushed = false;
+    return h->phase ? tdt_phase_reset(h->phase) : TDT_OK;
 }
 
 static int al_launch(tdt_alleles *h, const AlIn &I, size_t n, size_t raw_len) {
@@ -290,7 +295,9 @@ extern "C" int tdt_alleles_push_device(tdt_alleles *h, const void *const *d_arra
     if (rc) return rc;
     if (n == 0 || h->ns == 0) return TDT_OK;
     TDT_HIP(hipSetDevice(h->ctx->device));
-    return al_launch(h, AlIn{B.tid, B.pos, B.end, B.mapq, B.flag, B.rec_off, B.raw}, n, raw_len);
+    h->pushed = true;
+    const int rc2 = al_launch(h, AlIn{B.tid, B.pos, B.end, B.mapq, B.flag, B.rec_off, B.raw}, n, raw_len);
+    return rc2 == TDT_OK && h->phase ? tdt_phase_push(h->phase, B, n, raw_len) : rc2;
 }
 
 // The same kernel on host columns and host record bytes (uploaded into the handle's own block).  The stream is synchronised before the
@@ -305,8 +312,10 @@ extern "C" int tdt_alleles_push(tdt_alleles *h, const int32_t *tid, const int32_
     // al_count bounds every record by itself)
     if (n == 0 || h->ns == 0) return TDT_OK;
     TDT_HIP(hipSetDevice(h->ctx->device));
+    h->pushed = true;
     rc = tdt_batch_upload("tdt_alleles_push", h->ctx, &h->io, H, AL_NEED, n, raw_len, &B);
     if (rc == TDT_OK) rc = al_launch(h, AlIn{B.tid, B.pos, B.end, B.mapq, B.flag, B.rec_off, B.raw}, n, raw_len);
+    if (rc == TDT_OK && h->phase) rc = tdt_phase_push(h->phase, B, n, raw_len);
     if (rc) return rc;
     TDT_HIP(hipStreamSynchronize(h->ctx->stream));
     return TDT_OK;
@@ -342,4 +351,18 @@ extern "C" int tdt_alleles_counts_device(tdt_alleles *h, uint32_t *d_out, uint64
     if (d_stat2) TDT_HIP(hipMemcpyAsync(d_stat2, h->d_stat, 16, hipMemcpyDeviceToDevice, st));
     TDT_HIP(hipStreamSynchronize(st));
     return TDT_OK;
+}
+
+// ---- TIDDIT_PHASE: the observation store beside the counters (csrc/tdt_phase.hip).  site_codes = one byte per device site, ref2 | alt2 << 2
+// or 0xff for a site that is not phaseable.  Before the first push only (the store and the counters hold the same reads); a second
+// call, a call behind a push, or n_sites that is not the handle's: TDT_E_ARG.
+tdt_phase *tdt_alleles_phase_of(tdt_alleles *h) { return h ? h->phase : nullptr; }
+
+extern "C" int tdt_alleles_phase_enable(tdt_alleles *h, const uint8_t *site_codes, size_t n_sites, size_t capacity, int hash_bits) {
+    if (!h || h->phase || h->pushed || n_sites != h->ns || (n_sites && !site_codes)) {
+        tdt_set_error("tdt_alleles_phase_enable: bad argument, enabled already, pushed to already, or not the handle's %zu sites", h ? h->ns : (size_t)0);
+        return TDT_E_ARG;
+    }
+    TDT_HIP(hipSetDevice(h->ctx->device));
+    return tdt_phase_create(h->ctx, h->d_pos, h->d_off, h->ns, h->n_contigs, h->min_q, h->min_bq, site_codes, capacity, hash_bits, &h->phase);
 }

@@ -136,38 +136,40 @@ def read_sites(path, names, lengths):
 
 
 # ------------------------------------------------------------------------------------------- the definition
-def count_read(table, stats, site_pos, site_off, tid, pos, end, mapq, flag, rec_off, raw, min_q, min_bq):
-    """THE DEFINITION, one read: adds to ``table`` (uint32-like [sites][8]) and to ``stats`` = [reads_used, malformed].  ``raw`` is the
-    batch's record bytes (bytes-like), the other arguments the read's entries of the batch's columns."""
+MALFORMED = "malformed"
+
+
+def walk_read(site_pos, site_off, tid, pos, end, mapq, flag, rec_off, raw, min_q):
+    """the gate, the well-formedness test and the CIGAR walk of THE DEFINITION, one read (tiddit_phase imports them from here):
+    -> None (not a read that counts), :data:`MALFORMED`, or ``(name offset in raw, l_read_name, touches)`` with one
+    ``(site index, op, nibble, quality byte)`` per site of the read an operation touches, in walk order — op 0 for ``M = X`` (nibble
+    and quality are the base's), 2 for ``D``, 3 for ``N`` (both None)."""
     n_contigs = len(site_off) - 1
     if not (0 <= tid < n_contigs) or (flag & FLAG_MASK) or mapq < min_q:
-        return
+        return None
     o0, o1 = int(site_off[tid]), int(site_off[tid + 1])
     mine = range(bisect.bisect_left(site_pos, pos, o0, o1), bisect.bisect_left(site_pos, end, o0, o1))     # the sites in [pos, end)
     if not mine:
-        return
+        return None
     raw_len = len(raw)
     if rec_off + 36 > raw_len:
-        stats[1] += 1
-        return
+        return MALFORMED
     block_size, = struct.unpack_from("<I", raw, rec_off)
     r0 = rec_off + 4
     l_name = raw[r0 + 8]
     n_cig, = struct.unpack_from("<H", raw, r0 + 12)
     l_seq, = struct.unpack_from("<i", raw, r0 + 16)
     if n_cig == 0 or l_seq < 1:
-        return
+        return None
     if 32 + l_name + 4 * n_cig + (l_seq + 1) // 2 + l_seq > block_size or rec_off + 4 + block_size > raw_len:
-        stats[1] += 1
-        return
+        return MALFORMED
     cig = r0 + 32 + l_name
     seq = cig + 4 * n_cig
     qual = seq + (l_seq + 1) // 2
     ops = [struct.unpack_from("<I", raw, cig + 4 * j)[0] for j in range(n_cig)]
     if any((w & 0xf) > 8 for w in ops):
-        stats[1] += 1
-        return
-    adds = []
+        return MALFORMED
+    touches = []
     for k in mine:
         s = int(site_pos[k])
         r, q = pos, 0
@@ -177,23 +179,32 @@ def count_read(table, stats, site_pos, site_off, tid, pos, end, mapq, flag, rec_
                 if r <= s < r + ln:
                     qi = q + s - r
                     if qi >= l_seq:
-                        stats[1] += 1
-                        return
+                        return MALFORMED
                     byte = raw[seq + (qi >> 1)]
-                    nib = (byte & 0xf) if qi & 1 else (byte >> 4)
-                    ql = raw[qual + qi]
-                    adds.append((k, LOWBQ if ql != 0xff and ql < min_bq else _NIBBLE.get(nib, N)))
+                    touches.append((k, 0, (byte & 0xf) if qi & 1 else (byte >> 4), raw[qual + qi]))
                 r += ln
                 q += ln
             elif op == 2 or op == 3:
                 if r <= s < r + ln:
-                    adds.append((k, DEL if op == 2 else SKIP))
+                    touches.append((k, op, None, None))
                 r += ln
             elif op == 1 or op == 4:
                 q += ln
+    return r0 + 32, l_name, touches
+
+
+def count_read(table, stats, site_pos, site_off, tid, pos, end, mapq, flag, rec_off, raw, min_q, min_bq):
+    """THE DEFINITION, one read: adds to ``table`` (uint32-like [sites][8]) and to ``stats`` = [reads_used, malformed].  ``raw`` is the
+    batch's record bytes (bytes-like), the other arguments the read's entries of the batch's columns."""
+    got = walk_read(site_pos, site_off, tid, pos, end, mapq, flag, rec_off, raw, min_q)
+    if got is None:
+        return
+    if got is MALFORMED:
+        stats[1] += 1
+        return
     stats[0] += 1
-    for k, col in adds:
-        table[k][col] += 1
+    for k, op, nib, ql in got[2]:
+        table[k][DEL if op == 2 else SKIP if op == 3 else LOWBQ if ql != 0xff and ql < min_bq else _NIBBLE.get(nib, N)] += 1
 
 
 def count_batch(table, stats, site_pos, site_off, b, min_q, min_bq, only=None):
@@ -210,15 +221,24 @@ def count_batch(table, stats, site_pos, site_off, b, min_q, min_bq, only=None):
 class AlleleCounter:
     """``tdt_alleles_*``: the sites and their counters in HBM; one push per batch of the scan."""
 
-    def __init__(self, site_pos, site_off, min_q, min_bq, ctx=None):
+    def __init__(self, site_pos, site_off, min_q, min_bq, ctx=None, phase=None):
         self.ctx = ctx or _native.default_context()
         self.site_pos = numpy.ascontiguousarray(site_pos, dtype=numpy.int32)
         self.site_off = numpy.ascontiguousarray(site_off, dtype=numpy.int64)
         self.n_sites = len(self.site_pos)
+        self.min_bq = int(min_bq)
         h = ctypes.c_void_p()
         _native.check(self.ctx.lib.tdt_alleles_create(self.ctx.handle, _native.ptr(self.site_pos), _native.ptr(self.site_off),
                                                       len(self.site_off) - 1, int(min_q), int(min_bq), ctypes.byref(h)))
         self.handle = h
+        self.phase = phase                     # TIDDIT_PHASE: (site_codes uint8[sites], capacity, hash_bits[, S, H]) — the observation store beside the counters (tiddit_phase)
+        if phase is not None:
+            codes = numpy.ascontiguousarray(phase[0], dtype=numpy.uint8)
+            try:
+                _native.check(self.ctx.lib.tdt_alleles_phase_enable(h, _native.ptr(codes), len(codes), int(phase[1]), int(phase[2])))
+            except Exception:
+                self.close()
+                raise
 
     def push_device_batch(self, b):
         """one DeviceBatch: enqueued on the reader's stream, nothing waited for (call before the batch's buffers are handed on)"""
@@ -296,7 +316,8 @@ def main(counter, sites, prefix, multi=False, rank=0):
     STAGE_SECONDS.clear()
     t = time.time()
     table, used, bad = counter.counts()
-    counter.close()
+    if counter.phase is None:                              # (TIDDIT_PHASE: tiddit_phase.main runs the store's finish behind this stage and closes it)
+        counter.close()
     STAGE_SECONDS["allele counters to the host"] = time.time() - t
     if multi:
         t = time.time()

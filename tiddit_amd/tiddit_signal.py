@@ -365,7 +365,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
     if ALLELES is not None:
         # TIDDIT_ALLELES: the sites and their counters in HBM; every batch costs one more launch on the bytes it already holds there
         from . import tiddit_alleles
-        alleles = tiddit_alleles.AlleleCounter(ALLELES[0], ALLELES[1], min_q, ALLELES[2], ctx=getattr(reader, "ctx", None))
+        # (a fourth element: TIDDIT_PHASE's (site codes, capacity, hash_bits, S, H) — the observation store beside the counters, one more
+        #  launch per batch inside the same push; room for 8 keys per read is reserved before each launch, behind which a reserve asks
+        #  the device for the real count)
+        alleles = tiddit_alleles.AlleleCounter(ALLELES[0], ALLELES[1], min_q, ALLELES[2], ctx=getattr(reader, "ctx", None),
+                                               phase=ALLELES[3] if len(ALLELES) > 3 else None)
         T["allele counts (push)"] = 0.0
     qc = None
     if QC:
@@ -715,7 +719,7 @@ LAST_SEAM = {}              # seam offsets of the last sharded scan pass (dist.c
 COV_TRACK = None            # (bin_size, min_q): the scan also fills a second histogram over every contig — the coverage `tiddit --cov -z -q` computes —
                             # from the same batches; None (the default): the scan does what it does without it
 COV_TRACK_BINS = None       # {contig: float64 bins} of that histogram after the last scan that had COV_TRACK set (on N ranks: the reduced bins), else None
-ALLELES = None              # (site_pos, site_off, min_bq): the scan also counts the reads' bases at these sites (tiddit_alleles.AlleleCounter), one launch per batch
+ALLELES = None              # (site_pos, site_off, min_bq[, phase_opts]): the scan also counts the reads' bases at these sites (tiddit_alleles.AlleleCounter), one launch per batch
 ALLELE_COUNTER = None       # that counter after the last scan that had ALLELES set (the caller reads and closes it), else None
 QC = None                   # True: the scan also fills the read-level QC tables (tiddit_qc.QcCounter), two launches per batch
 QC_COUNTER = None           # that counter after the last scan that had QC set (the caller reads and closes it), else None
