@@ -1168,6 +1168,44 @@ int tdt_clip_mei_rows(tdt_clip *h, uint32_t *pair, uint32_t *part, uint32_t *qle
                       uint32_t *qend, uint32_t *fstart, uint32_t *fend, uint32_t *second, uint32_t *second_family, size_t *n);
 int tdt_clip_mei_timing(tdt_clip *h, double *ms3);
 
+/* ---- exact per-base depth and the small-variant genotypes (TIDDIT_SMALL_VCF) ---------------------------- *
+ * The number of eligible reads with an aligned base (M = X) at every reference position, CIGAR-exact (csrc/tdt_pileup.hip); the
+ * definition is tiddit_amd/tiddit_pileup.py's, the genotype rule tiddit_amd/tiddit_small_vcf.py's.  A handle keeps ONE int32 per
+ * reference base plus a guard slot per contig in HBM (4 bytes per base; zeroed at create and reset) and TDT_PILE_SN_N uint64 counters:
+ *   [0] records  [1] eligible  [2] malformed  [3] no_cigar  [4] spans  [5] covered_bases  [6] clamped_spans
+ * Eligible: flag & 0xF04 == 0, tid >= 0, mapq >= min_mapq.  An eligible record is bounded and judged malformed exactly as tdt_snv does
+ * it, and also when tid >= n_contigs; a malformed record adds one to `malformed` and nothing else, one without CIGAR to `no_cigar`.
+ * Touching M = X stretches are one span; every span is clamped to the contig (`clamped_spans`: cut or dropped) and adds +1 at its
+ * start and -1 at its end.  Nothing outside raw[0, raw_len) is ever read.  The push entries take what tdt_snv's take: the device entry
+ * enqueues one launch on the context's stream and waits for nothing, the host entry uploads, runs the same kernel and returns when it
+ * is done.  tdt_pile_finish turns the differences into depths (an in-place prefix sum over all slots, three launches) and returns
+ * when it is done; a second finish changes nothing.  Behind it tdt_pile_depth reads out[n] depths of contig tid from base start on, and
+ * tdt_pile_genotype / tdt_pile_genotype_device take n rows (K1 = tid << 32 | P with P 1-based, SUPPORT) from host / device memory and
+ * write eight uint32 per row to out8 (device: on a 16-byte boundary; enqueued, nothing is waited for):
+ *   [0] DP0 = depth[tid][P - 1], 0 outside the contig  [1] OTHER  [2] PL 0/0  [3] PL 0/1  [4] PL 1/1  [5] GT index  [6] GQ
+ *   [7] 1 when SUPPORT > DP0.
+ * tdt_pile_counters synchronises the stream.  tdt_pile_timing: device milliseconds of the last finish's three launches (tile sums,
+ * carry, scan and write) and of the last tdt_pile_genotype launch.
+ * Refusals: TDT_E_ARG (null pointers, record offsets that decrease, n >= 2^31, a push behind the finish without a reset,
+ * tdt_pile_depth or a genotype entry before the finish), TDT_E_RANGE (2^24 contigs or more, a length of 2^31 or more, min_mapq outside
+ * 0 ... 255, a range of tdt_pile_depth outside the contig), TDT_E_NOMEM; a refused call leaves its outputs untouched.
+ * tdt_pile_sn_size() = TDT_PILE_SN_N. */
+#define TDT_PILE_SN_N 7
+typedef struct tdt_pile tdt_pile;
+int tdt_pile_create(tdt_ctx *ctx, int n_contigs, const int64_t *lengths, int min_mapq, tdt_pile **out);
+int tdt_pile_destroy(tdt_pile *h);
+int tdt_pile_reset(tdt_pile *h);
+int tdt_pile_push_device(tdt_pile *h, const void *const *d_arrays14, size_t n, size_t raw_len);
+int tdt_pile_push(tdt_pile *h, const uint16_t *flag, const int32_t *tid, const int32_t *pos, const uint8_t *mapq, const uint64_t *rec_off,
+                  size_t n, const uint8_t *raw, size_t raw_len);
+int tdt_pile_finish(tdt_pile *h);
+int tdt_pile_depth(tdt_pile *h, int tid, int64_t start, int64_t n, uint32_t *out);
+int tdt_pile_genotype(tdt_pile *h, const uint64_t *k1, const uint32_t *support, size_t n, uint32_t *out8);
+int tdt_pile_genotype_device(tdt_pile *h, const uint64_t *d_k1, const uint32_t *d_support, size_t n, uint32_t *d_out8);
+int tdt_pile_counters(tdt_pile *h, uint64_t *sn_out);
+int tdt_pile_timing(tdt_pile *h, double *ms4);
+size_t tdt_pile_sn_size(void);
+
 /* ---- alignment-record decode (host) ---------------------------------------------------------- *
  * Replaces the per-read pysam attribute access that feeds the path (read.reference_start,
  * reference_end, mapq, flag, next_reference_id, next_reference_start, isize, cigartuples[0]/[-1],

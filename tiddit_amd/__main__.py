@@ -391,6 +391,13 @@ def run_sv(args, version):
         print("error, TIDDIT_SNVS={}: {}".format(os.environ.get("TIDDIT_SNVS"), e))
         sys.exit(1)
     try:
+        from . import tiddit_small_vcf
+        small_vcf = tiddit_small_vcf.parse_switch(os.environ.get("TIDDIT_SMALL_VCF"), snvs, indels)
+    except ValueError as e:
+        # (the same)
+        print("error, TIDDIT_SMALL_VCF={}: {}".format(os.environ.get("TIDDIT_SMALL_VCF"), e))
+        sys.exit(1)
+    try:
         from . import tiddit_clips
         clips = tiddit_clips.parse_switch(os.environ.get("TIDDIT_CLIPS"))
     except ValueError as e:
@@ -470,9 +477,9 @@ def run_sv(args, version):
     contig_number = {c: i for i, c in enumerate(contigs)}
     contig_length = {c["SN"]: c["LN"] for c in bam_header["SQ"]}
     prefix = args.o
-    if indels_norm or snvs is not None or clips_align is not None or clips_far is not None:
-        # TIDDIT_INDELS_NORM / TIDDIT_SNVS / TIDDIT_CLIPS_ALIGN / TIDDIT_CLIPS_FAR: the contigs of the BAM header are matched to the FASTA's by name now — one
-        # that is missing or has another length ends the job before anything is made
+    if indels_norm or snvs is not None or small_vcf is not None or clips_align is not None or clips_far is not None:
+        # TIDDIT_INDELS_NORM / TIDDIT_SNVS / TIDDIT_SMALL_VCF / TIDDIT_CLIPS_ALIGN / TIDDIT_CLIPS_FAR: the contigs of the BAM header are matched to the
+        # FASTA's by name now — one that is missing or has another length ends the job before anything is made
         from . import refseq
         norm_fasta = FastaFile(args.ref)
         try:
@@ -482,6 +489,8 @@ def run_sv(args, version):
                 print("error, TIDDIT_INDELS_NORM=1: {}".format(e))
             elif snvs is not None:
                 print("error, TIDDIT_SNVS={}: {}".format(os.environ.get("TIDDIT_SNVS"), e))
+            elif small_vcf is not None:
+                print("error, TIDDIT_SMALL_VCF=1: {}".format(e))
             elif clips_align is not None:
                 print("error, TIDDIT_CLIPS_ALIGN={}: {}".format(os.environ.get("TIDDIT_CLIPS_ALIGN"), e))
             else:
@@ -534,6 +543,11 @@ def run_sv(args, version):
         # (the same: a fragment's two mates can lie on two shards, and its link would be lost.  TIDDIT_ALLELES alone stays allowed)
         print("error, TIDDIT_PHASE is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
               "keys on another rank")
+        sys.exit(1)
+    if multi and small_vcf is not None:
+        # (the same, in front of its partners' refusals: a base near a shard seam is covered by two shards' reads)
+        print("error, TIDDIT_SMALL_VCF is a one-process switch: the N-rank job (WORLD_SIZE > 1 or TIDDIT_FORCE_DIST=1) holds every shard's "
+              "reads on another rank")
         sys.exit(1)
     if multi and indels is not None:
         # (the same: an event's support is spread over the shards, and merging per-rank rows needs an exchange of keys)
@@ -721,13 +735,15 @@ def run_sv(args, version):
     if indels is not None:
         # TIDDIT_INDELS: ... and a key per small indel of the reads' CIGARs, one launch per batch
         tiddit_signal.INDELS = indels
-    if indels_norm or snvs is not None or clips_align is not None or clips_far is not None:
-        # TIDDIT_INDELS_NORM / TIDDIT_SNVS / TIDDIT_CLIPS_ALIGN / TIDDIT_CLIPS_FAR: the reference goes into HBM before the scan (every contig of the BAM
-        # header: read, uploaded, packed to 4-bit codes), ONCE: the indel kernel moves every event as far left as it allows, the SNV
-        # kernel compares every aligned base with it, the clip stage searches it for the sites' consensus, and all hold the same handle
+    if indels_norm or snvs is not None or small_vcf is not None or clips_align is not None or clips_far is not None:
+        # TIDDIT_INDELS_NORM / TIDDIT_SNVS / TIDDIT_SMALL_VCF / TIDDIT_CLIPS_ALIGN / TIDDIT_CLIPS_FAR: the reference goes into HBM before the scan (every
+        # contig of the BAM header: read, uploaded, packed to 4-bit codes), ONCE: the indel kernel moves every event as far left as it allows, the SNV
+        # kernel compares every aligned base with it, the small-variant VCF takes its deletion records' bases from it, the clip stage searches it for
+        # the sites' consensus, and all hold the same handle
         t_ref = time.time()
         reference, t_read, t_load = refseq.load_for_bam(norm_fasta, chromosomes, [contig_length[c] for c in chromosomes])
         T["reference into HBM (%s)" % " + ".join(k for k, on in (("TIDDIT_INDELS_NORM", indels_norm), ("TIDDIT_SNVS", snvs is not None),
+                                                                  ("TIDDIT_SMALL_VCF", small_vcf is not None),
                                                                   ("TIDDIT_CLIPS_ALIGN", clips_align is not None),
                                                                   ("TIDDIT_CLIPS_FAR", clips_far is not None)) if on)] = time.time() - t_ref
         T["  reference: file read (host)"] = t_read
@@ -738,6 +754,13 @@ def run_sv(args, version):
             # TIDDIT_SNVS: ... and a key per base that differs from the reference, one launch per batch
             tiddit_signal.SNVS = snvs
             tiddit_signal.SNV_REFERENCE = reference
+        if small_vcf is not None:
+            # TIDDIT_SMALL_VCF: ... and +1 / -1 at the ends of every eligible read's aligned spans, one launch per batch: one more element
+            # in ONE partner's setting, whose counter carries the handle back
+            if snvs is not None:
+                tiddit_signal.SNVS = snvs + ("depth",)
+            else:
+                tiddit_signal.INDELS = indels + ("depth",)
     if clips is not None:
         # TIDDIT_CLIPS: ... and a key per soft clip of the reads, one launch per batch
         tiddit_signal.CLIPS = clips
@@ -813,8 +836,10 @@ def run_sv(args, version):
     if indels is not None:
         # (behind the scan: coverage_data is final, no later stage writes into it)
         counter, tiddit_signal.INDEL_COUNTER = tiddit_signal.INDEL_COUNTER, None
+        pile = counter.depth                          # (TIDDIT_SMALL_VCF without TIDDIT_SNVS: the depth handle, else None)
         t = time.time()
-        tiddit_indels.main(counter, prefix, coverage_data, chromosomes, indels[0])
+        indel_kept = {} if small_vcf is not None else None
+        tiddit_indels.main(counter, prefix, coverage_data, chromosomes, indels[0], keep=indel_kept)
         T["small indels ({o}.indels.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_indels.STAGE_SECONDS.items()})
         STAGE_NOTES.update(tiddit_indels.STAGE_NOTES)
@@ -829,11 +854,22 @@ def run_sv(args, version):
     if snvs is not None:
         # (the same)
         counter, tiddit_signal.SNV_COUNTER = tiddit_signal.SNV_COUNTER, None
+        pile = counter.depth                          # (TIDDIT_SMALL_VCF: the depth handle, else None)
         t = time.time()
-        tiddit_snvs.main(counter, prefix, coverage_data, chromosomes, snvs[0])
+        snv_kept = {} if small_vcf is not None else None
+        tiddit_snvs.main(counter, prefix, coverage_data, chromosomes, snvs[0], keep=snv_kept)
         T["snv candidates ({o}.snvs.tab)"] = time.time() - t
         T.update({"  " + k: v for k, v in tiddit_snvs.STAGE_SECONDS.items()})
         STAGE_NOTES.update(tiddit_snvs.STAGE_NOTES)
+    if small_vcf is not None:
+        # TIDDIT_SMALL_VCF: behind the two stages whose finished rows it genotypes — the prefix sum over the difference array the scan
+        # left, one gather launch per table, the records' text
+        t = time.time()
+        tiddit_small_vcf.main(pile, prefix, chromosomes, tiddit_clip_vcf.header_parts(bam_header, sample_id, version),
+                              snv_kept["rows"] if snvs is not None else None, indel_kept["rows"] if indels is not None else None, reference, indels_norm)
+        T["small variants ({o}.small.vcf)"] = time.time() - t
+        T.update({"  " + k: v for k, v in tiddit_small_vcf.STAGE_SECONDS.items()})
+        STAGE_NOTES.update(tiddit_small_vcf.STAGE_NOTES)
     if clips is not None:
         # (the same)
         counter, tiddit_signal.CLIP_COUNTER = tiddit_signal.CLIP_COUNTER, None

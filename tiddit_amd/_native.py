@@ -204,6 +204,18 @@ SYMBOLS = {
     "tdt_snv_timing": (_i, [_P, _P]),
     "tdt_snv_reserve_stats": (_i, [_P, _P]),
     "tdt_snv_sn_size": (_sz, []),
+    "tdt_pile_create": (_i, [_P, _i, _P, _i, _PP]),
+    "tdt_pile_destroy": (_i, [_P]),
+    "tdt_pile_reset": (_i, [_P]),
+    "tdt_pile_push_device": (_i, [_P, _P, _sz, _sz]),
+    "tdt_pile_push": (_i, [_P] * 6 + [_sz, _P, _sz]),
+    "tdt_pile_finish": (_i, [_P]),
+    "tdt_pile_depth": (_i, [_P, _i, _i64, _i64, _P]),
+    "tdt_pile_genotype": (_i, [_P, _P, _P, _sz, _P]),
+    "tdt_pile_genotype_device": (_i, [_P, _P, _P, _sz, _P]),
+    "tdt_pile_counters": (_i, [_P, _P]),
+    "tdt_pile_timing": (_i, [_P, _P]),
+    "tdt_pile_sn_size": (_sz, []),
     "tdt_clip_create": (_i, [_P, _i, _i, _i, _sz, _PP]),
     "tdt_clip_destroy": (_i, [_P]),
     "tdt_clip_reset": (_i, [_P]),

@@ -14,6 +14,7 @@ class KeyedCounter:
     DEFAULT_SUPPORT = 1
     ROW_DTYPES = (numpy.uint64, numpy.uint64, numpy.uint32, numpy.uint32)      # K1, K2 with bit 0 clear, SUPPORT, REV
     N_TIMES = 4
+    depth = None                # a tiddit_pileup.PileupDepth the scan filled beside this counter (TIDDIT_SMALL_VCF): the caller's to finish and close
 
     def _create(self, ctx, *args):
         """``PREFIX_create(ctx, *args, &handle)``"""

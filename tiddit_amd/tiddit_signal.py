@@ -406,6 +406,13 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         snvs = tiddit_snvs.SnvCounter(len(names), SNV_REFERENCE, SNVS[1], SNVS[2], capacity=min(max(os.path.getsize(bam_file_name) // 16, 1 << 16), 1 << 26),
                                       ctx=getattr(reader, "ctx", None))
         T["snv keys (push)"] = 0.0
+    pile = None
+    if (SNVS is not None and SNVS[3:] == ("depth",)) or (INDELS is not None and INDELS[2:] == ("depth",)):
+        # TIDDIT_SMALL_VCF (an element more in its partners' settings, as the phase options ride on the allele sites'): one int32 per reference
+        # base in HBM, counted at the partners' minimum MAPQ; every batch costs one more launch on the columns and bytes it already holds there
+        from . import tiddit_pileup
+        pile = tiddit_pileup.PileupDepth(lengths, (SNVS if SNVS is not None else INDELS)[1], ctx=getattr(reader, "ctx", None))
+        T["pileup spans (push)"] = 0.0
     clipc = None
     if CLIPS is not None:
         # TIDDIT_CLIPS: a key store in HBM; every batch costs one more launch on the columns and bytes it already holds there
@@ -505,6 +512,11 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                     t3b = time.time()
                     T["snv keys (push)"] += t3b - t3
                     t3 = t3b
+                if pile is not None:                            # (the same, beside the SNV push; no store: nothing is ever waited for)
+                    pile.push_device_batch(b)
+                    t3b = time.time()
+                    T["pileup spans (push)"] += t3b - t3
+                    t3 = t3b
                 if clipc is not None:                           # (the same, beside the SNV push)
                     clipc.push_device_batch(b)
                     t3b = time.time()
@@ -555,6 +567,10 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
                 t1b = time.time()
                 snvs.push_host_batch(b)
                 T["snv keys (push)"] += time.time() - t1b
+            if pile is not None:
+                t1b = time.time()
+                pile.push_host_batch(b)
+                T["pileup spans (push)"] += time.time() - t1b
             if clipc is not None:
                 t1b = time.time()
                 clipc.push_host_batch(b)
@@ -633,6 +649,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
             indels.close()
         if snvs is not None:
             snvs.close()
+        if pile is not None:
+            pile.close()
         if clipc is not None:
             clipc.close()
         if strc is not None:
@@ -659,6 +677,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
         indels.ctx.sync()                                       # (the same)
     if snvs is not None:
         snvs.ctx.sync()                                         # (the same)
+    if pile is not None:
+        pile.ctx.sync()                                         # (the same)
     if clipc is not None:
         clipc.ctx.sync()                                        # (the same)
     if strc is not None:
@@ -669,6 +689,8 @@ def _scan(bam_file_name, min_q, max_ins, min_contig, min_anchor_len, min_clip_le
     DUP_COUNTER = dups                                          # (the same: the caller runs its finish and closes it)
     INDEL_COUNTER = indels                                      # (the same)
     SNV_COUNTER = snvs                                          # (the same)
+    if pile is not None:
+        (snvs if snvs is not None else indels).depth = pile     # (the same: the counter beside which it was filled carries it to the caller)
     CLIP_COUNTER = clipc                                        # (the same)
     if STR is not None:
         STR.counter = strc                                      # (the same, in the tap that asked for it)
@@ -725,6 +747,8 @@ QC = None                   # True: the scan also fills the read-level QC tables
 QC_COUNTER = None           # that counter after the last scan that had QC set (the caller reads and closes it), else None
 DUPS = None                 # True: the scan also stores a duplicate key per fragment and pair (tiddit_dup.DupCounter), one launch per batch
 DUP_COUNTER = None          # that counter after the last scan that had DUPS set (the caller runs its finish and closes it), else None
+# (SNVS or INDELS with one more element, "depth": the scan also adds every eligible read's aligned spans to a per-base difference array —
+#  tiddit_pileup.PileupDepth, at that setting's min_mapq, one launch per batch — and leaves the handle in that counter's ``depth``)
 INDELS = None               # (min_support, min_mapq): the scan also stores a key per small indel of the reads' CIGARs (tiddit_indels.IndelCounter), one launch per batch
 INDEL_REFERENCE = None      # a refseq.RefSeq: the indel counter of the scan left-normalises its events against it (TIDDIT_INDELS_NORM)
 SNVS = None                 # (min_support, min_mapq, min_bq): the scan also stores a key per base that differs from SNV_REFERENCE (tiddit_snvs.SnvCounter), one launch per batch

@@ -237,13 +237,16 @@ def summary_line(counts):
         *(int(c[SN_INDEX[k]]) for k in ("records", "eligible", "aligned_bases", "mismatches", "distinct_events", "reported_events", "noisy_reads", "malformed")))
 
 
-def main(counter, prefix, coverage_data, names, S):
-    """the stage behind the scan: the sort and the run lengths on the device, the file and the summary line"""
+def main(counter, prefix, coverage_data, names, S, keep=None):
+    """the stage behind the scan: the sort and the run lengths on the device, the file and the summary line; ``keep``: a dict that gets
+    the finished rows under ``"rows"`` (TIDDIT_SMALL_VCF genotypes them)"""
     STAGE_SECONDS.clear()
     STAGE_NOTES.clear()
     t = time.time()
     counts = counter.finish(S)
     rows = counter.rows()
+    if keep is not None:
+        keep["rows"] = rows
     ms = counter.timing()
     asks, grows, cap = counter.reserve_stats()
     min_mapq, min_bq = counter.min_mapq, counter.min_bq
